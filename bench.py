@@ -16,14 +16,18 @@ library's own in-place ncclAllGather (RCCL over xGMI, mcx_exchange_rccl_*).
   python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c5|c3-murray]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries: `end_to_end` (the same job with every sample
-row copied out to host memory), `roofline` with hardware counters collected live by child `rocprofv3 --pmc`
-passes of this same script -- of the kernel that actually ran: its name is taken from the child's own kernel
-trace, and without live counters `frac` is null --, the other configurations as `config.other_configs`,
-`host_callback` (the same shape with a user likelihood on the host), `cpu_baseline` (the CPU oracle on the
-host cores) and, as the LAST key, `summary`: every headline number again in a few hundred bytes, because
-whoever keeps only the tail of a long line should still see them.  What each field means and how it is
-computed is written down once, in DESIGN.md section 6 ("the bench line"), not in the line.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps jobs and prints the line (`value`,
+`ms_per_step`, ...); everything else is measured only with --full.  At N = 1 the line of a --full run also carries:
+`end_to_end` (the same job with every sample row copied out to host memory), `roofline` with hardware counters
+collected live by child `rocprofv3 --pmc` passes of this same script -- of the kernel that actually ran: its name
+is taken from the child's own kernel trace, and without live counters `frac` is null --, the other configurations
+as `config.other_configs`, `host_callback` (the same shape with a user likelihood on the host), `cpu_baseline`
+(the CPU oracle on the host cores); at N > 1 the reference's exchange schedule, a Murray configuration and strong
+scaling.  The LAST key is `summary`: every headline number again in a few hundred bytes, because whoever keeps
+only the tail of a long line should still see them.  What each field means and how it is computed is written down
+once, in DESIGN.md section 6 ("the bench line"), not in the line.
+
+  --dump-outputs DIR   after the timed steps, what the last of them computed, as float32 .npy files (dump_outputs)
 """
 import argparse
 import csv
@@ -379,6 +383,42 @@ class Job:
 
 
 # ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, so that two builds can be compared output for output
+# ---------------------------------------------------------------------------------------------
+DUMP_BYTES = 60 << 20  # all files together: under 64 MB with their headers
+DUMP_SEED = 20261016
+DUMP_MAX_STEPS = 64
+
+
+def dump_outputs(eng, d, n, nsamp, emit, out_dir, suffix=""):
+    """What a caller of run() receives after the last timed job, as float32 out_dir/<name><suffix>.npy: the chains' final
+    `state` and `loglike`, their running `mean` and `var` and, with rows kept, `samples` (step, chain, d + 1).  A whole job's
+    rows do not fit (4.5 GB at C3): a fixed, seeded choice of main-loop steps, as many as half the budget holds; should the
+    per-chain arrays alone pass the other half, a fixed, seeded choice of chains too, the same in every file.  The inputs
+    are the same on every run with the same arguments."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    half = DUMP_BYTES // 2
+    chains = np.arange(n)
+    if n * (3 * d + 1) * 4 > half:
+        chains = np.sort(rng.choice(n, half // ((3 * d + 1) * 4), replace=False))
+    arrays = dict(state=eng.state[chains], loglike=eng.loglike[chains], mean=eng.mean[chains], var=eng.var[chains])
+    steps = []
+    if emit and nsamp > 0:
+        k = min(nsamp, DUMP_MAX_STEPS, half // (len(chains) * (d + 1) * 4))
+        steps = np.sort(rng.choice(nsamp, k, replace=False))
+        arrays["samples"] = np.stack([eng.samples_range(int(s), 1)[chains] for s in steps])
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        fn = name + suffix + ".npy"
+        np.save(os.path.join(out_dir, fn), np.ascontiguousarray(a, dtype=np.float32))
+        files[fn] = list(a.shape)
+    return dict(files=files, chains="all" if len(chains) == n else "%d of %d, seeded" % (len(chains), n),
+                sample_steps=[int(s) for s in steps])
+
+
+# ---------------------------------------------------------------------------------------------
 # N > 1 without a launcher: this process starts the N ranks itself (VERDICT r4 item 1)
 # ---------------------------------------------------------------------------------------------
 EXIT_TOO_FEW_DEVICES = 66   # a rank found fewer GPUs than ranks (and no --one-device)
@@ -543,9 +583,14 @@ def main():
     ap.add_argument("--nsamp", type=int, default=-1)
     ap.add_argument("--pl", type=float, default=-1.0)
     ap.add_argument("--no-samples", action="store_true", help="summary-only mode (not the default metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not spawn rocprofv3 --pmc children; read profiles/ instead")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip end_to_end and the other configurations")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the host-pinit timing, the roofline and its "
+                    "counters, the CPU baseline and the extra legs (other configurations, end to end, ...); off by default")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed "
+                    "as DIR/<name>.npy (float32; a fixed, seeded sample where the whole would pass 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not spawn rocprofv3 --pmc children")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip end_to_end, the other configurations and the "
+                    "N > 1 legs")
     ap.add_argument("--keep-pmc", default="", help="directory in which to keep the rocprofv3 output of the PMC passes")
     ap.add_argument("--max-segment", type=int, default=0, help="cap on steps per fused launch (0 = engine default)")
     ap.add_argument("--exchange", default="rccl", choices=("rccl", "staged"),
@@ -566,6 +611,8 @@ def main():
                     "leg (reference schedule, Murray configuration, strong scaling) is begun")
     ap.add_argument("--exchange-fallback-reason", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
         # called the way the driver calls it (`python3 bench.py --gpus 8 ...`, no launcher): be the launcher
@@ -785,13 +832,19 @@ def main():
     cnt = eng.counters
     chain_steps = float(world) * n * (nburn + nsamp) * args.steps
     value = chain_steps / dt
-    value_host_pinit = chain_steps / timed(job, args.steps, host_pinit=True)  # PCIe-inclusive input, never `value`
+    outputs = None
+    if args.dump_outputs:
+        outputs = dump_outputs(eng, d, n, nsamp, emit, args.dump_outputs, "_shard%d" % rank if world > 1 else "")
+    extras = args.full and not args.no_extras
+    value_host_pinit = None
+    if args.full:
+        value_host_pinit = chain_steps / timed(job, args.steps, host_pinit=True)  # PCIe-inclusive input, never `value`
 
     # N > 1: the same job with the reference's own exchange schedule (an all-gather at every sync point,
     # src/mcpar.cc:127-140, overlapped with the next segment) next to the default, which gathers only the
     # snapshots a Murray step or the end of the run reads (bit-identical results: tests/test_gpu_multishard.py)
     ref_sched = None
-    if world > 1 and not args.no_extras and within_budget("reference_schedule"):
+    if world > 1 and extras and within_budget("reference_schedule"):
         eng.set_option(E.OPT_EAGER_EXCHANGE, 1)
         job.run()
         ke = max(1, args.steps // 2)
@@ -809,8 +862,10 @@ def main():
         j.eng.set_option(E.OPT_PROFILE, 0)
         return {k: {f: pr[k][f] - base[k][f] for f in ("ms", "launches", "chain_steps")} for k in pr}, j.eng.counters
 
-    prof, pcnt = profiled(job)  # every rank runs it (it contains the same collectives)
-    sync()
+    prof = pcnt = None
+    if args.full:
+        prof, pcnt = profiled(job)  # every rank runs it (it contains the same collectives)
+        sync()
 
     def murray_block(c, nn, pr, cn):
         """k_remote_sweep in ALGORITHMIC flops (n_act N (3d+4) per pass; DESIGN.md 6 "the bench line")"""
@@ -846,7 +901,7 @@ def main():
 
     roofline = murray = cpu = end_to_end = claims = host_cb = device_vl = None
     others = {}
-    if rank == 0:
+    if rank == 0 and prof is not None:
         fm, fb, rs = prof["fused_main"], prof["fused_burn"], prof["run_small"]
         if rs["launches"] > 0 and rs["ms"] > 0:
             # small-n mode: burn-in and main-loop steps run in ONE launch of k_run_small (mcx_persist.hpp)
@@ -874,7 +929,7 @@ def main():
 
     # ---- N > 1: a Murray (pl < 1) configuration over the same ranks, first-class next to the R-local number ----
     murray_multi = None
-    if world > 1 and cfg["pl"] >= 1.0 and not args.no_extras and within_budget("murray"):
+    if world > 1 and cfg["pl"] >= 1.0 and extras and within_budget("murray"):
         job.close()
         c5 = dict(CONFIGS["c5"])
         j5 = make_job(c5, c5["n"], True)
@@ -893,7 +948,7 @@ def main():
 
     # ---- N > 1: the same total job split over the ranks (strong scaling; `value` above is weak scaling) ----------
     strong_multi = None
-    if world > 1 and not args.strong and not args.no_extras and total % world == 0 and within_budget("strong_scaling"):
+    if world > 1 and not args.strong and extras and total % world == 0 and within_budget("strong_scaling"):
         if job is not None:
             job.close()
             job = None
@@ -918,7 +973,7 @@ def main():
 
     # ---- N = 1 extras: end to end, other configurations, counters, CPU baseline ---------------------------
     if world == 1 and rank == 0:
-        if emit and not args.no_extras:
+        if emit and extras:
             # the reference's product is the samples on the host (src/mcout.cc:30-94): the same job with every row
             # streamed out through the engine's sample sink (mcx_set_sink: device ring -> interleave -> pinned host
             # memory on a copy stream, overlapped with the steps), and -- for comparison -- the older way, the whole
@@ -990,7 +1045,7 @@ def main():
                               copy_after_the_run=dict(value=n * (nburn + nsamp) / dc, ms_per_step=dc * 1e3), text=text)
         job.close()
         job = None
-        if not args.no_extras:
+        if extras:
             for name in sorted(CONFIGS):
                 if name == args.config:
                     continue
@@ -1118,11 +1173,11 @@ def main():
                                                          GRBM_GUI_ACTIVE=pmc[kg]["GRBM_GUI_ACTIVE"],
                                                          frac_of_simd_cycles=pmc[kg]["SQ_VALU_MFMA_BUSY_CYCLES"] / (N_SIMD * cyc3),
                                                          note="mean over the dispatches of the measured child job (all pass sizes)")
-        if not args.no_extras and args.config == "c3" and not args.chains and args.dim == 0:
+        if extras and args.config == "c3" and not args.chains and args.dim == 0:
             claims = claims_under_the_clock(M, E, dt / args.steps * 1e3, n, nburn, nsamp)
             host_cb = host_callback_leg(M, E, cfg, n)
             device_vl = device_vlfunc_leg(M, E, cfg, n, dt / args.steps * 1e3, emit)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(cfg)
 
     if rank == 0:
@@ -1195,6 +1250,7 @@ def main():
                        "full_cov": (claims or {}).get("full_cov"), "strong_proxy": sp,
                        "accept_rate_reference_shape": (claims or {}).get("accept_rate_reference_shape")},
             "end_to_end": end_to_end, "host_callback": host_cb, "device_vlfunc": device_vl, "murray_roofline": murray, "cpu_baseline": cpu, "roofline": roofline,
+            "full": args.full, "outputs": outputs,
             "summary": summary,  # LAST: whoever keeps only the tail of this line still has every headline number
         }
         os.write(json_fd, (json.dumps(out) + "\n").encode())

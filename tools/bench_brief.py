@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Runs bench.py with the given arguments and prints only the figures of its `summary` and of the Murray sweeps (the whole
+"""Runs bench.py --full with the given arguments and prints only the figures of its `summary` and of the Murray sweeps (the whole
 line is a screenful).  usage: python tools/bench_brief.py --config c5 [...]"""
 import json
 import os
@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + sys.argv[1:], capture_output=True, text=True)
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + sys.argv[1:], capture_output=True, text=True)
 if out.returncode:
     sys.stderr.write(out.stderr[-2000:])
     sys.exit(out.returncode)
