@@ -670,6 +670,36 @@ __device__ __forceinline__ uint32_t group_bcast(uint32_t v, uint32_t owner, int 
   return (uint32_t)r;
 }
 
+// group_bcast of four values from the same owner: one wave-uniform switch instead of four
+template <int LPC>
+__device__ __forceinline__ void group_bcast4(uint32_t v[4], uint32_t owner, int q)
+{
+  if (LPC <= 2) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = group_bcast<LPC>(v[k], owner, q);
+    return;
+  }
+  int r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = (int)v[k];
+  switch (owner & 3u) {
+#define MCX_BCAST4(CTRL) for (int k = 0; k < 4; ++k) r[k] = __builtin_amdgcn_update_dpp(0, r[k], CTRL, 0xF, 0xF, true)
+  case 0: MCX_BCAST4(0x00); break;
+  case 1: MCX_BCAST4(0x55); break;
+  case 2: MCX_BCAST4(0xAA); break;
+  default: MCX_BCAST4(0xFF); break;
+#undef MCX_BCAST4
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (LPC >= 8) {  // (as group_bcast)
+      const int other = __builtin_amdgcn_update_dpp(0, r[k], 0x141, 0xF, 0xF, true);
+      r[k] = ((int)(owner >> 2) == (q >> 2)) ? r[k] : other;
+    }
+    v[k] = (uint32_t)r[k];
+  }
+}
+
 // PREGEN: the normals and accept thresholds of the launch were produced beforehand by k_gen_normals
 // (same functions, same bits) and are streamed in with a 4-step register prefetch ring.  With few
 // chains the fused kernel is bound by the latency of one wave's instruction stream, two thirds of which
@@ -708,21 +738,31 @@ __device__ __forceinline__ float quad_bcast(float v, int qq)
   return as_f32((uint32_t)r);
 }
 
-template <int LPC, bool MAIN, int LIK, bool PREGEN, bool FULL>
+// Sample rows of a fused launch, fixed at compile time so that the step holds no test for them: EMIT_ANY decides per step
+// at run time (the kernels other than the plain hot-path one); the others are chosen per launch by the host --
+// EMIT_NONE: no rows (burn-in, or samples not kept), EMIT_EVERY: a row per step (samp_stride <= 1), EMIT_THIN: a row
+// when (isamp0 + s) % samp_stride == 0.  EMIT_EVERY / EMIT_THIN store from every lane, without exec-mask regions:
+// lanes that own no parameters (d < 4 LPC) store their row to a.trash (16 B per lane, a.n * LPC lanes), every lane
+// of a chain stores the chain's (same) log-likelihood.
+enum EmitMode : int { EMIT_ANY = 0, EMIT_NONE = 1, EMIT_EVERY = 2, EMIT_THIN = 3 };
+
+template <int LPC, bool MAIN, int LIK, bool PREGEN, bool FULL, int EMIT = EMIT_ANY>
 __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a);
 
 // (the body returns early for threads without a chain, with the wavefront's accepted proposals otherwise; the tuner
 // at the end is every thread's)
-template <int LPC, bool MAIN, int LIK = LIK_ROSEN1, bool PREGEN = false, bool FULL = false>
+template <int LPC, bool MAIN, int LIK = LIK_ROSEN1, bool PREGEN = false, bool FULL = false, int EMIT = EMIT_ANY>
 __global__ __launch_bounds__(BLOCK) void k_fused_fast(const SegArgs a)
 {
-  const uint32_t wacc = fused_fast_body<LPC, MAIN, LIK, PREGEN, FULL>(a);
+  const uint32_t wacc = fused_fast_body<LPC, MAIN, LIK, PREGEN, FULL, EMIT>(a);
   tuner_epilogue(a, wacc);
 }
 
-template <int LPC, bool MAIN, int LIK, bool PREGEN, bool FULL>
+template <int LPC, bool MAIN, int LIK, bool PREGEN, bool FULL, int EMIT>
 __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
 {
+  static_assert(EMIT == EMIT_ANY || !PREGEN, "the small-n kernel keeps its run-time emission choice");
+  static_assert(MAIN || EMIT == EMIT_ANY || EMIT == EMIT_NONE, "burn-in stores no rows");
   static_assert(LIK == LIK_ROSEN1 || LIK == LIK_GAUSS || LIK == LIK_MIX || (LIK == LIK_ROSEN2F && !PREGEN && !FULL) || (LIK == LIK_USER && !PREGEN),
                 "fast path: Rosenbrock1, diagonal Gaussian, a mixture of <= 8 unit Gaussians, (plain kernel only) the overlapping Rosenbrock, or a user's source");
   static_assert(!(FULL && PREGEN), "the pre-generated normals are laid out for diagonal proposals");
@@ -736,6 +776,10 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
 #endif
 #ifndef MCX_FAST_UNROLL4
 #define MCX_FAST_UNROLL4 1
+#endif
+// MCX_TAKE_SELECT: the acceptance as selects (1) or as the compiler's branch (0) -- see the step
+#ifndef MCX_TAKE_SELECT
+#define MCX_TAKE_SELECT 0
 #endif
   constexpr bool TREGS = FULL && LPC <= 4 && (MCX_FULL_T_REGS != 0);
   __shared__ __attribute__((aligned(16))) float4 lds_T[FULL && !TREGS ? 4 * LPC * LPC : 1];
@@ -811,8 +855,30 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
   float *sx = a.samp_x ? a.samp_x + off : nullptr;
   float *sl = a.samp_x ? a.samp_ly + chain : nullptr;
   const size_t sx_stride = (size_t)a.n * d, sl_stride = (size_t)a.n;
-  float *sxv = (PREGEN && a.samp_x) ? (live ? a.samp_x + off : a.trash + 4 * gid) : nullptr;  // per-lane pointer
+  float *sxv = ((PREGEN || EMIT == EMIT_EVERY || EMIT == EMIT_THIN) && a.samp_x) ? (live ? a.samp_x + off : a.trash + 4 * gid) : nullptr;  // per-lane pointer
   const size_t sxv_stride = live ? sx_stride : 0;
+  float *slv = a.samp_ly + chain;  // (EMIT_EVERY / EMIT_THIN: every lane of the chain)
+  // EMIT_THIN: steps to the next kept one (a wave-uniform countdown), and the first kept row
+  int thin_wait = 0;
+  if (EMIT == EMIT_THIN) {
+    const int ph = a.isamp0 % a.samp_stride;
+    thin_wait = ph == 0 ? 0 : a.samp_stride - ph;
+    const size_t row = (size_t)((a.isamp0 + thin_wait) / a.samp_stride);
+    sxv += row * sxv_stride;
+    slv += row * sl_stride;
+  }
+  // snapshot for the next exchange after step snap_after (src/mcpar.cc:202-208), winv_s = that step's 1/pwgt
+  auto snapshot = [&](float winv_s) {
+    if (live) {
+      const f32x2 w2 = splat2(winv_s);
+      const f32x2 ve = se * w2, vo = so * w2;
+      float4 *slot = reinterpret_cast<float4 *>(a.musig_own + 2 * off);
+      slot[0] = make_float4(me.x, ve.x, mo.x, vo.x);
+      slot[1] = make_float4(me.y, ve.y, mo.y, vo.y);
+      // the run's last step: the variances as mcx_get_var returns them (k_variance otherwise)
+      if (a.sig_out) *reinterpret_cast<float4 *>(a.sig_out + off) = make_float4(ve.x, vo.x, ve.y, vo.y);
+    }
+  };
 
   // one Metropolis step given this lane's four normals (ze = z0,z2; zo = z1,z3) and the log of the acceptance draw
   auto step = [&](int s, f32x2 ze, f32x2 zo, float u, float winv_s) {
@@ -933,6 +999,12 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
       lyt = 0.0f - group_sum<LPC>(acc);
     }
     // src/mcpar.cc:62-75 (cfac = 1 for local proposals): log u < ly' - ly
+    // The acceptance: left to itself the compiler makes a divergent branch of it -- one exec-mask region per step, the
+    // taken side moving (pe, po, lyt) into place and computing the Welford differences from them.  With the pin
+    // (MCX_TAKE_SELECT=1) the trial values are opaque, there is nothing to move, and the step is one basic block of
+    // selects: 7 more VALU instructions per 4 steps, v_cndmask at 4.4 cycles where the moves cost 2.6.  Timed in turn
+    // on one MI355X (headline job, 4 runs each): selects 2.00 ms, branch 1.98 ms -- the branch stays.
+    if (MCX_TAKE_SELECT && EMIT != EMIT_ANY) asm volatile("" : "+v"(pe), "+v"(po), "+v"(lyt));
     const bool take = accept_local(lyt, ly, u);
     xe = take ? pe : xe;
     xo = take ? po : xo;
@@ -946,15 +1018,23 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
       mo = fma2(dO, w2, mo);
       se = fma2(de, xe - me, se);
       so = fma2(dO, xo - mo, so);
-      if (s == a.snap_after && live) {  // snapshot for the next exchange (src/mcpar.cc:202-208)
-        const f32x2 ve = se * w2, vo = so * w2;
-        float4 *slot = reinterpret_cast<float4 *>(a.musig_own + 2 * off);
-        slot[0] = make_float4(me.x, ve.x, mo.x, vo.x);
-        slot[1] = make_float4(me.y, ve.y, mo.y, vo.y);
-        // the run's last step: the variances as mcx_get_var returns them (k_variance otherwise)
-        if (a.sig_out) *reinterpret_cast<float4 *>(a.sig_out + off) = make_float4(ve.x, vo.x, ve.y, vo.y);
-      }
-      if (sx) {  // src/mcpar.cc:177-182
+      // (the step-loop drivers without pre-generated normals split the launch's steps at snap_after instead)
+      if (PREGEN && s == a.snap_after) snapshot(winv_s);
+      if (EMIT == EMIT_EVERY) {  // src/mcpar.cc:177-182
+        *reinterpret_cast<float4 *>(sxv) = make_float4(xe.x, xo.x, xe.y, xo.y);
+        *slv = ly;
+        sxv += sxv_stride;
+        slv += sl_stride;
+      } else if (EMIT == EMIT_THIN) {
+        if (thin_wait == 0) {  // (wave-uniform)
+          *reinterpret_cast<float4 *>(sxv) = make_float4(xe.x, xo.x, xe.y, xo.y);
+          *slv = ly;
+          sxv += sxv_stride;
+          slv += sl_stride;
+          thin_wait = a.samp_stride;
+        }
+        --thin_wait;
+      } else if (EMIT == EMIT_ANY && sx) {  // src/mcpar.cc:177-182
         if (PREGEN && a.samp_stride <= 1) {
           // latency-bound mode: no exec-mask regions -- idle lanes store to their trash slot, every lane
           // of the chain stores the (same) log-likelihood
@@ -1011,31 +1091,39 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
       const float lu = as_f32(group_bcast<LPC>(as_u32(mine), blk & (uint32_t)(LPC - 1), q));
       step(s, ze, zo, lu, wthis);
     };
+    // The snapshot is taken between two runs of the step loop, [0, snap_after] and the rest, rather than tested for in
+    // every step (one copy of the loop: the second pass starts where the first ended)
+    const bool snap = MAIN && a.snap_after >= 0 && a.snap_after < a.nsteps;
     int s = 0;
+#pragma nounroll
+    for (int pass = 0; pass < (MAIN ? 2 : 1); ++pass) {
+      const int hi = (pass == 0 && snap) ? a.snap_after + 1 : a.nsteps;
 #if MCX_FAST_UNROLL4
-    // Four steps at a time from a step index that is a multiple of 4 on: which of the block's four logs a step takes is then
-    // known at compile time, and the lane that holds them is looked up once per block instead of once per step (two
-    // wave-uniform switches per step otherwise: some ten scalar branches and two moves)
-    if (!FULL) {
-      for (; s < a.nsteps && ((a.t0 + (uint32_t)s) & 3u); ++s) one_step(s);
-      for (; s + 4 <= a.nsteps; s += 4) {
-        const uint32_t t = a.t0 + (uint32_t)s, blk = t >> 2;
-        refresh(blk);
-        const uint32_t holder = blk & (uint32_t)(LPC - 1);
-        const float lu4[4] = {as_f32(group_bcast<LPC>(as_u32(al01.x), holder, q)), as_f32(group_bcast<LPC>(as_u32(al01.y), holder, q)),
-                              as_f32(group_bcast<LPC>(as_u32(al23.x), holder, q)), as_f32(group_bcast<LPC>(as_u32(al23.y), holder, q))};
+      // Four steps at a time from a step index that is a multiple of 4 on: which of the block's four logs a step takes is then
+      // known at compile time, and the lane that holds them is looked up once per block instead of once per step (two
+      // wave-uniform switches per step otherwise: some ten scalar branches and two moves)
+      if (!FULL) {
+        for (; s < hi && ((a.t0 + (uint32_t)s) & 3u); ++s) one_step(s);
+        for (; s + 4 <= hi; s += 4) {
+          const uint32_t t = a.t0 + (uint32_t)s, blk = t >> 2;
+          refresh(blk);
+          const uint32_t holder = blk & (uint32_t)(LPC - 1);
+          uint32_t lu4[4] = {as_u32(al01.x), as_u32(al01.y), as_u32(al23.x), as_u32(al23.y)};
+          group_bcast4<LPC>(lu4, holder, q);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float wthis = wnext;
-          if (MAIN) wnext = wtab[a.isamp0 + s + u + 1];
-          f32x2 ze, zo;
-          normal4_packed(philox4x32_10(t + (uint32_t)u, g, (uint32_t)q, 0u, a.seed, ST_LOCAL), ze, zo);
-          step(s + u, ze, zo, lu4[u], wthis);
+          for (int u = 0; u < 4; ++u) {
+            const float wthis = wnext;
+            if (MAIN) wnext = wtab[a.isamp0 + s + u + 1];
+            f32x2 ze, zo;
+            normal4_packed(philox4x32_10(t + (uint32_t)u, g, (uint32_t)q, 0u, a.seed, ST_LOCAL), ze, zo);
+            step(s + u, ze, zo, as_f32(lu4[u]), wthis);
+          }
         }
       }
-    }
 #endif
-    for (; s < a.nsteps; ++s) one_step(s);
+      for (; s < hi; ++s) one_step(s);
+      if (pass == 0 && snap) snapshot(wtab[a.isamp0 + a.snap_after]);
+    }
   } else {
     // Batches of P steps, double buffered: at the top of a batch every load of it (issued one whole
     // batch earlier) is awaited at once and moved to `cur`, then the loads of the next batch are issued,

@@ -263,6 +263,12 @@ static int launch_fused(mcx_engine *e, bool main, const SegArgs &a, hipStream_t 
     int bpl = e->opt_bpl;
     if (bpl == 0) bpl = (lik == LIK_MIX && lpc == 8) ? 2 : 1;
     while (bpl > lpc) bpl >>= 1;
+    if (fast && a.samp_x && a.d < 4 * lpc) {  // the plain hot-path kernel's lanes without parameters store their rows here
+      MCXCHK(e->trash.alloc(4 * (size_t)a.n * lpc));
+      SegArgs b = a;
+      b.trash = e->trash.p;
+      return launch_fused_plain(lpc, lik, main, b, st, fast, bpl, e->opt_bpl);
+    }
     return launch_fused_plain(lpc, lik, main, a, st, fast, bpl, e->opt_bpl);
   }
   // generator and step kernel alternate on the engine's stream (overlapping them on two streams was

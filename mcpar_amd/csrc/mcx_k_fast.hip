@@ -1,14 +1,19 @@
-// mcx_k_fast.hip -- instantiations of the hot-path kernel k_fused_fast<LPC, MAIN, LIK> (mcx_device.hpp)
+// mcx_k_fast.hip -- instantiations of the hot-path kernel k_fused_fast<LPC, MAIN, LIK, ..., EMIT> (mcx_device.hpp)
 #include "mcx_launch.hpp"
 
 using namespace mcx;
 
+// the sample rows' mode (EmitMode) is chosen here, per launch: burn-in and main segments without rows EMIT_NONE,
+// rows every step EMIT_EVERY, thinned EMIT_THIN -- the only main-loop instances the engine can ask for
 template <int LPC, int LIK>
 static hipError_t go(bool main, const SegArgs &a, hipStream_t st)
 {
   const dim3 grid((unsigned)(((size_t)a.n * LPC + BLOCK - 1) / BLOCK)), block(BLOCK);
-  if (main) hipLaunchKernelGGL((k_fused_fast<LPC, true, LIK>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_fused_fast<LPC, false, LIK>), grid, block, 0, st, a);
+  if (a.samp_x && a.d < 4 * LPC && !a.trash) return hipErrorInvalidValue;  // idle lanes store to a.trash
+  if (!main) hipLaunchKernelGGL((k_fused_fast<LPC, false, LIK, false, false, EMIT_NONE>), grid, block, 0, st, a);
+  else if (!a.samp_x) hipLaunchKernelGGL((k_fused_fast<LPC, true, LIK, false, false, EMIT_NONE>), grid, block, 0, st, a);
+  else if (a.samp_stride <= 1) hipLaunchKernelGGL((k_fused_fast<LPC, true, LIK, false, false, EMIT_EVERY>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_fused_fast<LPC, true, LIK, false, false, EMIT_THIN>), grid, block, 0, st, a);
   return hipGetLastError();
 }
 

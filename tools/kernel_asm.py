@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Compile the translation units of libmcx with -save-temps and summarise one kernel: registers and the instruction
-mix of its biggest loop.  usage: tools/kernel_asm.py <mangled-name-substring> [--dump]"""
+mix of its biggest loop.  usage: tools/kernel_asm.py <mangled-name-substring> [--dump]
+
+The biggest loop is the biggest INNERMOST one (a backward branch whose span holds no other): the hot kernels' step
+loops sit inside an outer loop of passes (k_fused_fast's snapshot split), and the outer one would count the prologue and
+the epilogue steps too.  tests/test_hot_loop_codegen_cpu.py uses the functions below."""
 import collections
 import os
 import re
@@ -9,51 +13,84 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TMP = "/tmp/mcx_asm"
+# the Makefile's HIPFLAGS
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
+         "-fno-gpu-flush-denormals-to-zero", "-I" + ROOT + "/include"]
+VCOPY = re.compile(r"v_mov_b(32|64)(_e32|_e64)?\s+v(\[\d+:\d+\]|\d+),\s*v(\[\d+:\d+\]|\d+)\s*$")
+
+
+def compile_tu(tu, tmp=TMP, hipcc="hipcc", device_only=False):
+    """device assembly (gfx950) of mcpar_amd/csrc/<tu>.hip (device_only: without compiling the host side)"""
+    os.makedirs(tmp, exist_ok=True)
+    src = ROOT + "/mcpar_amd/csrc/%s.hip" % tu
+    if device_only:
+        out = os.path.join(tmp, tu + ".s")
+        subprocess.check_call([hipcc] + FLAGS + ["--cuda-device-only", "-S", "-o", out, src], cwd=tmp, stderr=subprocess.DEVNULL)
+        return open(out).read()
+    subprocess.check_call([hipcc] + FLAGS + ["-c", "-save-temps", "-o", "x.o", src], cwd=tmp, stderr=subprocess.DEVNULL)
+    return open(tmp + "/%s-hip-amdgcn-amd-amdhsa-gfx950.s" % tu).read()
+
+
+def kernel_body(s, name):
+    i = s.index("\n" + name + ":")
+    j = s.index(".Lfunc_end", i)
+    return s[i:j].split("\n")
+
+
+def kernel_meta(s, name):
+    meta = s[s.index(".name:           " + name):]
+    return {k: re.search(k + r":\s+(\d+)", meta).group(1) for k in (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size")}
+
+
+def biggest_loop(body):
+    """(first, last) line of the biggest innermost loop, or None"""
+    labels = {}
+    for k, l in enumerate(body):
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m:
+            labels[m.group(1)] = k
+    loops = []
+    for k, l in enumerate(body):
+        m = re.search(r"s_c?branch\w* (\.LBB\d+_\d+)", l)
+        if m and m.group(1) in labels and labels[m.group(1)] < k:
+            loops.append((labels[m.group(1)], k))
+    inner = [a for a in loops if not any(b != a and a[0] <= b[0] and b[1] <= a[1] for b in loops)]
+    return max(inner, key=lambda a: a[1] - a[0]) if inner else None
+
+
+def loop_ops(body, loop):
+    """instruction counts of the loop, and the number of VGPR-to-VGPR copies"""
+    ops = collections.Counter()
+    vcopies = 0
+    for l in body[loop[0]:loop[1] + 1]:
+        l = l.strip()
+        if not l or l.startswith((".", ";")) or l.endswith(":"):
+            continue
+        ops[l.split()[0]] += 1
+        vcopies += 1 if VCOPY.match(l) else 0
+    return ops, vcopies
 
 
 def main():
     pat = sys.argv[1]
-    os.makedirs(TMP, exist_ok=True)
     s = ""
     for tu in ("mcx_k_fast", "mcx_k_fast_full", "mcx_k_fastb", "mcx_k_fastb_full", "mcx_k_pregen", "mcx_k_generic_main", "mcx_k_generic_burn", "mcx_engine"):
         if pat.startswith("k_fused_fast") and tu not in ("mcx_k_fast", "mcx_k_fast_full", "mcx_k_fastb", "mcx_k_fastb_full", "mcx_k_pregen"):
             continue
-        subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off",
-                               "-fno-fast-math", "-fno-gpu-flush-denormals-to-zero", "-I" + ROOT + "/include", "-c",
-                               "-save-temps", "-o", "x.o", ROOT + "/mcpar_amd/csrc/%s.hip" % tu], cwd=TMP,
-                              stderr=subprocess.DEVNULL)
-        s += open(TMP + "/%s-hip-amdgcn-amd-amdhsa-gfx950.s" % tu).read()
+        s += compile_tu(tu)
     names = sorted(set(re.findall(r"^(_Z\w+):", s, flags=re.M)))
     hits = [n for n in names if pat in n]
     for name in hits:
-        i = s.index("\n" + name + ":")
-        j = s.index(".Lfunc_end", i)
-        body = s[i:j].split("\n")
-        meta = s[s.index(".name:           " + name):]
-        regs = {k: re.search(k + r":\s+(\d+)", meta).group(1) for k in (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size")}
-        labels = {}
-        for k, l in enumerate(body):
-            m = re.match(r"^(\.LBB\d+_\d+):", l)
-            if m:
-                labels[m.group(1)] = k
-        best = None
-        for k, l in enumerate(body):
-            m = re.search(r"s_c?branch\w* (\.LBB\d+_\d+)", l)
-            if m and m.group(1) in labels and labels[m.group(1)] < k:
-                a = labels[m.group(1)]
-                if best is None or k - a > best[1] - best[0]:
-                    best = (a, k)
-        print(name, regs)
+        body = kernel_body(s, name)
+        print(name, kernel_meta(s, name))
+        best = biggest_loop(body)
         if best:
-            ops = collections.Counter()
-            for l in body[best[0]:best[1] + 1]:
-                l = l.strip()
-                if not l or l.startswith((".", ";")) or l.endswith(":"):
-                    continue
-                ops[l.split()[0]] += 1
+            ops, vcopies = loop_ops(body, best)
             tot = sum(ops.values())
             valu = sum(v for k, v in ops.items() if k.startswith("v_"))
-            print("  biggest loop: %d instrs, %d VALU, %d branches" % (tot, valu, sum(v for k, v in ops.items() if "branch" in k)))
+            salu = sum(v for k, v in ops.items() if k.startswith("s_") and k != "s_nop")
+            print("  biggest loop: %d instrs, %d VALU, %d VGPR copies, %d exec-mask regions, %d SALU (+ %d s_nop), %d branches"
+                  % (tot, valu, vcopies, ops["s_and_saveexec_b64"], salu, ops["s_nop"], sum(v for k, v in ops.items() if "branch" in k)))
             print("  " + ", ".join("%s %d" % kv for kv in ops.most_common(40)))
             if "--dump" in sys.argv:
                 print("\n".join(body[best[0]:best[1] + 1]))
