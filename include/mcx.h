@@ -340,6 +340,39 @@ int mcx_format_rows(const float *rows, size_t nrows, int ncol, char *text, size_
 /* running maximum-likelihood sample of this shard (MCout::add's maxlval, src/mcout.cc:140-144) */
 int mcx_samples_maxlike(mcx_engine *e, float *lmax, float *params);
 
+/* ---- summaries of the sample store, on the device (DESIGN.md "Sample-store summaries") ----
+ * Per column (the np parameters, then log L) over N = nsteps * nc values.  Split chains: each chain's nsteps values
+ * are cut into two halves of n = floor(nsteps / 2) (odd nsteps: the middle step is dropped), M = 2 nc half-chains.
+ *   mean, sd   over all N values, sd with divisor N - 1
+ *   min, max   exact, in float order (-inf < finite < +inf); a NaN anywhere makes min, max and every quantile NaN
+ *   rhat       split R-hat: W = mean of the half-chain variances (divisor n - 1), B/n = variance of the half-chain means
+ *              (divisor M - 1), var+ = (n - 1)/n W + B/n, rhat = sqrt(var+ / W)
+ *   ess        split "basic" ESS (Geyer's initial positive and monotone sequences on the chain-averaged biased
+ *              autocovariance, no rank normalisation), ess_lag the last lag its sum used; mcse_mean = sd / sqrt(ess)
+ *   quantiles  R type 7 / numpy "linear" from exact order statistics: h = (N - 1) p, x(lo) + (h - lo)(x(lo+1) - x(lo))
+ * A column holding an inf or NaN has MCX_SUMMARY_NONFINITE and NaN mean, sd, rhat, ess and mcse_mean.  A column that is
+ * constant within every half-chain (W = 0) has NaN rhat, ess and mcse_mean. */
+enum { MCX_SUMMARY_NONFINITE = 1 }; /* the column holds an inf or NaN */
+typedef struct mcx_col_summary {
+  double mean, sd;  /* over all N = nsteps*nc values of the column; sd with divisor N - 1 */
+  float min, max;   /* exact */
+  double rhat;      /* split R-hat */
+  double ess;       /* split "basic" ESS, no rank normalisation */
+  double mcse_mean; /* sd / sqrt(ess) */
+  int ess_lag;      /* max_t of the ESS sum: the last lag it used */
+  int flags;        /* MCX_SUMMARY_* */
+} mcx_col_summary;
+/* Steps [first_step, first_step + nsteps) of the store (kept steps, as mcx_samples_copy counts them), nsteps >= 4.
+ * cols[np + 1]; quantiles[(np + 1) * nprobs], row = column (may be NULL when nprobs == 0); probs in [0, 1], nprobs <= 32.
+ * MCX_ERR_INVALID when the store does not hold the range (no run yet, MCX_OPT_SAMPLES = 0, a run into a sink).  Works on
+ * the engine's stream after a queued MCX_OPT_ASYNC_RUN run is finished; the same store and arguments give the same bytes. */
+int mcx_samples_summary(mcx_engine *e, int first_step, int nsteps, const double *probs, int nprobs,
+                        mcx_col_summary *cols, double *quantiles);
+/* the same for rows on the host in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows), e.g. what
+ * MCout collected from a sink: uploaded to a scratch store, summarised there */
+int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs,
+                     mcx_col_summary *cols, double *quantiles);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote
@@ -420,6 +453,16 @@ int mcx_debug_numerics(int what, int n, const uint32_t *in, uint32_t *out_bits);
 /* number of float bit patterns in [lo_bits, hi_bits) where the kernels' lean sqrt (valid for +-0 and
  * positive normal floats) differs from IEEE sqrtf, and the smallest such pattern */
 int mcx_debug_sqrt_sweep(uint32_t lo_bits, uint32_t hi_bits, uint64_t *nbad, uint32_t *first_bad);
+/* the host step of mcx_samples_summary for one column (no device): n, M half-chains of n steps, N values; mean, var_all
+ * (divisor N - 1) and var_means (B/n, divisor M - 1); acov[nlags] = the mean over half-chains of the biased autocovariance
+ * (1/n) sum_{i<n-t} (x_i - m_c)(x_{i+t} - m_c); ostat = [min, max, then x(lo), x(lo+1) of every probability] as floats;
+ * flags as given (MCX_SUMMARY_NONFINITE: only min, max and quantiles are computed).  *need_lags = 0 when col is complete,
+ * else the number of lags the ESS sum needs (more than nlags; col's R-hat / ESS fields are then not final). */
+int mcx_debug_summary_finish(int n, int M, double mean, double var_all, double var_means, const double *acov, int nlags,
+                             const float *ostat, long long N, const double *probs, int nprobs, int flags,
+                             mcx_col_summary *col, double *quantiles, int *need_lags);
+/* mcx_samples_summary without quantiles, reporting the number of 32-lag autocovariance windows it computed */
+int mcx_debug_summary_windows(mcx_engine *e, int first_step, int nsteps, int *nwin);
 /* normals of stream `stream`, counter (t, g0+i, a, q) for i < n: out[n*4] */
 int mcx_debug_normals(uint32_t seed, uint32_t stream, uint32_t t, uint32_t g0, uint32_t a,
                       uint32_t q, int n, float *out);

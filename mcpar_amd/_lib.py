@@ -63,6 +63,7 @@ def load():
                            "there is no CPU fallback" % p)
     L = C.CDLL(p)
     fp, u32p, vp = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_void_p
+    dp = C.POINTER(C.c_double)
     sig = {
         "mcx_vlfunc_eval": [C.POINTER(VLFunc), C.c_int, fp, fp],
         "mcx_create": [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -91,6 +92,11 @@ def load():
         "mcx_samples_text": [vp, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)],
         "mcx_format_rows": [fp, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)],
         "mcx_samples_maxlike": [vp, fp, fp],
+        "mcx_samples_summary": [vp, C.c_int, C.c_int, dp, C.c_int, vp, dp],
+        "mcx_rows_summary": [fp, C.c_int, C.c_int, C.c_int, dp, C.c_int, vp, dp],
+        "mcx_debug_summary_finish": [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.c_int, fp,
+                                     C.c_longlong, dp, C.c_int, C.c_int, vp, dp, C.POINTER(C.c_int)],
+        "mcx_debug_summary_windows": [vp, C.c_int, C.c_int, C.POINTER(C.c_int)],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

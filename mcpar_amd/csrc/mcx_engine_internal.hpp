@@ -244,6 +244,10 @@ struct mcx_engine {
   DevBuf<float> samp_x, samp_ly, winv_tab, psum, pmax, racpt, pinit_dev, zpre, upre, trash;
   bool pinit_staged = false;
   DevBuf<uint8_t> mask;
+  // mcx_samples_summary's scratch (mcx_summary.hip): fp64 sums and slabs, histograms, prefixes / masks
+  DevBuf<double> summ_d;
+  DevBuf<unsigned long long> summ_h;
+  DevBuf<uint32_t> summ_u;
   // host staging
   PinBuf<float> h_ptrial, h_lytrial;
   PinBuf<unsigned long long> h_ctr;  // the run's counters, read back once at its end

@@ -2,12 +2,14 @@
 // only through its library API: SURVEY fact 3).
 //   mcpar-run [--func rosen1|rosen2|rosen2fixed|gauss|dgauss|mix | --func-source FILE.hip [--par a,b,...]] [--np D]
 //             [--nc CHAINS] [--nsamp N] [--nburn B] [--pl P] [--sync S] [--ncomp K] [--quiet] [--iter] [--binary]
-//             [--stream-text] [--out FILE]
+//             [--stream-text] [--out FILE] [--summary FILE]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
 // that src/anly/mcpar-analysis.R:80-120 reconstructs; --quiet prints only the summary (stderr); --out FILE: the sample
 // text goes to FILE, every rank writing its own share at its place (MCout::text_file) instead of through rank 0.
+// --summary FILE: one row per column (p0 .. p{np-1}, then LL) of the kept rows' summary on the GPU (mcx_rows_summary):
+// name mean sd q01 q50 q99 rhat ess mcse.  Needs the rows on the host: not with --stream-text, and one rank only.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -24,13 +26,43 @@
 
 #include "../csrc/fmt_g6.hpp"
 
+// --summary: the per-column statistics of MCout's rows, one row per column
+static int write_summary(const char *path, MCout &rows, int nsamp, int nc, int np)
+{
+  const double probs[3] = {0.01, 0.5, 0.99};
+  std::vector<mcx_col_summary> cols((size_t)np + 1);
+  std::vector<double> q(((size_t)np + 1) * 3);
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 4) {
+    std::cerr << "--summary: " << rows.size() << " rows stored, a summary needs nsamp * nc of them and nsamp >= 4\n";
+    return 1;
+  }
+  if (mcx_rows_summary(rows.getpset(0), nsamp, nc, np, probs, 3, cols.data(), q.data()) != MCX_OK) {
+    std::cerr << "--summary: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "name mean sd q01 q50 q99 rhat ess mcse\n");
+  for (int c = 0; c <= np; ++c) {
+    const mcx_col_summary &s = cols[c];
+    const double *qc = q.data() + (size_t)c * 3;
+    std::string name = c < np ? "p" + std::to_string(c) : "LL";
+    fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", name.c_str(), s.mean, s.sd, qc[0], qc[1], qc[2],
+            s.rhat, s.ess, s.mcse_mean);
+  }
+  return fclose(f) == 0 ? 0 : 1;
+}
+
 int main(int argc, char *argv[])
 {
   std::string func = "rosen1";
   int np = 16, nc = 4096, nsamp = 100, nburn = 500, sync = 10, ncomp = 8;
   float pl = 1.0f;
   bool quiet = false, iter = false, binary = false, stream_text = false;
-  std::string out_file, func_source;
+  std::string out_file, func_source, summary_file;
   std::vector<float> user_par;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -53,12 +85,20 @@ int main(int argc, char *argv[])
     else if (a == "--binary") binary = true;  // rows as raw float32 (np+1 per row) instead of text
     else if (a == "--stream-text") stream_text = true;  // the same text, formatted on the GPU, nothing kept on the host
     else if (a == "--out") out_file = val();
+    else if (a == "--summary") summary_file = val();
     else { std::cerr << "unknown option " << a << "\n"; return 2; }
   }
   MPI_Init(&argc, &argv);
   int size, rank;
   MPI_Comm_size(MPI_COMM_WORLD, &size);
   MPI_Comm_rank(MPI_COMM_WORLD, &rank);
+  if (!summary_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--summary needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
 
   VLFunc *L = 0;
   std::vector<float> means, w;
@@ -133,6 +173,10 @@ int main(int argc, char *argv[])
     return 2;
   }
   rslts.text_file(0);
+  if (!summary_file.empty() && write_summary(summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
   float lmax;
   const std::vector<float> &pmax = rslts.maxlike(&lmax);
   if (rank == 0) {

@@ -25,6 +25,12 @@ OPT_ASYNC_RUN = 19
 OPT_REFERENCE_CALLS = 20
 OPT_SELF_REPORT = 21
 XCHG_BEGIN, XCHG_WAIT = 0, 1
+SUMMARY_NONFINITE = 1  # mcx_col_summary.flags: the column holds an inf or NaN
+# include/mcx.h mcx_col_summary
+SUMMARY_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("min", np.float32), ("max", np.float32),
+                          ("rhat", np.float64), ("ess", np.float64), ("mcse_mean", np.float64), ("ess_lag", np.int32),
+                          ("flags", np.int32)], align=True)
+assert SUMMARY_DTYPE.itemsize == 56
 
 
 def _fp(a):
@@ -99,6 +105,43 @@ def plan(nsamp, nburn, sync=10, pl=0.9, seed=8675309, tbase=0, nshards=1, eager=
     check(load().mcx_plan(nsamp, nburn, sync, pl, seed, tbase, nshards, eager, fused, max_segment, has_output_hook,
                           sink_block, items, n.value, C.byref(n)))
     return [(PLAN_NAMES[it.kind], it.first, it.nsteps, it.aux) for it in items[:n.value]]
+
+
+def _probs(probs):
+    p = np.ascontiguousarray(np.asarray(probs, np.float64).reshape(-1))
+    return p, p.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _summary_dict(cols, q):
+    out = {name: cols[name].copy() for name in SUMMARY_DTYPE.names}
+    out["quantiles"] = q
+    return out
+
+
+def rows_summary(rows, nsteps, nc, probs=(0.01, 0.5, 0.99)):
+    """mcx_rows_summary: Engine.summary's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    p, pp = _probs(probs)
+    cols = np.zeros(ncol, SUMMARY_DTYPE)
+    q = np.zeros((ncol, len(p)), np.float64)
+    check(load().mcx_rows_summary(_fp(rows), nsteps, nc, ncol - 1, pp, len(p), cols.ctypes.data_as(C.c_void_p),
+                                  q.ctypes.data_as(C.POINTER(C.c_double))))
+    return _summary_dict(cols, q)
+
+
+def debug_summary_finish(n, M, mean, var_all, var_means, acov, ostat, N, probs=(), flags=0):
+    """mcx_debug_summary_finish for one column: (record of SUMMARY_DTYPE, quantiles, lags still needed)"""
+    a = np.ascontiguousarray(acov, np.float64)
+    o = np.ascontiguousarray(ostat, np.float32)
+    p, pp = _probs(probs)
+    col = np.zeros(1, SUMMARY_DTYPE)
+    q = np.zeros(max(len(p), 1), np.float64)
+    need = C.c_int(0)
+    check(load().mcx_debug_summary_finish(n, M, mean, var_all, var_means, a.ctypes.data_as(C.POINTER(C.c_double)), len(a),
+                                          _fp(o), N, pp, len(p), flags, col.ctypes.data_as(C.c_void_p),
+                                          q.ctypes.data_as(C.POINTER(C.c_double)), C.byref(need)))
+    return col[0], q[:len(p)], need.value
 
 
 def device_count():
@@ -415,6 +458,30 @@ class Engine:
         else:
             check(load().mcx_samples_text(self.h, first_step, nsteps, buf.ctypes.data_as(C.c_char_p), buf.size, C.byref(nb)))
         return nb.value
+
+    def summary(self, probs=(0.01, 0.5, 0.99), first_step=0, nsteps=None):
+        """mcx_samples_summary: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps)
+        -- a dict of arrays [np + 1]: mean, sd, min, max, rhat, ess, mcse_mean, ess_lag, flags; quantiles [np + 1, nprobs]"""
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        p, pp = _probs(probs)
+        cols = np.zeros(self.np + 1, SUMMARY_DTYPE)
+        q = np.zeros((self.np + 1, len(p)), np.float64)
+        check(load().mcx_samples_summary(self.h, first_step, nsteps, pp, len(p), cols.ctypes.data_as(C.c_void_p),
+                                         q.ctypes.data_as(C.POINTER(C.c_double))))
+        return _summary_dict(cols, q)
+
+    def summary_windows(self, first_step=0, nsteps=None):
+        """how many 32-lag autocovariance windows the summary of that range computes (mcx_debug_summary_windows)"""
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        nw = C.c_int(0)
+        check(load().mcx_debug_summary_windows(self.h, first_step, nsteps, C.byref(nw)))
+        return nw.value
 
     def maxlike(self):
         lm = C.c_float(0)

@@ -1,0 +1,161 @@
+"""mcx_debug_summary_finish -- the host step of mcx_samples_summary (R-hat, Geyer's ESS, quantile interpolation) --
+against the float64 restatement of DESIGN.md "Sample-store summaries" (tests/summary_ref.py).  No GPU."""
+import math
+
+import numpy as np
+import pytest
+
+import summary_ref as R
+from mcpar_amd import McxError
+from mcpar_amd import engine as E
+
+
+def finish(n, M, acov, var_means, probs=(), ostat=None, N=None, flags=0, mean=0.25, var_all=1.5):
+    N = N if N is not None else 2 * n * M // 2
+    ostat = ostat if ostat is not None else np.zeros(2 + 2 * len(probs), np.float32)
+    return E.debug_summary_finish(n, M, mean, var_all, var_means, acov, ostat, N, probs, flags)
+
+
+def expect(n, M, acov, var_means):
+    W = acov[0] * n / (n - 1)
+    var_plus = acov[0] + var_means
+    ess, max_t, pairs = R.geyer(n, M, np.asarray(acov), W, var_plus)
+    return math.sqrt(var_plus / W), ess, max_t, pairs
+
+
+def check_col(col, n, M, acov, var_means, var_all=1.5):
+    rhat, ess, max_t, _ = expect(n, M, acov, var_means)
+    assert abs(col["rhat"] - rhat) < 1e-14
+    assert col["ess_lag"] == max_t
+    assert col["ess"] == pytest.approx(ess, rel=1e-13)
+    assert col["mcse_mean"] == pytest.approx(math.sqrt(var_all) / math.sqrt(ess), rel=1e-13)
+    assert col["sd"] == pytest.approx(math.sqrt(var_all), rel=1e-15)
+    assert col["flags"] == 0
+
+
+def ar_acov(n, M, phi, seed):
+    """per-half-chain means / variances and the chain-averaged autocovariance of M synthetic AR(1) half-chains"""
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, M))
+    x[0] = rng.standard_normal(M)
+    for i in range(1, n):
+        x[i] = phi * x[i - 1] + rng.standard_normal(M)
+    x += rng.normal(0, 0.05, M)  # chain offsets
+    m = x.mean(axis=0)
+    acov = R.half_chain_acov(x) / (n * M)
+    s2 = x.var(axis=0, ddof=1)
+    assert acov[0] * n / (n - 1) == pytest.approx(s2.mean(), rel=1e-12)  # W from lag 0
+    return acov, m.var(ddof=1)
+
+
+@pytest.mark.parametrize("n,M,phi,seed", [(100, 8, 0.6, 1), (257, 4, 0.9, 2), (64, 2, 0.3, 3), (500, 16, -0.4, 4)])
+def test_synthetic_half_chains(n, M, phi, seed):
+    acov, vm = ar_acov(n, M, phi, seed)
+    col, _, need = finish(n, M, acov, vm)
+    assert need == 0
+    check_col(col, n, M, acov, vm)
+
+
+def test_asks_for_more_lags():
+    n, M = 400, 8
+    acov, vm = ar_acov(n, M, 0.97, 5)
+    _, _, max_t, _ = expect(n, M, acov, vm)
+    assert max_t > 40
+    col, _, need = finish(n, M, acov[:32], vm)
+    assert 32 < need <= max_t + 4
+    got = need
+    while need:  # the device's windows arrive 32 lags at a time
+        got = min(n, got + 32)
+        col, _, need = finish(n, M, acov[:got], vm)
+    check_col(col, n, M, acov, vm)
+
+
+def test_monotone_step_fires():
+    n, M = 60, 4
+    rho = np.zeros(n)
+    rho[:10] = [1.0, 0.5, 0.2, 0.1, 0.35, 0.3, 0.05, 0.02, -0.3, -0.2]
+    rho[10:] = -0.01
+    acov0, vm = 2.0, 0.1
+    var_plus = acov0 + vm
+    W = acov0 * n / (n - 1)
+    acov = W - (1 - rho) * var_plus  # rho(t) = 1 - (W - acov(t)) / var+
+    acov[0] = acov0
+    rr = 1 - (W - acov) / var_plus
+    rr[0] = 1
+    assert rr[4] + rr[5] > rr[2] + rr[3]  # the pair the monotone step replaces
+    col, _, need = finish(n, M, acov, vm)
+    assert need == 0
+    check_col(col, n, M, acov, vm)
+    rhat, ess, max_t, _ = expect(n, M, acov, vm)
+    # without the monotone step tau would hold the larger pair
+    tau_raw = -1 + 2 * rr[:max_t].sum() + (rr[max_t] if rr[max_t] > 0 else 0)
+    assert col["ess"] > M * n / tau_raw
+
+
+def test_pair_sums_never_end():
+    n, M = 30, 4
+    acov, vm = ar_acov(n, M, 0.995, 6)
+    col, _, need = finish(n, M, acov, vm)
+    assert need == 0
+    _, _, max_t, pairs = expect(n, M, acov, vm)
+    assert max_t >= n - 5 and pairs[-1] > 0
+    check_col(col, n, M, acov, vm)
+
+
+def test_log10_floor():
+    n, M = 50, 4
+    acov0, vm = 1.0, 0.0
+    var_plus = acov0 + vm
+    W = acov0 * n / (n - 1)
+    rho = np.full(n, -0.3)
+    rho[1] = -0.95  # strongly antithetic: the sum goes below the floor
+    acov = W - (1 - rho) * var_plus
+    acov[0] = acov0
+    col, _, need = finish(n, M, acov, vm)
+    assert need == 0
+    assert col["ess"] == pytest.approx(M * n * math.log10(M * n), rel=1e-14)
+    check_col(col, n, M, acov, vm)
+
+
+def test_quantile_interpolation():
+    N = 101
+    rng = np.random.default_rng(7)
+    srt = np.sort(rng.standard_normal(N).astype(np.float32))
+    probs = (0.0, 1.0, 0.25, 0.013, 0.5, 0.99)
+    want, lo_hi = R.quantiles_from_sorted(srt, probs)
+    ostat = np.array([srt[0], srt[-1]] + [v for ab in lo_hi for v in ab], np.float32)
+    acov, vm = ar_acov(50, 2, 0.5, 8)
+    col, q, need = finish(50, 2, acov, vm, probs, ostat, N)
+    assert q[0] == srt[0] and q[1] == srt[-1]  # p = 0 and 1: the extremes, exactly
+    assert q[2] == srt[25]                     # h = 25 integral: the order statistic itself
+    np.testing.assert_allclose(q, want, rtol=1e-15)
+    assert col["min"] == srt[0] and col["max"] == srt[-1]
+    np.testing.assert_allclose(q, np.quantile(srt.astype(np.float64), probs), rtol=1e-12)
+
+
+def test_nonfinite_and_nan():
+    N = 8
+    ostat = np.array([-np.inf, 3.0, -np.inf, 2.0], np.float32)  # min, max, x(lo), x(lo+1) for p = 0.1
+    col, q, need = finish(2, 2, [1.0, 0.5], 0.1, (0.1,), ostat, N, flags=E.SUMMARY_NONFINITE)
+    assert need == 0 and col["flags"] == E.SUMMARY_NONFINITE
+    for f in ("mean", "sd", "rhat", "ess", "mcse_mean"):
+        assert math.isnan(col[f])
+    assert col["min"] == -np.inf and col["max"] == 3.0
+    assert math.isnan(q[0])  # -inf + 0.7 (2 - -inf): the formula's inf - inf
+    ostat = np.array([-np.inf, np.inf, np.inf, np.inf], np.float32)
+    col, q, _ = finish(2, 2, [1.0, 0.5], 0.1, (0.5,), ostat, N, flags=E.SUMMARY_NONFINITE)
+    assert q[0] == np.inf  # inside a run of equal values: that value
+    ostat = np.array([-1.0, np.nan, 0.0, 1.0], np.float32)
+    col, q, _ = finish(2, 2, [1.0, 0.5], 0.1, (0.5,), ostat, N, flags=E.SUMMARY_NONFINITE)
+    assert math.isnan(col["min"]) and math.isnan(col["max"]) and math.isnan(q[0])
+
+
+def test_constant_column():
+    col, _, need = finish(10, 4, np.zeros(10), 0.0, var_all=0.0)
+    assert need == 0
+    assert math.isnan(col["rhat"]) and math.isnan(col["ess"]) and col["sd"] == 0.0
+
+
+def test_bad_arguments():
+    with pytest.raises(McxError):
+        E.debug_summary_finish(1, 2, 0.0, 1.0, 0.0, [1.0], np.zeros(2, np.float32), 4)
