@@ -344,7 +344,8 @@ int mcx_samples_maxlike(mcx_engine *e, float *lmax, float *params);
  * Per column (the np parameters, then log L) over N = nsteps * nc values.  Split chains: each chain's nsteps values
  * are cut into two halves of n = floor(nsteps / 2) (odd nsteps: the middle step is dropped), M = 2 nc half-chains.
  *   mean, sd   over all N values, sd with divisor N - 1
- *   min, max   exact, in float order (-inf < finite < +inf); a NaN anywhere makes min, max and every quantile NaN
+ *   min, max   exact, in float order (-inf < finite < +inf; -0 before +0); a NaN anywhere makes min, max and every
+ *              quantile NaN (a NaN, payload unspecified)
  *   rhat       split R-hat: W = mean of the half-chain variances (divisor n - 1), B/n = variance of the half-chain means
  *              (divisor M - 1), var+ = (n - 1)/n W + B/n, rhat = sqrt(var+ / W)
  *   ess        split "basic" ESS (Geyer's initial positive and monotone sequences on the chain-averaged biased
@@ -463,6 +464,12 @@ int mcx_debug_summary_finish(int n, int M, double mean, double var_all, double v
                              mcx_col_summary *col, double *quantiles, int *need_lags);
 /* mcx_samples_summary without quantiles, reporting the number of 32-lag autocovariance windows it computed */
 int mcx_debug_summary_windows(mcx_engine *e, int first_step, int nsteps, int *nwin);
+/* the autocovariance sums of mcx_rows_summary's device passes, for tests: the same kernels and launches, but every finite
+ * column takes lag windows until it holds nlags lags (1 <= nlags <= n) instead of stopping where its Geyer loop does.
+ * acov[(np + 1) * nlags], row = column: sum over the M half-chains of sum_{i<n-t} c_i c_{i+t}, c = the half-chain centred
+ * on its mean (n M times the acov of mcx_debug_summary_finish); sumsq[np + 1]: sum over all N values of (x - mean)^2.
+ * A column that is not finite gets NaN in both. */
+int mcx_debug_rows_acov(const float *rows, int nsteps, int nc, int np, int nlags, double *acov, double *sumsq);
 /* normals of stream `stream`, counter (t, g0+i, a, q) for i < n: out[n*4] */
 int mcx_debug_normals(uint32_t seed, uint32_t stream, uint32_t t, uint32_t g0, uint32_t a,
                       uint32_t q, int n, float *out);

@@ -97,6 +97,7 @@ def load():
         "mcx_debug_summary_finish": [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.c_int, fp,
                                      C.c_longlong, dp, C.c_int, C.c_int, vp, dp, C.POINTER(C.c_int)],
         "mcx_debug_summary_windows": [vp, C.c_int, C.c_int, C.POINTER(C.c_int)],
+        "mcx_debug_rows_acov": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

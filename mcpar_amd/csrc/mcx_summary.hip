@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(SB) k_sum_hist(TileSet t, int nc, int64_t T, i
 // pass 3: lag windows k0 .. k0 + KW - 1.  grid = KW * ntiles * nbc, the window fastest (its workgroups read the same rows).
 // part[((y * ncol + col) * NQ + q) * pstride + bc]
 __global__ void __launch_bounds__(SB) k_sum_acov(TileSet t, int nc, int64_t T, int64_t n, int k0, int KW, int ncol,
-                                                 const double *hm, const double *coltot, double invN, const int *active,
+                                                 const double *hm, const double *coltot, double Nd, const int *active,
                                                  double *part, size_t pstride)
 {
   __shared__ double red[SB];
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(SB) k_sum_acov(TileSet t, int nc, int64_t T, i
   for (int q = 0; q < WLAG; ++q) acc[q] = 0.0;
   if (on) {
     const float *p = t.src + (size_t)l.chain * t.cs + l.lcol;
-    const double mu = coltot[col] * invN;
+    const double mu = coltot[col] / Nd;  // the reported mean: a constant column gives a zero sum
     for (int h = 0; h < 2; ++h) {
       const float *ph = p + (size_t)(h ? T - n : 0) * t.rs;
       const double m = hm[((size_t)col * 2 + h) * nc + l.chain];
@@ -256,9 +256,13 @@ struct Bufs {
 
 }  // namespace
 
-// the summary of x[T][nc][np], ly[T][nc] (device) on stream st
+// the summary of x[T][nc][np], ly[T][nc] (device) on stream st.  force_lags > 0 (mcx_debug_rows_acov): every finite
+// column takes windows until it holds force_lags lags instead of stopping where its Geyer loop does; the raw lag sums go to
+// acov_out[ncol][force_lags] and the centred sums of squares to sumsq_out[ncol] (NaN for a column that is not finite),
+// and cols / quantiles are not computed.
 static int summary_device(hipStream_t st, Bufs B, const float *x, const float *ly, int nc, int np, int64_t T,
-                          const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles, int *nwin_out)
+                          const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles, int *nwin_out,
+                          int force_lags = 0, double *acov_out = nullptr, double *sumsq_out = nullptr)
 {
   const int ncol = np + 1;
   const int64_t n = T / 2, M = 2 * (int64_t)nc, N = T * (int64_t)nc;
@@ -377,7 +381,7 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
     HIPCHK(hipMemcpyAsync(B.u->p, active.data(), (size_t)ncol * 4, hipMemcpyHostToDevice, st));
     for (const TileSet *t : {&tx, &tl}) {
       hipLaunchKernelGGL(k_sum_acov, dim3((unsigned)(KW * t->ntiles * t->nbc)), dim3(SB), 0, st, *t, nc, T, n, k0, KW, ncol,
-                         D + o_hm, D + o_cs, 1.0 / (double)N, (const int *)B.u->p, D + o_part, pstride);
+                         D + o_hm, D + o_cs, (double)N, (const int *)B.u->p, D + o_part, pstride);
       HIPCHK(hipGetLastError());
     }
     MCXCHK(rows(D + o_part, pstride, NQ, (size_t)KW * ncol * NQ, tx.nbc, tl.nbc, nullptr, 0.0, D + o_win));
@@ -398,6 +402,10 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
     // which columns want more lags than they have
     for (int c = 0; c < ncol; ++c) {
       if (!active[c]) continue;
+      if (force_lags > 0) {
+        active[c] = (int64_t)acov[c].size() < force_lags ? 1 : 0;
+        continue;
+      }
       std::vector<double> a(acov[c].size());
       for (size_t t = 0; t < a.size(); ++t) a[t] = acov[c][t] / ((double)n * (double)M);
       mcx_col_summary tmp;
@@ -409,6 +417,17 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
     }
   }
   if (nwin_out) *nwin_out = nwin;
+  if (force_lags > 0) {
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    for (int c = 0; c < ncol; ++c) {
+      const bool fin = std::isfinite(cs[c]);
+      if (fin && (int64_t)acov[c].size() < force_lags)
+        return fail(MCX_ERR_INVALID, "internal: column %d holds %d of %d lags", c, (int)acov[c].size(), force_lags);
+      for (int t = 0; t < force_lags; ++t) acov_out[(size_t)c * force_lags + t] = fin ? acov[c][t] : qnan;
+      sumsq_out[c] = fin ? ss[c] : qnan;
+    }
+    return MCX_OK;
+  }
 
   // ---- 4. the host finish
   for (int c = 0; c < ncol; ++c) {
@@ -454,10 +473,10 @@ extern "C" int mcx_samples_summary(mcx_engine *e, int first_step, int nsteps, co
                         nullptr);
 }
 
-extern "C" int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs,
-                                mcx_col_summary *cols, double *quantiles)
+// rows [nsteps * nc][np + 1] on the host (MCout layout) uploaded to a scratch store x, ly on a stream of its own:
+// f(st, bufs, x, ly) runs summary_device there
+template <class F> static int on_rows(const float *rows, int nsteps, int nc, int np, F f)
 {
-  MCXCHK(summary_args(nsteps, probs, nprobs, cols, quantiles));
   if (!rows || nc < 1 || np < 1 || np > 256) return fail(MCX_ERR_INVALID, "bad arguments");
   MCXCHK(need_device());
   const size_t nr = (size_t)nsteps * nc;
@@ -474,7 +493,7 @@ extern "C" int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, c
     HIPCHK(hipMemcpyAsync(rd.p, rows, nr * (np + 1) * sizeof(float), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_sum_deinterleave, dim3(nblocks(nr * (np + 1))), dim3(BLOCK), 0, st, rd.p, nr, np, x.p, ly.p);
     HIPCHK(hipGetLastError());
-    return summary_device(st, Bufs{&d, &h, &u}, x.p, ly.p, nc, np, nsteps, probs, nprobs, cols, quantiles, nullptr);
+    return f(st, Bufs{&d, &h, &u}, x.p, ly.p);
   };
   const int rc = run();
   if (st) {
@@ -483,6 +502,25 @@ extern "C" int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, c
   }
   rd.release(); x.release(); ly.release(); d.release(); h.release(); u.release();
   return rc;
+}
+
+extern "C" int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs,
+                                mcx_col_summary *cols, double *quantiles)
+{
+  MCXCHK(summary_args(nsteps, probs, nprobs, cols, quantiles));
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
+    return summary_device(st, B, x, ly, nc, np, nsteps, probs, nprobs, cols, quantiles, nullptr);
+  });
+}
+
+extern "C" int mcx_debug_rows_acov(const float *rows, int nsteps, int nc, int np, int nlags, double *acov, double *sumsq)
+{
+  if (nsteps < 4) return fail(MCX_ERR_INVALID, "a summary needs nsteps >= 4 (two half-chains of >= 2 steps), got %d", nsteps);
+  if (nlags < 1 || nlags > nsteps / 2 || !acov || !sumsq)
+    return fail(MCX_ERR_INVALID, "nlags = %d: 1 to n = %d lags, acov and sumsq not NULL", nlags, nsteps / 2);
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
+    return summary_device(st, B, x, ly, nc, np, nsteps, nullptr, 0, nullptr, nullptr, nullptr, nlags, acov, sumsq);
+  });
 }
 
 extern "C" int mcx_debug_summary_windows(mcx_engine *e, int first_step, int nsteps, int *nwin)

@@ -130,6 +130,18 @@ def rows_summary(rows, nsteps, nc, probs=(0.01, 0.5, 0.99)):
     return _summary_dict(cols, q)
 
 
+def debug_rows_acov(rows, nsteps, nc, nlags):
+    """mcx_debug_rows_acov: (acov [np + 1, nlags], sumsq [np + 1]), the device's raw autocovariance sums over the
+    half-chains of rows [nsteps * nc, np + 1] and its centred sums of squares"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    acov = np.zeros((ncol, nlags), np.float64)
+    sumsq = np.zeros(ncol, np.float64)
+    check(load().mcx_debug_rows_acov(_fp(rows), nsteps, nc, ncol - 1, nlags, acov.ctypes.data_as(C.POINTER(C.c_double)),
+                                     sumsq.ctypes.data_as(C.POINTER(C.c_double))))
+    return acov, sumsq
+
+
 def debug_summary_finish(n, M, mean, var_all, var_means, acov, ostat, N, probs=(), flags=0):
     """mcx_debug_summary_finish for one column: (record of SUMMARY_DTYPE, quantiles, lags still needed)"""
     a = np.ascontiguousarray(acov, np.float64)

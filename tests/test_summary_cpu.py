@@ -159,3 +159,113 @@ def test_constant_column():
 def test_bad_arguments():
     with pytest.raises(McxError):
         E.debug_summary_finish(1, 2, 0.0, 1.0, 0.0, [1.0], np.zeros(2, np.float32), 4)
+
+
+# ---- the reference itself on the edges of the contract: key order, quantiles, the lag sums, W = 0
+
+def edge_values(seed):
+    """float32 values with every kind of edge: signed zeros and NaNs, infinities, subnormals, ties, extremes"""
+    rng = np.random.default_rng(seed)
+    bits = [0x00000000, 0x80000000, 0x7fc00000, 0xffc00000, 0x7f800001, 0x7f800000, 0xff800000, 0x00000001, 0x80000001,
+            0x007fffff, 0x807fffff, 0x00800000, 0x7f7fffff, 0xff7fffff]
+    special = np.array(bits, np.uint32).view(np.float32)
+    x = np.concatenate([special, special, rng.standard_normal(200).astype(np.float32), np.full(20, 1.5, np.float32)])
+    return x[rng.permutation(x.size)]
+
+
+def py_key(v):
+    """the kernel's key of one float32, bit by bit in plain Python"""
+    u = int(np.float32(v).view(np.uint32))
+    if math.isnan(v):
+        return 0xffffffff
+    return (~u & 0xffffffff) if u >> 31 else (u | 0x80000000)
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_reference_order_is_the_key_order(seed):
+    x = edge_values(seed)
+    want = sorted((py_key(v) for v in x))
+    assert R.okey(x).tolist() == [py_key(v) for v in x]
+    srt = R.key_sort(x)
+    finite = ~np.isnan(srt)
+    assert [py_key(v) for v in srt[finite]] == want[:int(finite.sum())]
+    assert np.isnan(srt[~finite]).all() and not finite[-int((~finite).sum()):].any()
+    # -0 strictly before +0: the first zero is -0 whichever comes first in x
+    z = np.flatnonzero(srt == 0)
+    assert srt[z[0]].view(np.uint32) == 0x80000000 and srt[z[-1]].view(np.uint32) == 0
+
+
+@pytest.mark.parametrize("first", [0.0, -0.0])
+def test_reference_min_max_signed_zero(first):
+    x = np.array([[first, -first], [1.0, 2.0], [-first, first], [3.0, 4.0]], np.float32)
+    r = R.restate_column(x, (0.0, 1.0))
+    assert np.float32(r["min"]).view(np.uint32) == 0x80000000
+    y = -x
+    r = R.restate_column(y, (0.0, 1.0))
+    assert np.float32(r["max"]).view(np.uint32) == 0x00000000
+
+
+@pytest.mark.parametrize("nan_bits", [0x7fc00000, 0xffc00000, 0x7f800001])
+def test_reference_nan_column(nan_bits):
+    x = np.arange(12, dtype=np.float32).reshape(6, 2)
+    x[3, 1] = np.array([nan_bits], np.uint32).view(np.float32)[0]
+    r = R.restate_column(x, (0.0, 0.5, 1.0))
+    assert r["flags"] == 1 and math.isnan(r["min"]) and math.isnan(r["max"]) and np.isnan(r["quantiles"]).all()
+    got = dict(flags=[1], min=[np.float32(np.nan)], max=[np.array([0xffffffff], np.uint32).view(np.float32)[0]],
+               quantiles=[np.full(3, np.nan)], mean=[np.nan], sd=[np.nan], rhat=[np.nan], ess=[np.nan], mcse_mean=[np.nan])
+    R.check(got, {0: r})  # any NaN payload is "a NaN"
+    got["max"] = [np.float32(11.0)]
+    with pytest.raises(AssertionError):
+        R.check(got, {0: r})
+
+
+@pytest.mark.parametrize("N,seed", [(101, 1), (8385, 2), (1000, 3)])
+def test_reference_quantiles_match_numpy(N, seed):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(N).astype(np.float32)
+    x[:N // 10] = x[N // 10]  # a run of ties
+    probs = np.concatenate([[0.0, 1.0, 0.29, 0.5, 1 / 64, 63 / 64], rng.random(20)])
+    q, _ = R.quantiles_from_sorted(R.key_sort(x), probs)
+    np.testing.assert_allclose(q, np.quantile(x.astype(np.float64), probs, method="linear"), rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("n,M,phi,seed", [(2, 2, 0.0, 1), (33, 4, 0.5, 2), (97, 6, 0.9, 3), (300, 2, -0.3, 4)])
+def test_direct_acov_equals_fft(n, M, phi, seed):
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, M))
+    x[0] = rng.standard_normal(M)
+    for i in range(1, n):
+        x[i] = phi * x[i - 1] + rng.standard_normal(M)
+    x += rng.normal(0, 3, M)
+    d, f = R.direct_acov(x, n), R.half_chain_acov(x)
+    assert abs(d - f).max() <= 1e-12 * d[0]
+    c = x - x.mean(axis=0)
+    assert d[n - 1] == pytest.approx((c[0] * c[n - 1]).sum(), rel=1e-15)  # the last lag: one product per half-chain
+
+
+def test_reference_w_zero():
+    """W = 0 (constant within every half-chain): NaN rhat, ess, mcse; ess_lag 0; sd the plain value"""
+    T, nc = 9, 3
+    with np.errstate(all="raise"):  # no division by zero on the way
+        r = R.restate_column(np.full((T, nc), 0.1, np.float32), (0.5,))
+        assert r["sd"] == 0.0 and r["mean"] == pytest.approx(np.float32(0.1), rel=1e-15) and r["flags"] == 0
+        assert math.isnan(r["rhat"]) and math.isnan(r["ess"]) and math.isnan(r["mcse_mean"]) and r["ess_lag"] == 0
+        x = np.empty((T, nc), np.float32)
+        x[:4], x[4], x[5:] = [1.0, 2.0, 3.0], 7.0, [-1.0, 0.5, 4.0]  # halves differ; the middle step of odd T is in neither
+        r = R.restate_column(x, (0.5,))
+    assert math.isnan(r["rhat"]) and math.isnan(r["ess"]) and r["ess_lag"] == 0
+    assert r["sd"] == pytest.approx(x.astype(np.float64).std(ddof=1), rel=1e-15) and r["sd"] > 0
+    nan = float("nan")
+    got = {k: [v] for k, v in dict(flags=0, min=r["min"], max=r["max"], quantiles=r["quantiles"], mean=r["mean"],
+                                   sd=r["sd"], rhat=nan, ess=nan, mcse_mean=nan, ess_lag=0).items()}
+    R.check(got, {0: r})
+    got["ess"] = [1.0]
+    with pytest.raises(AssertionError):
+        R.check(got, {0: r})
+
+
+def test_debug_rows_acov_bad_arguments():
+    rows = np.zeros((8 * 2, 3), np.float32)  # nsteps 8, nc 2, np 2: n = 4
+    for nsteps, nlags in ((8, 0), (8, 5), (3, 1)):
+        with pytest.raises(McxError):
+            E.debug_rows_acov(rows, nsteps, 2, nlags)
