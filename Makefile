@@ -11,7 +11,7 @@ all: lib oracle
 lib:
 	$(MAKE) -j6 mcpar_amd/libmcx.so
 
-OBJS = $(CSRC)/mcx_engine.o $(CSRC)/mcx_plan.o $(CSRC)/mcx_exchange.o $(CSRC)/mcx_sink.o $(CSRC)/mcx_murray.o $(CSRC)/mcx_k_fast.o $(CSRC)/mcx_k_fastb.o $(CSRC)/mcx_k_fastb_full.o $(CSRC)/mcx_k_fast_full.o $(CSRC)/mcx_k_pregen.o $(CSRC)/mcx_k_generic_burn.o \
+OBJS = $(CSRC)/mcx_engine.o $(CSRC)/mcx_run.o $(CSRC)/mcx_plan.o $(CSRC)/mcx_exchange.o $(CSRC)/mcx_sink.o $(CSRC)/mcx_murray.o $(CSRC)/mcx_k_fast.o $(CSRC)/mcx_k_fastb.o $(CSRC)/mcx_k_fastb_full.o $(CSRC)/mcx_k_fast_full.o $(CSRC)/mcx_k_pregen.o $(CSRC)/mcx_k_generic_burn.o \
        $(CSRC)/mcx_k_generic_main.o $(CSRC)/mcx_k_persist.o $(CSRC)/mcx_user.o $(CSRC)/mcx_summary.o
 HDRS = $(CSRC)/mcx_device.hpp $(CSRC)/mcx_numerics.hpp $(CSRC)/mcx_launch.hpp $(CSRC)/mcx_persist.hpp $(CSRC)/mcx_engine_internal.hpp include/mcx.h
 

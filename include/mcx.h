@@ -439,6 +439,13 @@ int mcx_debug_copy_bandwidth(size_t bytes, int reps, double *gbps);
  * wavefronts per workgroup of lpc2 lanes per chain x bpl blocks per lane, and who generates what: tab[3][16][24] item
  * codes (0xffffffff ends a wavefront's list; kind << 14 | step pair << 4 | (owner, block)) */
 int mcx_debug_persist_deal(int lpc2, int bpl, int own, int *rec, int *ksteps, uint32_t *tab, int max_words);
+/* host logic of mcx_run in small-n mode, for tests (no device): the stretch of a plan (mcx_plan) that one launch of the
+ * one-launch kernel takes when the executor stands at items[index] -- items [index, *end) -- and out5 = its burn-in steps,
+ * main-loop steps, 1 if it starts the moments, its first main-loop step, and the step of its main loop after which the
+ * kernel snapshots the slot (or -1).  Zero steps and *end = index: nothing to merge there, the item is executed by itself.
+ * gather_in_flight: the last run's final gather has not been waited for yet. */
+int mcx_debug_small_stretch(const mcx_plan_item *items, int nitems, int index, int nsamp, int gather_in_flight,
+                            int *end, int *out5);
 /* the per-pair screen of the Murray sweeps alone (mcx_screen.hpp; np = 16 or 32), for tests: nact chains x[nact][d], in
  * groups of 128 as given, against N Gaussians musig[N][d][2] = (mu, sig2); sums != 0: the sum sweeps' bound (176), else
  * the min-arg sweep's (chain j's own Gaussian is own0 + j).  masks[(N + 63) / 64][(nact + 127) / 128]: bit b of word w

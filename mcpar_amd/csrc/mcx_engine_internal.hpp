@@ -1,7 +1,8 @@
 // mcx_engine_internal.hpp -- what the translation units of libmcx.so's host side share: the engine's state, the error
 // and check macros, the device buffers, and the handful of functions that cross the seams between
-//   mcx_engine.hip    the C ABI's create / destroy / options / run (the plan executor) / getters / standalone operators
-//   mcx_plan.hip      the schedule of one run (pure host logic, exported as mcx_plan)
+//   mcx_engine.hip    the C ABI's create / destroy / options / getters / standalone operators, likelihood and covariance set-up
+//   mcx_run.hip       mcx_run: the plan executor run_once, its launch helpers, the meeting lock, the ends of a run
+//   mcx_plan.hip      the schedule of one run and the small-n stretches of it (pure host logic, exported as mcx_plan)
 //   mcx_exchange.hip  the inter-shard exchange: begin / wait / publish, the RCCL shim, mcx_exchange_rccl_*
 //   mcx_sink.hip      the streaming sample sink, its text side, mcx_samples_text / mcx_format_rows
 //   mcx_murray.hip    genRemote on device buffers: draws, sweeps, decisions, the two exact screens
@@ -283,7 +284,7 @@ struct mcx_engine {
   // native RCCL exchange (mcx_exchange_rccl_*): in-place ncclAllGather of the musigall slots on a side stream
   ncclComm_t xcomm = nullptr;
   bool xcomm_owned = false;
-  // MCX_OPT_ASYNC_RUN: a run whose kernels are queued and whose end nobody has waited for yet (mcx_engine.hip: finish_pending)
+  // MCX_OPT_ASYNC_RUN: a run whose kernels are queued and whose end nobody has waited for yet (mcx_run.hip: finish_pending)
   int opt_async_run = 0;
   int opt_reference_calls = 0;  // MCX_OPT_REFERENCE_CALLS: make the reference's discarded per-chain L(1, pvals_j) calls (host functors)
   struct PendingRun {
@@ -366,7 +367,7 @@ struct mcx_engine {
 // every entry point may be called from a thread whose current device is another one; whatever an asynchronous run
 // (MCX_OPT_ASYNC_RUN) left in flight is finished first -- waited for, its counters taken, a run whose tuner meeting was
 // abandoned repeated -- so that no entry point ever sees a run half done (mcx_run itself queues behind it instead)
-int finish_pending(mcx_engine *e);  // mcx_engine.hip
+int finish_pending(mcx_engine *e);  // mcx_run.hip
 static inline int enter_raw(mcx_engine *e)
 {
   if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
@@ -415,9 +416,27 @@ struct PlanCfg {
   int sink_block;  // > 0: cut the main loop into blocks of this many steps for the sample sink
 };
 MCXI std::vector<mcx_plan_item> build_plan(const PlanCfg &c);  // mcx_plan.hip
+// what one launch of the one-launch small-n kernel takes of the plan from item `pi` on: items [pi, end)
+struct SmallStretch {
+  size_t end;
+  int burn, main, init_moments, first_main;  // steps of either loop, MCX_PLAN_INIT_MOMENTS swallowed, first main-loop step
+  int snap_after;                            // step of the stretch's main loop after which the slot is rewritten, or -1
+  bool plan_over;                            // nothing but the slot's final publish is left behind it
+};
+MCXI SmallStretch small_stretch(const std::vector<mcx_plan_item> &plan, size_t pi, int nsamp, bool gather_in_flight);  // mcx_plan.hip
 
 constexpr int MCX_INTERNAL_MEET_ABANDONED = 1000;  // run_once: a tuner meeting of the one-launch kernel was abandoned
-MCXI int meet_release(mcx_engine *e, bool stream_is_idle);  // mcx_engine.hip
+// mcx_run.hip
+MCXI int meet_release(mcx_engine *e, bool stream_is_idle);
+MCXI void fill_step(mcx_engine *e, StepArgs &a, uint32_t t, int isamp, bool main, size_t maskrow, int samprow, int remote);
+MCXI int launch_propose(mcx_engine *e, const StepArgs &a);
+
+// mcx_engine.hip
+MCXI int lik_setup(LikDev &L, const mcx_vlfunc *f, int np, hipStream_t st);
+MCXI int eval_device(const LikDev &L, const float *x, float *y, int n, int d, hipStream_t st);
+MCXI int covar_install(mcx_engine *e, const float *incov, float *cov_out, bool sync = true);
+MCXI void prof_collect(mcx_engine *e);
+MCXI void samp_vbase(const mcx_engine *e, int isamp, float **px, float **pl);
 
 // mcx_exchange.hip
 MCXI int exchange_begin(mcx_engine *e);
@@ -430,7 +449,6 @@ MCXI bool exchange_tail_may_stay_in_flight(const mcx_engine *e);
 // mcx_sink.hip
 MCXI int sink_block_done(mcx_engine *e, int done, int nsteps, int seq);
 MCXI int sink_drain(mcx_engine *e, int nblocks_done);
-MCXI void samp_vbase(const mcx_engine *e, int isamp, float **px, float **pl);  // (mcx_engine.hip)
 
 // cells of the Murray screens' "pairs kept" counters behind mcx_engine::nact (= CULL_NCOUNT of mcx_remote.hpp, which only
 // mcx_murray.hip includes and checks)

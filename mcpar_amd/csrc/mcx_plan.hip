@@ -90,6 +90,64 @@ std::vector<mcx_plan_item> build_plan(const PlanCfg &c)
   return p;
 }
 
+// Small-n mode (mcx_persist.hpp): the stretch of local steps that one k_run_small launch takes when the executor stands
+// at item `pi` -- the burn-in with its tuner events, the start of the moments and every run of consecutive main-loop
+// segments.  Nothing to merge at `pi` (an init_moments item that no main segment follows, or an item of another kind):
+// zero steps, end = pi, and the executor handles the item itself.
+SmallStretch small_stretch(const std::vector<mcx_plan_item> &plan, size_t pi, int nsamp, bool gather_in_flight)
+{
+  SmallStretch s = {pi, 0, 0, 0, 0, -1, false};
+  const int kind = plan[pi].kind;
+  if (kind != MCX_PLAN_BURN_SEGMENT && kind != MCX_PLAN_INIT_MOMENTS && kind != MCX_PLAN_MAIN_SEGMENT) return s;
+  size_t pj = pi;
+  while (pj < plan.size() && (plan[pj].kind == MCX_PLAN_BURN_SEGMENT || plan[pj].kind == MCX_PLAN_TUNER)) {
+    if (plan[pj].kind == MCX_PLAN_BURN_SEGMENT) s.burn += plan[pj].nsteps;
+    ++pj;
+  }
+  const size_t pj_burn_end = pj;
+  if (pj + 1 < plan.size() && plan[pj].kind == MCX_PLAN_INIT_MOMENTS) {
+    // (a sharded run's first sync point is step 0: its slot publish -- of zero steps, i.e. nothing -- sits between
+    // the start of the moments and the first segment and must not cost the run a second launch)
+    size_t pk = pj + 1;
+    while (pk < plan.size() && plan[pk].kind == MCX_PLAN_PUBLISH && plan[pk].first == 0) ++pk;
+    if (pk < plan.size() && plan[pk].kind == MCX_PLAN_MAIN_SEGMENT) {
+      s.init_moments = 1;
+      pj = pk;
+    }
+  }
+  if (pj < plan.size() && plan[pj].kind == MCX_PLAN_MAIN_SEGMENT) {
+    s.first_main = plan[pj].first;
+    while (pj < plan.size() && plan[pj].kind == MCX_PLAN_MAIN_SEGMENT && plan[pj].first == s.first_main + s.main) {
+      if (plan[pj].aux >= 0) s.snap_after = s.main + plan[pj].aux;  // the last sync point inside the stretch
+      s.main += plan[pj].nsteps;
+      ++pj;
+    }
+  }
+  if (gather_in_flight && s.burn > 0 && s.main > 0 && s.snap_after >= 0) {
+    // The last run's final gather is still in flight (finish_tail) and this stretch will rewrite the slot it
+    // reads: the burn-in, which does not touch the slot, goes first in a launch of its own and runs under the
+    // gather; the main-loop stretch follows in a second launch, behind the wait.
+    pj = pj_burn_end;
+    s.main = 0; s.init_moments = 0; s.first_main = 0; s.snap_after = -1;
+  }
+  if (s.burn + s.main == 0) return s;
+  s.end = pj;
+  // (what may be left of the plan behind a run's last launch: the slot's final publish, which the launch does itself / of no step)
+  s.plan_over = true;
+  for (size_t pk = pj; pk < plan.size(); ++pk) s.plan_over = s.plan_over && plan[pk].kind == MCX_PLAN_PUBLISH && plan[pk].first == nsamp;
+  return s;
+}
+
+extern "C" int mcx_debug_small_stretch(const mcx_plan_item *items, int nitems, int index, int nsamp, int gather_in_flight,
+                                       int *end, int *out5)
+{
+  if (!items || nitems < 1 || index < 0 || index >= nitems || nsamp < 0 || !end || !out5) return fail(MCX_ERR_INVALID, "bad arguments");
+  const SmallStretch s = small_stretch(std::vector<mcx_plan_item>(items, items + nitems), (size_t)index, nsamp, gather_in_flight != 0);
+  *end = (int)s.end;
+  out5[0] = s.burn; out5[1] = s.main; out5[2] = s.init_moments; out5[3] = s.first_main; out5[4] = s.snap_after;
+  return MCX_OK;
+}
+
 extern "C" int mcx_plan(int nsamp, int nburn, int sync, float pl, uint32_t seed, uint32_t tbase, int nshards,
                         int eager, int fused, int max_segment, int has_output_hook, int sink_block_steps,
                         mcx_plan_item *items, int max_items, int *nitems)

@@ -1,5 +1,5 @@
 // mcx_remote.hpp -- the Murray inter-chain proposal, MCPar::genRemote (src/mcpar.cc:315-451), as gfx950 kernels.
-// Included by mcx_engine.hip only (the fused step kernels never see it).
+// Included by mcx_murray.hip only (the fused step kernels never see it).
 #pragma once
 #include "mcx_device.hpp"
 

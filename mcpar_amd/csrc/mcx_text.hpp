@@ -5,7 +5,7 @@
 //   k_text_sizes   bytes of every number's field, summed per workgroup
 //   k_text_scan    one workgroup: the sums become byte offsets, the last one the total
 //   k_text_write   the fields again, placed: neighbouring lanes write neighbouring bytes
-// Included by mcx_engine.hip only.
+// Included by mcx_sink.hip only.
 #pragma once
 #include "fmt_g6.hpp"
 #include "mcx_device.hpp"

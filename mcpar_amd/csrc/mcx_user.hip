@@ -249,7 +249,7 @@ int user_lik_get(const char *source, int np, std::shared_ptr<UserLik> *out)
   return MCX_OK;
 }
 
-// which of the user's step kernels a segment takes: the same tests as launch_fused_plain for the built-ins
+// which of the user's step kernels a segment takes: the same tests as fused_choice (mcx_run.hip) for the built-ins
 int user_lik_variant(int lpc, const mcx::SegArgs &a)
 {
   if (lpc <= 8 && a.vec4 && !a.mask) return a.diag ? 0 : 1;  // hot-path kernel, diagonal / full factor

@@ -107,6 +107,17 @@ def plan(nsamp, nburn, sync=10, pl=0.9, seed=8675309, tbase=0, nshards=1, eager=
     return [(PLAN_NAMES[it.kind], it.first, it.nsteps, it.aux) for it in items[:n.value]]
 
 
+def small_stretch(items, index, nsamp, gather_in_flight=False):
+    """what one launch of the one-launch small-n kernel takes of the plan `items` (as plan() returns it) when mcx_run stands
+    at items[index]: (end, burn steps, main steps, init_moments, first main step, snap_after); zero steps and end = index
+    where nothing can be merged (host logic only, needs no GPU)"""
+    kinds = {v: k for k, v in PLAN_NAMES.items()}
+    arr = (PlanItem * max(1, len(items)))(*[PlanItem(kinds[k], f, n, a) for k, f, n, a in items])
+    end, out = C.c_int(0), (C.c_int * 5)()
+    check(load().mcx_debug_small_stretch(arr, len(items), index, nsamp, int(bool(gather_in_flight)), C.byref(end), out))
+    return (end.value,) + tuple(out)
+
+
 def _probs(probs):
     p = np.ascontiguousarray(np.asarray(probs, np.float64).reshape(-1))
     return p, p.ctypes.data_as(C.POINTER(C.c_double))
