@@ -374,6 +374,24 @@ int mcx_samples_summary(mcx_engine *e, int first_step, int nsteps, const double 
 int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs,
                      mcx_col_summary *cols, double *quantiles);
 
+/* ---- covariance of the sample store, on the device -----------------
+ * Columns as above (the np parameters, then log L), N = nsteps * nc rows, nsteps >= 1 and N >= 2.
+ *   mean[c]    = column sum / N: the number mcx_samples_summary reports, bit for bit
+ *   cov[i][j]  = sum over the rows of (x_i - mean[i]) (x_j - mean[j]) / (N - 1), fp64 throughout, centred (two passes);
+ *                the full symmetric matrix, row-major, cov[i][j] and cov[j][i] the same bits
+ * A column holding an inf or NaN has MCX_SUMMARY_NONFINITE in flags[c], NaN mean[c] and NaN in row and column c of cov;
+ * every other entry is what it would be without that column.  MCX_ERR_INVALID in the cases mcx_samples_summary refuses
+ * (the store does not hold the range).  The same store and arguments give the same bytes.
+ * mean[np+1], cov[(np+1)*(np+1)] row-major, flags[np+1] (MCX_SUMMARY_*; may be NULL) */
+int mcx_samples_covariance(mcx_engine *e, int first_step, int nsteps, double *mean, double *cov, int *flags);
+/* the same for host rows in MCout layout (what a sink / MCout collected): uploaded, computed on the device */
+int mcx_rows_covariance(const float *rows, int nsteps, int nc, int np, double *mean, double *cov, int *flags);
+/* host only, no device: the np x np parameter block of cov (leading dimension ld >= np), times scale
+ * (scale <= 0: 2.38^2 / np, the Gaussian-target optimum of Gelman, Roberts & Gilks), rounded to float and made exactly
+ * symmetric -> incov[np*np], ready for mcx_run / mcx_covar_setup / MCPar::run.  MCX_ERR_INVALID, with the column or
+ * pivot named in mcx_last_error, when an entry is not finite or the float Cholesky mcx_covar_setup uses rejects it. */
+int mcx_proposal_from_cov(int np, const double *cov, int ld, double scale, float *incov);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote
@@ -477,6 +495,9 @@ int mcx_debug_summary_windows(mcx_engine *e, int first_step, int nsteps, int *nw
  * on its mean (n M times the acov of mcx_debug_summary_finish); sumsq[np + 1]: sum over all N values of (x - mean)^2.
  * A column that is not finite gets NaN in both. */
 int mcx_debug_rows_acov(const float *rows, int nsteps, int nc, int np, int nlags, double *acov, double *sumsq);
+/* mcx_samples_covariance with HIP events around its device passes, for tools/covariance_bench.py: ms[0] the column-sum
+ * sweep (k_sum_moments, the pass mcx_samples_summary shares), ms[1] the covariance sweep, ms[2] the reducer of its partials */
+int mcx_debug_covariance_times(mcx_engine *e, int first_step, int nsteps, double *ms);
 /* normals of stream `stream`, counter (t, g0+i, a, q) for i < n: out[n*4] */
 int mcx_debug_normals(uint32_t seed, uint32_t stream, uint32_t t, uint32_t g0, uint32_t a,
                       uint32_t q, int n, float *out);

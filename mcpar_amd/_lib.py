@@ -98,6 +98,10 @@ def load():
                                      C.c_longlong, dp, C.c_int, C.c_int, vp, dp, C.POINTER(C.c_int)],
         "mcx_debug_summary_windows": [vp, C.c_int, C.c_int, C.POINTER(C.c_int)],
         "mcx_debug_rows_acov": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp],
+        "mcx_samples_covariance": [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int)],
+        "mcx_rows_covariance": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int)],
+        "mcx_proposal_from_cov": [C.c_int, dp, C.c_int, C.c_double, fp],
+        "mcx_debug_covariance_times": [vp, C.c_int, C.c_int, dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

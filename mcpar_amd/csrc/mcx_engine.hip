@@ -60,8 +60,9 @@ extern "C" int mcx_device_info(char *name, size_t namelen, int *cu_count, size_t
 // small helpers
 // ---------------------------------------------------------------------------------------------
 // Cholesky factor, lower, row-major, strict upper triangle zeroed: the role of spotrf('U') on the
-// column-major view in MCPar::covar_setup (src/mcpar.cc:470-480).  Host side, np <= 32, once per run.
-static int cholesky_lower(int d, float *a)
+// column-major view in MCPar::covar_setup (src/mcpar.cc:470-480).  Host side, np <= 32, once per run.  Returns 0, or
+// 1 + the index of the pivot that is not > 0 (mcx_proposal_from_cov asks the same function for its verdict).
+int cholesky_lower(int d, float *a)
 {
   for (int i = 0; i < d; ++i) {
     for (int j = 0; j <= i; ++j) {

@@ -435,6 +435,7 @@ MCXI int launch_propose(mcx_engine *e, const StepArgs &a);
 MCXI int lik_setup(LikDev &L, const mcx_vlfunc *f, int np, hipStream_t st);
 MCXI int eval_device(const LikDev &L, const float *x, float *y, int n, int d, hipStream_t st);
 MCXI int covar_install(mcx_engine *e, const float *incov, float *cov_out, bool sync = true);
+MCXI int cholesky_lower(int d, float *a);  // the float factorisation covar_install accepts or rejects an incov by
 MCXI void prof_collect(mcx_engine *e);
 MCXI void samp_vbase(const mcx_engine *e, int isamp, float **px, float **pl);
 

@@ -2,7 +2,7 @@
 // only through its library API: SURVEY fact 3).
 //   mcpar-run [--func rosen1|rosen2|rosen2fixed|gauss|dgauss|mix | --func-source FILE.hip [--par a,b,...]] [--np D]
 //             [--nc CHAINS] [--nsamp N] [--nburn B] [--pl P] [--sync S] [--ncomp K] [--quiet] [--iter] [--binary]
-//             [--stream-text] [--out FILE] [--summary FILE]
+//             [--stream-text] [--out FILE] [--summary FILE] [--covariance FILE] [--proposal FILE] [--incov FILE]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -10,6 +10,11 @@
 // text goes to FILE, every rank writing its own share at its place (MCout::text_file) instead of through rank 0.
 // --summary FILE: one row per column (p0 .. p{np-1}, then LL) of the kept rows' summary on the GPU (mcx_rows_summary):
 // name mean sd q01 q50 q99 rhat ess mcse.  Needs the rows on the host: not with --stream-text, and one rank only.
+// --covariance FILE: mean and covariance matrix of the kept rows on the GPU (mcx_rows_covariance): header `name mean p0 ..
+// LL`, then one row per column: name, mean, the matrix row.  --proposal FILE: np rows of np numbers, that matrix's
+// parameter block as the proposal covariance of a next run (mcx_proposal_from_cov, scale 2.38^2 / np).  Both under the
+// conditions of --summary.  --incov FILE: np * np whitespace-separated numbers, the proposal covariance of this run
+// (MCPar::run's incov) -- `--proposal P.txt` of a pilot run, then `--incov P.txt`, is the adaptive two-stage job.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -56,13 +61,88 @@ static int write_summary(const char *path, MCout &rows, int nsamp, int nc, int n
   return fclose(f) == 0 ? 0 : 1;
 }
 
+// --covariance / --proposal: the covariance of MCout's rows, and the proposal covariance made of it
+static int write_covariance(const char *cov_path, const char *prop_path, MCout &rows, int nsamp, int nc, int np)
+{
+  const size_t ncol = (size_t)np + 1;
+  std::vector<double> mean(ncol), cov(ncol * ncol);
+  if ((long long)rows.size() != (long long)nsamp * nc || (long long)nsamp * nc < 2) {
+    std::cerr << "--covariance / --proposal: " << rows.size() << " rows stored, a covariance needs nsamp * nc >= 2 of them\n";
+    return 1;
+  }
+  if (mcx_rows_covariance(rows.getpset(0), nsamp, nc, np, mean.data(), cov.data(), 0) != MCX_OK) {
+    std::cerr << "--covariance / --proposal: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  if (cov_path) {
+    FILE *f = fopen(cov_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << cov_path << "\n";
+      return 1;
+    }
+    fprintf(f, "name mean");
+    for (int c = 0; c <= np; ++c) fprintf(f, " %s", c < np ? ("p" + std::to_string(c)).c_str() : "LL");
+    fprintf(f, "\n");
+    for (int c = 0; c <= np; ++c) {
+      fprintf(f, "%s %.17g", c < np ? ("p" + std::to_string(c)).c_str() : "LL", mean[c]);
+      for (int k = 0; k <= np; ++k) fprintf(f, " %.17g", cov[c * ncol + k]);
+      fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) return 1;
+  }
+  if (prop_path) {
+    std::vector<float> prop((size_t)np * np);
+    if (mcx_proposal_from_cov(np, cov.data(), np + 1, 0.0, prop.data()) != MCX_OK) {
+      std::cerr << "--proposal: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    FILE *f = fopen(prop_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << prop_path << "\n";
+      return 1;
+    }
+    for (int i = 0; i < np; ++i)
+      for (int j = 0; j < np; ++j) fprintf(f, "%.9g%c", prop[(size_t)i * np + j], j + 1 < np ? ' ' : '\n');
+    if (fclose(f) != 0) return 1;
+  }
+  return 0;
+}
+
+// --incov: np * np numbers -> incov, checked by the factorisation MCPar::covar_setup will use
+static int read_incov(const char *path, int np, std::vector<float> &incov)
+{
+  FILE *f = fopen(path, "r");
+  if (!f) {
+    std::cerr << "--incov: cannot read " << path << "\n";
+    return 1;
+  }
+  std::vector<double> v;
+  double t;
+  while (fscanf(f, "%lf", &t) == 1) v.push_back(t);
+  const bool clean = feof(f) != 0;
+  fclose(f);
+  if (!clean || v.size() != (size_t)np * np) {
+    std::cerr << "--incov: " << path << " holds " << v.size() << " numbers" << (clean ? "" : " before something that is not one")
+              << ", np * np = " << (size_t)np * np << " are needed\n";
+    return 1;
+  }
+  incov.resize(v.size());
+  for (size_t i = 0; i < v.size(); ++i) v[i] = (double)(incov[i] = (float)v[i]);
+  std::vector<float> sym(v.size());
+  if (mcx_proposal_from_cov(np, v.data(), np, 1.0, sym.data()) != MCX_OK) {
+    std::cerr << "--incov: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  return 0;
+}
+
 int main(int argc, char *argv[])
 {
   std::string func = "rosen1";
   int np = 16, nc = 4096, nsamp = 100, nburn = 500, sync = 10, ncomp = 8;
   float pl = 1.0f;
   bool quiet = false, iter = false, binary = false, stream_text = false;
-  std::string out_file, func_source, summary_file;
+  std::string out_file, func_source, summary_file, covariance_file, proposal_file, incov_file;
   std::vector<float> user_par;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -86,6 +166,9 @@ int main(int argc, char *argv[])
     else if (a == "--stream-text") stream_text = true;  // the same text, formatted on the GPU, nothing kept on the host
     else if (a == "--out") out_file = val();
     else if (a == "--summary") summary_file = val();
+    else if (a == "--covariance") covariance_file = val();
+    else if (a == "--proposal") proposal_file = val();
+    else if (a == "--incov") incov_file = val();
     else { std::cerr << "unknown option " << a << "\n"; return 2; }
   }
   MPI_Init(&argc, &argv);
@@ -95,6 +178,13 @@ int main(int argc, char *argv[])
   if (!summary_file.empty() && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--summary needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if ((!covariance_file.empty() || !proposal_file.empty()) && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--covariance / --proposal need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -140,6 +230,11 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
+  std::vector<float> incov;
+  if (!incov_file.empty() && read_incov(incov_file.c_str(), np, incov) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
   std::vector<float> pinit((size_t)nc * np);
   for (int j = 0; j < nc; ++j)
     for (int i = 0; i < np; ++i)
@@ -147,7 +242,7 @@ int main(int argc, char *argv[])
   try {
     MCPar mcpar(np, nc, size, rank, pl, 0.2f, 0.5f, 0.2f, 1.5f, sync);
     auto t0 = std::chrono::steady_clock::now();
-    mcpar.run(nsamp, nburn, pinit.data(), *L, rslts);
+    mcpar.run(nsamp, nburn, pinit.data(), *L, rslts, incov.empty() ? 0 : incov.data());
     double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (iter && !quiet) {  // (the numbers through fmtg6 like MCout::output: the same characters as `cout << float`)
       std::vector<char> line((size_t)(np + 1) * 18 + 32);
@@ -174,6 +269,12 @@ int main(int argc, char *argv[])
   }
   rslts.text_file(0);
   if (!summary_file.empty() && write_summary(summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if ((!covariance_file.empty() || !proposal_file.empty()) &&
+      write_covariance(covariance_file.empty() ? 0 : covariance_file.c_str(), proposal_file.empty() ? 0 : proposal_file.c_str(),
+                       rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

@@ -153,6 +153,44 @@ def debug_rows_acov(rows, nsteps, nc, nlags):
     return acov, sumsq
 
 
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _covariance_dict(mean, cov, flags):
+    """mean, cov, flags and corr = cov_ij / sqrt(cov_ii cov_jj): NaN where a variance is 0 or NaN, else exactly 1 on the diagonal"""
+    v = np.diag(cov).copy()
+    v[~(v > 0)] = np.nan
+    s = np.sqrt(v)
+    with np.errstate(invalid="ignore"):
+        corr = cov / np.outer(s, s)
+    k = np.flatnonzero(~np.isnan(v))
+    corr[k, k] = 1.0
+    return dict(mean=mean, cov=cov, corr=corr, flags=flags)
+
+
+def rows_covariance(rows, nsteps, nc):
+    """mcx_rows_covariance: Engine.covariance's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    mean, cov, flags = np.zeros(ncol), np.zeros((ncol, ncol)), np.zeros(ncol, np.int32)
+    check(load().mcx_rows_covariance(_fp(rows), nsteps, nc, ncol - 1, _dp(mean), _dp(cov),
+                                     flags.ctypes.data_as(C.POINTER(C.c_int))))
+    return _covariance_dict(mean, cov, flags)
+
+
+def proposal_from_cov(cov, np_, scale=None):
+    """mcx_proposal_from_cov (host only): the np_ x np_ parameter block of cov (any leading dimension >= np_) times scale
+    (None: 2.38^2 / np_), rounded to float32 and exactly symmetric -- the incov of Engine.run.  McxError when an entry is
+    not finite or the float Cholesky of mcx_covar_setup rejects the matrix."""
+    cov = np.ascontiguousarray(cov, np.float64)
+    if cov.ndim != 2 or cov.shape[0] < np_ or cov.shape[1] < np_:
+        raise ValueError("cov must be a matrix of at least np_ x np_ entries")
+    out = np.zeros((np_, np_), np.float32)
+    check(load().mcx_proposal_from_cov(np_, _dp(cov), cov.shape[1], 0.0 if scale is None else float(scale), _fp(out)))
+    return out
+
+
 def debug_summary_finish(n, M, mean, var_all, var_means, acov, ostat, N, probs=(), flags=0):
     """mcx_debug_summary_finish for one column: (record of SUMMARY_DTYPE, quantiles, lags still needed)"""
     a = np.ascontiguousarray(acov, np.float64)
@@ -495,6 +533,33 @@ class Engine:
         check(load().mcx_samples_summary(self.h, first_step, nsteps, pp, len(p), cols.ctypes.data_as(C.c_void_p),
                                          q.ctypes.data_as(C.POINTER(C.c_double))))
         return _summary_dict(cols, q)
+
+    def covariance(self, first_step=0, nsteps=None):
+        """mcx_samples_covariance of kept steps [first_step, first_step + nsteps): a dict of mean [np + 1] (summary()'s,
+        bit for bit), cov and corr [np + 1, np + 1] (the parameters, then log L) and flags [np + 1]"""
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        ncol = self.np + 1
+        mean, cov, flags = np.zeros(ncol), np.zeros((ncol, ncol)), np.zeros(ncol, np.int32)
+        check(load().mcx_samples_covariance(self.h, first_step, nsteps, _dp(mean), _dp(cov),
+                                            flags.ctypes.data_as(C.POINTER(C.c_int))))
+        return _covariance_dict(mean, cov, flags)
+
+    def covariance_times(self, first_step=0, nsteps=None):
+        """mcx_debug_covariance_times: ms of (the column-sum sweep, the covariance sweep, the partials' reducer) of one call"""
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        ms = np.zeros(3)
+        check(load().mcx_debug_covariance_times(self.h, first_step, nsteps, _dp(ms)))
+        return ms
+
+    def proposal_cov(self, scale=None, first_step=0, nsteps=None):
+        """covariance() then proposal_from_cov(): the incov of the next run from this run's store"""
+        return proposal_from_cov(self.covariance(first_step, nsteps)["cov"], self.np, scale)
 
     def summary_windows(self, first_step=0, nsteps=None):
         """how many 32-lag autocovariance windows the summary of that range computes (mcx_debug_summary_windows)"""
