@@ -470,6 +470,15 @@ int mcx_debug_small_stretch(const mcx_plan_item *items, int nitems, int index, i
  * for group g set = Gaussian 64 w + b may matter to some chain of the group. */
 int mcx_debug_murray_screen(int d, int nact, int N, const float *x, const float *musig, int own0, int sums,
                             unsigned long long *masks);
+/* host logic of a Murray step, for tests (no device): what the counter block of one kernel turn says.  words[nwords >= 132],
+ * 64-bit: [0] the two survivor counters (turn `it` counted in the low half when `it` is even, in the high half when odd),
+ * [1, 65) the cells of the pairs kept by the min-arg sweep's screen, [65, 129) those of the sum sweeps' screens, [129] a
+ * word of the kernels' own, [130, 132) tried[4] as 32-bit words: chains that came as far as candidate c of a turn over
+ * candidates (multi != 0).  nact_before chains went into the turn, against N Gaussians.  out5 = the survivors, the
+ * passes of the reference the turn stood for, the pairs those passes swept, the pairs kept by the min-arg screen and by
+ * the sum screens so far (both 0 unless cull_can != 0). */
+int mcx_debug_murray_decode(const unsigned long long *words, int nwords, int it, int multi, int cull_can,
+                            int nact_before, int N, unsigned long long *out5);
 /* device evaluation of the arithmetic primitives for bit-exactness tests:
  * what = 0 logf(bits), 1 expf(bits), 2 sin(2 pi w/2^32), 3 cos(...), 4 u24, 5 uopen,
  * 6 philox word 0 of ctr=(w,0,0,0) key=(0,0), 7 the kernels' lean sqrt, 8 IEEE sqrtf,

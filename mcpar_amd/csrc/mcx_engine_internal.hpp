@@ -5,7 +5,8 @@
 //   mcx_plan.hip      the schedule of one run and the small-n stretches of it (pure host logic, exported as mcx_plan)
 //   mcx_exchange.hip  the inter-shard exchange: begin / wait / publish, the RCCL shim, mcx_exchange_rccl_*
 //   mcx_sink.hip      the streaming sample sink, its text side, mcx_samples_text / mcx_format_rows
-//   mcx_murray.hip    genRemote on device buffers: draws, sweeps, decisions, the two exact screens
+//   mcx_murray.hip    genRemote on device buffers: remote_device over one MurrayStep context (min_arg_sweep, murray_passes with
+//                     pass_big / pass_multi / pass_plain, wait_pass_counters, decode_pass), screen_pass / sweep_pass, the screens
 // Nothing here is part of the library's interface (include/mcx.h is); every cross-unit function has hidden visibility.
 #pragma once
 #include "../../include/mcx.h"
@@ -223,9 +224,8 @@ struct mcx_engine {
   DevBuf<uint32_t> acc_cnt, acc_slots;
   int nslots = 0;
   DevBuf<unsigned long long> ctr;  // [0..3] tuner (k_tuner), [4] main-loop accepts
-  DevBuf<int> active0, active1, nact, ntrace;  // nact: [0] survivors of the pass; as u64: [1 .. 1 + CULL_NCOUNT) / the next
-                                               // CULL_NCOUNT cells: pairs kept by the exclusion tests of the min-arg sweep /
-                                               // of the sum sweeps of this genRemote call (spread: same-address atomics are slow)
+  DevBuf<int> active0, active1, nact, ntrace;  // nact: a Murray pass's counter block (MurrayCounters, below); the screens'
+                                               // "pairs kept" counts are spread over cells: same-address atomics are slow
   // exact exclusion of far Gaussians in the Murray sweeps (mcx_remote.hpp, k_cull_*)
   DevBuf<unsigned> cull_keys, cull_hist;
   DevBuf<int> cull_sorted;
@@ -253,7 +253,7 @@ struct mcx_engine {
   PinBuf<float> h_ptrial, h_lytrial;
   PinBuf<unsigned long long> h_ctr;  // the run's counters, read back once at its end
   unsigned long long remote_serial = 0;  // Murray passes so far (what k_remote_decide signs its counters with)
-  PinBuf<unsigned long long> h_nact;  // a Murray pass's survivor count (and the exclusion tests' counters)
+  PinBuf<unsigned long long> h_nact;  // a Murray pass's counter block on the host (MurrayCounters) and its serial number
   std::vector<float> h_cov, h_cov_dev, h_winv;  // h_cov_dev = what cov0 holds
   bool cov_pending = false;  // cov has not been reset to cov0 for the current run yet
   bool cov_offdiag = false;  // cov (device) may hold non-zero entries below the diagonal
@@ -454,6 +454,43 @@ MCXI int sink_drain(mcx_engine *e, int nblocks_done);
 // cells of the Murray screens' "pairs kept" counters behind mcx_engine::nact (= CULL_NCOUNT of mcx_remote.hpp, which only
 // mcx_murray.hip includes and checks)
 constexpr int NACT_CULL_CELLS = 64;
+
+// The counter block of a Murray pass, behind mcx_engine::nact on the device and mirrored in mcx_engine::h_nact (pinned).  In
+// 64-bit words: [0] the two survivor counters as its halves (kernel turn `it` counts in half it & 1 and zeroes the other
+// for the next), [1, 65) the min-arg screen's "pairs kept" cells, [65, 129) the sum screens', [129] the word
+// k_remote_decide counts its workgroups in (low half; left zero), [130, 132) tried[TRIED] of a turn over candidates as
+// 32-bit words.  The host mirror has the pass's serial number behind them, in a word of its own.
+struct MurrayCounters {
+  static constexpr int CELLS = NACT_CULL_CELLS, TRIED = 4;  // TRIED = MULTI_K of mcx_murray.hip, which checks
+  static constexpr int W_SURVIVORS = 0, W_KEPT_MIN = 1, W_KEPT_SUMS = W_KEPT_MIN + CELLS, W_DONE = W_KEPT_SUMS + CELLS,
+                       W_TRIED = W_DONE + 1, WORDS = W_TRIED + TRIED / 2;
+  static constexpr int WORDS_SCREENS = W_DONE;       // what a pass sends home where screens may run: survivors and cells
+  static constexpr int W_SERIAL = WORDS, HOST_WORDS = WORDS + 1;
+  // the device allocation in ints: the words above and four ints nothing uses (the allocation has always had them)
+  static constexpr int DEVICE_INTS = 2 * WORDS + 4;
+  // zeroed at the start of every genRemote call: the screens' cells and the `done` word right behind them
+  static constexpr size_t CALL_ZERO_BYTES = (size_t)(W_TRIED - W_KEPT_MIN) * sizeof(unsigned long long);
+  static int *survivors(int *base, int it) { return base + 2 * W_SURVIVORS + (it & 1); }
+  static const unsigned long long *words(const int *base) { return reinterpret_cast<const unsigned long long *>(base); }
+  static unsigned long long *kept(int *base, bool sums)
+  {
+    return reinterpret_cast<unsigned long long *>(base) + (sums ? W_KEPT_SUMS : W_KEPT_MIN);
+  }
+  static void *call_zero_from(int *base) { return base + 2 * W_KEPT_MIN; }
+  static unsigned *done(int *base) { return reinterpret_cast<unsigned *>(base) + 2 * W_DONE; }
+  static int *tried(int *base) { return base + 2 * W_TRIED; }
+  static const unsigned *tried(const unsigned long long *host) { return reinterpret_cast<const unsigned *>(host + W_TRIED); }
+};
+static_assert(MurrayCounters::DEVICE_INTS == 2 * (1 + 2 * NACT_CULL_CELLS) + 2 + 8, "the allocation does not shrink");
+
+// what the counters of one kernel turn say (mcx_murray.hip: decode_pass; pure host logic, exported as mcx_debug_murray_decode)
+struct PassOutcome {
+  int survivors;                        // chains still rejected
+  int passes;                           // passes of the reference the turn stood for
+  unsigned long long pairs;             // (chain, Gaussian) pairs those passes swept: what remote_pairs grows by
+  unsigned long long kept_min, kept_sums;  // pairs the screens have kept so far in this genRemote call
+};
+MCXI PassOutcome decode_pass(const unsigned long long *back, int it, bool multi, bool cull_can, int nact_before, int N);
 
 // mcx_murray.hip: MCPar::genRemote on device buffers (src/mcpar.cc:315-451)
 MCXI int remote_device(mcx_engine *e, uint32_t t, const float *pvals, const float *musigall, float *ptrial, float *cfac,

@@ -329,6 +329,7 @@ static void never_leave_the_lock_behind(mcx_engine *e, int rc)
 // A run whose last launch reports to its counter slot itself (RunArgs::report): has the serial number arrived?  Spins for
 // at most `spin_us` -- jobs this is about take 0.3-0.5 ms; whoever waits for a longer one loses nothing by sleeping in
 // hipStreamSynchronize instead -- and says whether it saw it.
+// (mcx_murray.hip's wait_pass_counters waits for one pass and yields after 60 us: a different policy on purpose.)
 static bool report_arrived(const unsigned long long *slot, unsigned long long serial, int spin_us)
 {
   const auto t0 = std::chrono::steady_clock::now();

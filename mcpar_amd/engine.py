@@ -251,6 +251,18 @@ def debug_murray_screen(x, musig, own0=0, sums=True):
     return masks
 
 
+def murray_decode(words, it, multi, cull_can, nact_before, N):
+    """what the counter block of one kernel turn of a Murray step says (mcx_debug_murray_decode; host logic only, needs no
+    GPU): (survivors, passes the turn stood for, pairs those passes swept, pairs kept by the min-arg screen, by the sum
+    screens) from words[>= 132] uint64 as include/mcx.h lays them out"""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    out = np.zeros(5, np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    check(load().mcx_debug_murray_decode(w.ctypes.data_as(u64p), w.size, it, int(bool(multi)), int(bool(cull_can)), nact_before, N,
+                                         out.ctypes.data_as(u64p)))
+    return tuple(int(v) for v in out)
+
+
 def debug_normals(seed, stream, t, g0, a, q, n):
     out = np.empty((n, 4), np.float32)
     check(load().mcx_debug_normals(seed, stream, t, g0, a, q, n, _fp(out)))

@@ -49,6 +49,115 @@ def test_gen_remote_same_bits_with_and_without_exclusion(d, n, nshards):
         eg.close()
 
 
+@pytest.mark.parametrize("d,n,nshards", [(65, 130, 1), (12, 130, 2)])
+def test_gen_remote_same_bits_outside_the_power_of_two_kernels(d, n, nshards):
+    """np = 65: the first past the register kernels (pass_big: draw, sweep and decision of a pass in one kernel, the
+    survivors by copy); np = 12: not a power of two (the generic sweep, never screened).  More than one group of 128
+    chains, not a multiple of 64."""
+    import mcpar_amd as M
+    rng = np.random.default_rng(d * 1000 + n)
+    N = n * nshards
+    shard = nshards - 1
+    ms, _ = realistic_state(rng, N, d, n, stuck_every=7)
+    own = slice(shard * n, (shard + 1) * n)
+    pv = (ms[own, :, 0] + np.sqrt(ms[own, :, 1]) * rng.standard_normal((n, d))).astype(np.float32)
+    pv[::7] = ms[own][::7, :, 0]
+    ro = O.Engine(d, n, nshards=nshards, shard=shard, threads=THREADS).gen_remote(41, pv, ms)
+    eg = M.Engine(d, n, nshards=nshards, shard=shard)
+    rg = eg.gen_remote(41, pv, ms)
+    c = eg.counters
+    eg.close()
+    assert rg[4] == ro[4]
+    for a, b, name in zip(rg[:4], ro[:4], ("ptrial", "cfac", "mutrial", "sigtrial")):
+        assert same_bits(a, b), name
+    assert c["remote_pairs_evaluated"] >= c["remote_pairs"] >= 2 * n * N  # (no screen ran: the min-arg sweep and every pass in full)
+
+
+def broad_state(d=32, n=4096, sigma=0.1, seed=5, wide_first=0.0):
+    """Gaussians as broad as their centres are spread (both 0.1 per coordinate), every chain opposite its own centre: in
+    float64 on the host, 0.996 of the (chain, Gaussian) pairs have an argument below min(176, the chain's own) and 0.997 of
+    the (proposal, Gaussian) pairs one below 176 -- pairs no exact screen may drop, so either screen keeps more than the
+    0.85 at which auto mode gives it up; the reference needs 5 passes at step 41.
+    wide_first: Gaussian 0 gets this sigma instead.  At 100 it is 1 within 1e-4 at every proposal where the others reach
+    e^-16 at best, max Q_i / sum Q_i rounds to one, and the reference accepts every chain in its first pass (step 41;
+    18 of the steps 41 .. 60); the pairs below the bounds are the same 0.996 and 0.997."""
+    rng = np.random.default_rng(seed)
+    ms = np.empty((n, d, 2), np.float32)
+    ms[:, :, 0] = rng.normal(0.0, sigma, (n, d))
+    ms[:, :, 1] = np.float32(sigma) ** 2
+    pv = (-ms[:, :, 0]).astype(np.float32)
+    if wide_first:
+        ms[0, :, 1] = np.float32(wide_first) ** 2
+    return ms, pv
+
+
+GIVE_UP_CALLS = 10
+# mcx_murray.hip: murray_close sets cull_skip[] = 7 after a call whose screens kept more than 0.85 of their pairs, murray_open
+# counts it down through the next seven calls, which go unscreened, and the eighth tries again
+GIVE_UP_SCREENED = (0, 8)
+
+
+def calls_in_a_row(ms, pv):
+    """ten genRemote calls on one engine in auto mode at 4096 chains x 4096 Gaussians x 32-D, the least at which auto
+    mode screens at all: (the reference's passes, per call (same bits as the oracle, pairs, pairs evaluated, launches), the
+    same of one call of an engine that never screens)"""
+    import mcpar_amd as M
+    from mcpar_amd import engine as E
+    n, d = pv.shape
+    ro = O.Engine(d, n, threads=THREADS).gen_remote(41, pv, ms)
+
+    def call(e):
+        before = e.counters
+        rg = e.gen_remote(41, pv, ms)
+        after = e.counters
+        same = rg[4] == ro[4] and all(same_bits(a, b) for a, b in zip(rg[:4], ro[:4]))
+        return (same,) + tuple(after[k] - before[k] for k in ("remote_pairs", "remote_pairs_evaluated", "kernel_launches"))
+
+    eg = M.Engine(d, n)
+    calls = [call(eg) for _ in range(GIVE_UP_CALLS)]
+    eg.close()
+    e0 = M.Engine(d, n)
+    e0.set_option(E.OPT_CULL, 0)
+    off = call(e0)
+    e0.close()
+    return ro[4], calls, off
+
+
+def check_seven_call_skip(calls, off):
+    assert off[0]
+    for k, (same, pairs, evaluated, launches) in enumerate(calls):
+        assert same, k
+        assert pairs == off[1], k
+        if k in GIVE_UP_SCREENED:  # both screens ran, their kernels among the launches, and kept what made them useless
+            assert 0.85 * pairs < evaluated <= off[2] and launches > off[3], k
+        else:                      # neither ran: the call of an engine that never screens
+            assert (evaluated, launches) == off[2:], k
+
+
+def test_auto_mode_gives_a_useless_screen_up_for_seven_calls():
+    """with rejection passes behind the first, the last of them as one kernel turn over candidates"""
+    npass, calls, off = calls_in_a_row(*broad_state())
+    assert npass > 1
+    check_seven_call_skip(calls, off)
+    # (the turn over candidates sweeps four proposals per chain left, remote_pairs counts what the reference would have swept)
+    assert all(evaluated >= pairs for k, (_s, pairs, evaluated, _l) in enumerate(calls) if k not in GIVE_UP_SCREENED)
+
+
+def test_unscreened_calls_evaluate_every_pair():
+    """remote_pairs_evaluated == remote_pairs, exactly, on the calls in which neither sweep kind is screened -- which holds
+    where every kernel turn is one pass of the reference: a turn over candidates (pass_multi) sweeps four proposals per chain
+    and remote_pairs counts those the reference would have come to, so a state with such a turn cannot show it (the state
+    above: 551 chains left after pass 0, 4 x 551 rows swept for 629 chain-passes, 42 582 016 evaluated against 36 130 816
+    pairs).  Here the reference is through in one pass: 2 x 4096 x 4096 pairs, the min-arg sweep's and pass 0's."""
+    ms, pv = broad_state(wide_first=100.0)
+    npass, calls, off = calls_in_a_row(ms, pv)
+    assert npass == 1
+    check_seven_call_skip(calls, off)
+    for k, (_same, pairs, evaluated, _launches) in enumerate(calls):
+        if k not in GIVE_UP_SCREENED:
+            assert evaluated == pairs == 2 * 4096 * 4096, k
+
+
 @pytest.mark.parametrize("cfg", ["rosen16", "mix32"])
 def test_whole_murray_job_same_bits_and_most_pairs_excluded(cfg):
     import mcpar_amd as M
