@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MCX_ABI_VERSION 4
+#define MCX_ABI_VERSION 5
 
 typedef enum mcx_status {
   MCX_OK = 0,
@@ -35,7 +35,12 @@ typedef enum mcx_status {
   MCX_ERR_UNSUPPORTED = 4, /* np > 256 */
   MCX_ERR_ALLOC = 5,       /* sample store does not fit (reference: exit(2), src/mcpar.cc:34-40) */
   MCX_ERR_EXCHANGE = 6,    /* exchange hook failed / missing (reference: MPI_Abort, src/mcpar.cc:133-137) */
-  MCX_ERR_VLFUNC = 7       /* host likelihood callback missing */
+  MCX_ERR_VLFUNC = 7,      /* host likelihood callback missing */
+  /* ABI 5 */
+  MCX_ERR_NONFINITE = 8    /* a Murray step could not end: a NaN among the gathered per-chain moments, or chains still rejected
+                              after MCX_OPT_MURRAY_MAX_PASSES passes (the reference loops for ever, src/mcpar.cc:443).
+                              mcx_last_error names the step and the global chain; the run stops before that step: state,
+                              log L, moments and sample rows are those of the steps before it */
 } mcx_status;
 
 /* ---- likelihood plug-in: replaces class VLFunc (src/vlfunc.hh:9-12) ---------------------- */
@@ -140,7 +145,7 @@ int mcx_gen_local(mcx_engine *e, uint32_t t, const float *pvals, float *ptrial, 
 /* MCPar::genRemote(pvals, musigall, ptrial, cfac)  src/mcpar.hh:41-42, src/mcpar.cc:315-451.
  * musigall[nshards*nc*np*2] interleaved (mu, sig^2).  mutrial/sigtrial[nc*np] are the side
  * outputs the reference keeps in members (sigtrial returned squared, :447-448); npass = number
- * of rejection passes. */
+ * of rejection passes.  MCX_ERR_NONFINITE: see mcx_status. */
 int mcx_gen_remote(mcx_engine *e, uint32_t t, const float *pvals, const float *musigall,
                    float *ptrial, float *cfac, float *mutrial, float *sigtrial, int *npass);
 /* MCPar::covar_setup(incov, cov)  src/mcpar.hh:38, src/mcpar.cc:454-484: cov[np*np] in/out,
@@ -275,6 +280,10 @@ enum {
   MCX_OPT_MURRAY_OVERLAP = 18, /* Murray passes over many chains (np = 16 or 32, the per-pair screen): cut the Gaussians into this
                               many column chunks and screen chunk c + 1 (matrix cores, step stream) while chunk c is swept
                               (vector units, a side stream).  Same bits.  0 / 1: one screen, then one sweep */
+  MCX_OPT_MURRAY_MAX_PASSES = 22, /* a Murray step (genRemote call) gives up with MCX_ERR_NONFINITE when chains are still rejected
+                              after this many rejection passes: a backstop for moments no proposal can come from (sig^2 = +inf
+                              from an overflowed variance, a negative sig^2 handed to mcx_gen_remote), not a tuned value
+                              [default 10 000 000: DESIGN.md section 3; the longest call measured took 3 217]; <= 0: the default */
   MCX_OPT_MEET_UNDER_GATHER = 17 /* small-n mode, sharded runs: may a launch with tuner meetings -- whose workgroups must all
                               be resident at once -- start while this engine's own last gather is still in flight
                               (MCX_OPT_ASYNC_TAIL)?  0: no, the step stream waits for the gather first: no cycle of a

@@ -49,7 +49,8 @@ def lib_path():
 
 
 _lib = None
-ABI_VERSION = 4  # include/mcx.h MCX_ABI_VERSION
+ABI_VERSION = 5  # include/mcx.h MCX_ABI_VERSION
+ERR_NONFINITE = 8  # include/mcx.h MCX_ERR_NONFINITE: McxError.code of a Murray step that could not end
 
 
 def load():

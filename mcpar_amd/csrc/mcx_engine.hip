@@ -387,6 +387,9 @@ extern "C" int mcx_set_option(mcx_engine *e, int opt, int64_t value)
     if (value < 0 || value > 64) return fail(MCX_ERR_INVALID, "MURRAY_OVERLAP: 0 (off) or the number of column chunks, <= 64");
     e->opt_murray_overlap = (int)value;
     break;
+  case MCX_OPT_MURRAY_MAX_PASSES:
+    e->opt_murray_max_passes = value <= 0 ? MURRAY_MAX_PASSES_DEFAULT : (int)std::min<int64_t>(value, MURRAY_MAX_PASSES_DEFAULT);
+    break;
   case MCX_OPT_MEET_UNDER_GATHER: e->opt_meet_under_gather = value < 0 ? -1 : (value ? 1 : 0); break;
   case MCX_OPT_DEBUG_MEET:
     e->opt_debug_meet = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));

@@ -72,6 +72,9 @@ MCXI int need_device();
 // kernel wait for k workgroups more than the grid has, i.e. they can never complete (tests/test_gpu_small_n_safety.py).
 enum { MCX_OPT_DEBUG_MEET = 12 };
 
+// MCX_OPT_MURRAY_MAX_PASSES' default: 3 100 times the longest genRemote call measured, 3 217 passes
+constexpr int MURRAY_MAX_PASSES_DEFAULT = 10000000;
+
 // ---------------------------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------------------------
@@ -319,6 +322,7 @@ struct mcx_engine {
   hipStream_t mstream = nullptr;   // Murray passes by column chunks: the sweeps' stream (mcx_murray.hip: screen_sweep_chunked)
   std::vector<hipEvent_t> mev;
   int opt_murray_overlap = 0;
+  int opt_murray_max_passes = MURRAY_MAX_PASSES_DEFAULT;
   hipStream_t xstream = nullptr;
   hipEvent_t xready = nullptr, xdone = nullptr;
   mcx_output_fn ofn = nullptr;
@@ -459,17 +463,21 @@ constexpr int NACT_CULL_CELLS = 64;
 // 64-bit words: [0] the two survivor counters as its halves (kernel turn `it` counts in half it & 1 and zeroes the other
 // for the next), [1, 65) the min-arg screen's "pairs kept" cells, [65, 129) the sum screens', [129] the word
 // k_remote_decide counts its workgroups in (low half; left zero), [130, 132) tried[TRIED] of a turn over candidates as
-// 32-bit words.  The host mirror has the pass's serial number behind them, in a word of its own.
+// 32-bit words.  The host mirror has the pass's serial number behind them, in a word of its own.  Behind the words on the
+// device, an int k_remote_prep leaves N - g in when global chain g is the first whose (mu, sig2) hold a NaN (0: none); the
+// first kernel turn of a call sends it home with its counters, to the word behind the serial number.
 struct MurrayCounters {
   static constexpr int CELLS = NACT_CULL_CELLS, TRIED = 4;  // TRIED = MULTI_K of mcx_murray.hip, which checks
   static constexpr int W_SURVIVORS = 0, W_KEPT_MIN = 1, W_KEPT_SUMS = W_KEPT_MIN + CELLS, W_DONE = W_KEPT_SUMS + CELLS,
                        W_TRIED = W_DONE + 1, WORDS = W_TRIED + TRIED / 2;
   static constexpr int WORDS_SCREENS = W_DONE;       // what a pass sends home where screens may run: survivors and cells
-  static constexpr int W_SERIAL = WORDS, HOST_WORDS = WORDS + 1;
-  // the device allocation in ints: the words above and four ints nothing uses (the allocation has always had them)
-  static constexpr int DEVICE_INTS = 2 * WORDS + 4;
-  // zeroed at the start of every genRemote call: the screens' cells and the `done` word right behind them
-  static constexpr size_t CALL_ZERO_BYTES = (size_t)(W_TRIED - W_KEPT_MIN) * sizeof(unsigned long long);
+  static constexpr int W_SERIAL = WORDS, W_NONFINITE = WORDS + 1, HOST_WORDS = WORDS + 2;
+  // the device allocation in ints: the words above, the NaN flag and three ints nothing uses (the allocation has always had them)
+  static constexpr int DEVICE_INTS = 2 * WORDS + 4, I_NONFINITE = 2 * WORDS;
+  // zeroed at the start of every genRemote call, in one fill: the screens' cells, the `done` word right behind them, tried[]
+  // (which a turn over candidates zeroes again for itself) and the NaN flag
+  static constexpr size_t CALL_ZERO_BYTES = (size_t)(WORDS - W_KEPT_MIN) * sizeof(unsigned long long) + sizeof(int);
+  static unsigned *nonfinite(int *base) { return reinterpret_cast<unsigned *>(base) + I_NONFINITE; }
   static int *survivors(int *base, int it) { return base + 2 * W_SURVIVORS + (it & 1); }
   static const unsigned long long *words(const int *base) { return reinterpret_cast<const unsigned long long *>(base); }
   static unsigned long long *kept(int *base, bool sums)

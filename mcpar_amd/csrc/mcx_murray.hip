@@ -480,7 +480,8 @@ static int min_arg_sweep(MurrayStep &c)
   mcx_engine *e = c.e;
   const int n = c.n, d = c.d, N = c.N;
   hipStream_t st = c.st;
-  hipLaunchKernelGGL(k_remote_prep, dim3(nblocks((size_t)N * d)), dim3(BLOCK), 0, st, c.musigall, e->winvall.p, (size_t)N * d);
+  hipLaunchKernelGGL(k_remote_prep, dim3(nblocks((size_t)N * d)), dim3(BLOCK), 0, st, c.musigall, e->winvall.p, (size_t)N * d, d, N,
+                     MurrayCounters::nonfinite(e->nact.p));
   if (c.big) {
     hipLaunchKernelGGL(k_remote_cmax_big, dim3(nblocks((size_t)n)), dim3(BLOCK), 0, st, c.pvals, e->winvall.p, e->cmax.p, n, d, N);
     c.evaluated_host += (uint64_t)n * (uint64_t)N;
@@ -517,6 +518,7 @@ static RemoteArgs fill_remote_args(const MurrayStep &c, bool multi)
   a.ncounts = multi ? MurrayCounters::WORDS : (c.cull_can ? MurrayCounters::WORDS_SCREENS : 1);
   a.nflag = MurrayCounters::W_SERIAL;  // (a word of its own whatever ncounts is: serial numbers only ever grow there)
   a.serial = ++e->remote_serial;
+  a.nonfinite = it == 0 ? MurrayCounters::nonfinite(e->nact.p) : nullptr;  // (the call's first turn brings k_remote_prep's flag home)
   a.ncand = MULTI_K;
   a.cand_p = e->cand.p;
   a.cand_mu = a.cand_p + (size_t)MULTI_MAX_CHAINS * MULTI_K * d;
@@ -536,6 +538,8 @@ static int pass_big(MurrayStep &c, RemoteArgs &a)
   e->cnt.kernel_launches += 1;
   c.evaluated_host += (uint64_t)c.nact * (uint64_t)c.N;
   HIPCHK(hipMemcpyAsync(e->h_nact.p, e->nact.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.st));
+  if (a.nonfinite)  // (the low half of a word whose high half is never written)
+    HIPCHK(hipMemcpyAsync(e->h_nact.p + MurrayCounters::W_NONFINITE, a.nonfinite, sizeof(unsigned), hipMemcpyDeviceToHost, c.st));
   HIPCHK(hipStreamSynchronize(c.st));
   return MCX_OK;
 }
@@ -662,7 +666,21 @@ static void note_pass(MurrayStep &c, const PassOutcome &o, uint64_t pairs_now)
   ++c.it;
 }
 
-// the rejection passes (src/mcpar.cc:337-449): kernel turns until no chain is left
+// The call gives up ("Non-finite values"): nothing of it is left in flight, and the run it belongs to
+// stops before this step.  `left` chains were still rejected after `passes` passes; `list`: their list on the device, if any.
+static int murray_gave_up(MurrayStep &c, int left, int passes, const int *list)
+{
+  HIPCHK(hipStreamSynchronize(c.st));
+  int j = -1;
+  if (list && hipMemcpy(&j, list, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) j = -1;
+  if (j >= 0)
+    return fail(MCX_ERR_NONFINITE, "Murray step %u: %d chains still rejected after %d passes (MCX_OPT_MURRAY_MAX_PASSES), global chain %d among them",
+                (unsigned)c.t, left, passes, c.own0 + j);
+  return fail(MCX_ERR_NONFINITE, "Murray step %u: %d chains still rejected after %d passes (MCX_OPT_MURRAY_MAX_PASSES)", (unsigned)c.t, left, passes);
+}
+
+// the rejection passes (src/mcpar.cc:337-449): kernel turns until no chain is left -- or the call gives up: after its first
+// turn when k_remote_prep found a NaN among the moments, and when chains are left after MCX_OPT_MURRAY_MAX_PASSES passes
 static int murray_passes(MurrayStep &c)
 {
   mcx_engine *e = c.e;
@@ -670,7 +688,9 @@ static int murray_passes(MurrayStep &c)
     MCXCHK(e->h_nact.alloc(MurrayCounters::HOST_WORDS));
     memset(e->h_nact.p, 0, MurrayCounters::HOST_WORDS * sizeof(unsigned long long));
   }
+  const int maxp = e->opt_murray_max_passes;
   while (c.nact > 0) {
+    if (c.pass >= maxp) return murray_gave_up(c, c.nact, c.pass, c.ain);
     const bool multi = !c.big && c.pass > 0 && c.nact <= MULTI_MAX_CHAINS;
     RemoteArgs a = fill_remote_args(c, multi);
     if (c.big) {
@@ -678,6 +698,19 @@ static int murray_passes(MurrayStep &c)
     } else {
       MCXCHK(multi ? pass_multi(c, a) : pass_plain(c, a));
       MCXCHK(wait_pass_counters(e->h_nact.p + a.nflag, a.serial, c.st));
+    }
+    if (c.it == 0) {
+      const unsigned bad = (unsigned)__atomic_load_n(e->h_nact.p + MurrayCounters::W_NONFINITE, __ATOMIC_RELAXED);
+      if (bad) {
+        HIPCHK(hipStreamSynchronize(c.st));
+        return fail(MCX_ERR_NONFINITE, "Murray step %u: the moments of global chain %d hold a NaN", (unsigned)c.t, c.N - (int)bad);
+      }
+    }
+    // a turn over candidates stands for passes c.pass .. c.pass + MULTI_K - 1: chains that came as far as the candidate of
+    // pass `maxp` were still rejected after maxp passes
+    if (multi && maxp - c.pass < MULTI_K) {
+      const unsigned beyond = MurrayCounters::tried(e->h_nact.p)[maxp - c.pass];
+      if (beyond) return murray_gave_up(c, (int)beyond, maxp, nullptr);
     }
     const uint64_t pairs_now = (uint64_t)c.nact * (uint64_t)c.N * (multi ? MULTI_K : 1);
     note_pass(c, decode_pass(e->h_nact.p, c.it, multi, c.cull_can, c.nact, c.N), pairs_now);
@@ -768,7 +801,8 @@ static int debug_screen(int nact, int N, const float *x, const float *musig, int
   HIPCHK(hipMemset(b.excl.p, 0, nmask * sizeof(unsigned long long)));
   hipStream_t st = nullptr;
   const ScreenView v = {b.q.p, b.centre.p, b.A.p, b.B.p, b.stats.p, b.hist.p, b.excl.p, b.kept.p};
-  hipLaunchKernelGGL(k_remote_prep, dim3(nblocks((size_t)N * d)), dim3(BLOCK), 0, st, (const float *)b.dms.p, b.q.p, (size_t)N * d);
+  hipLaunchKernelGGL(k_remote_prep, dim3(nblocks((size_t)N * d)), dim3(BLOCK), 0, st, (const float *)b.dms.p, b.q.p, (size_t)N * d, d, N,
+                     (unsigned *)nullptr);
   screen_launch_q<DM>(v, N, d, st);
   screen_launch_x<DM>(v, b.dx.p, nullptr, nact, sums, sums ? -1 : own0, st);
   screen_gemm_go<DM>(v, L, 0, L.nblk, st);

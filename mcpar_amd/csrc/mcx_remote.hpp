@@ -14,12 +14,16 @@ namespace mcx {
 // Gaussian, then xm * xm -- with the division replaced by a multiplication with w (arithmetic v3: sub, mul,
 // fma per pair-dimension; v2's fma(-x, s, mu s) lost the cancellation when |mu| s was large).  One Q_i is 2d
 // contiguous floats.
-static __global__ void k_remote_prep(const float *__restrict__ musigall, float *__restrict__ qpar, size_t nd)
+// A NaN among them would be summed by every chain's sweep -- no chain could ever be taken ("Non-finite
+// values"): *nonfinite (zero before) is left at N - g for the first global chain g that has one, which ends the call.
+static __global__ void k_remote_prep(const float *__restrict__ musigall, float *__restrict__ qpar, size_t nd, int d, int N,
+                                     unsigned *__restrict__ nonfinite)
 {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nd) {
     const float2 ms = reinterpret_cast<const float2 *>(musigall)[i];
     reinterpret_cast<float2 *>(qpar)[i] = make_float2(ms.x, 1.0f / ms.y);
+    if (nonfinite && (ms.x != ms.x || ms.y != ms.y)) atomicMax(nonfinite, (unsigned)N - (unsigned)(i / (size_t)d));
   }
 }
 
@@ -176,6 +180,7 @@ struct RemoteArgs {
   int ncounts;
   int nflag;                  // counts_host[nflag] takes ...
   unsigned long long serial;  // ... the pass's serial number after the counters: what the host polls for
+  const unsigned *nonfinite;  // the call's first turn: k_remote_prep's NaN flag goes to counts_host[nflag + 1] (else null)
   // Several passes at once over few chains (k_remote_draw_multi / k_remote_decide_multi): candidate c of the chain at
   // position i of the active list is the proposal pass + c would draw for it, kept in row i * ncand + c of these
   float *cand_p, *cand_mu, *cand_sig, *cand_racpt;
@@ -684,7 +689,10 @@ __device__ __forceinline__ void decide_hand_over(const RemoteArgs &a)
   if (last) {
     for (int k = (int)threadIdx.x; k < a.ncounts; k += (int)blockDim.x)
       a.counts_host[k] = __hip_atomic_load(a.counts + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0) *a.done = 0u;
+    if (threadIdx.x == 0) {
+      *a.done = 0u;
+      if (a.nonfinite) a.counts_host[a.nflag + 1] = (unsigned long long)__hip_atomic_load(a.nonfinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) {  // the counters are on their way: now the pass's serial number, which the host spins on

@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, Counters, PlanItem, Profile, VLFunc, check, load)
+from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
 VL_DEVICE = 101
@@ -24,6 +25,7 @@ OPT_MURRAY_OVERLAP = 18
 OPT_ASYNC_RUN = 19
 OPT_REFERENCE_CALLS = 20
 OPT_SELF_REPORT = 21
+OPT_MURRAY_MAX_PASSES = 22
 XCHG_BEGIN, XCHG_WAIT = 0, 1
 SUMMARY_NONFINITE = 1  # mcx_col_summary.flags: the column holds an inf or NaN
 # include/mcx.h mcx_col_summary

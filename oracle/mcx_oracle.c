@@ -11,6 +11,7 @@
 #include "mcx_oracle.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -366,9 +367,11 @@ struct mcxo_engine {
   float *samples; size_t nrows, caprows;
   uint8_t *amask;
   uint32_t *acounts;
-  uint64_t nacc_burn, nacc_main, nremote_steps, nremote_passes;
+  uint64_t nacc_burn, nacc_main, nremote_steps, nremote_passes, nremote_passes_max;
   float trace[256]; int ntrace;
   mcxo_exchange_fn xfn; void *xctx;
+  int murray_max_passes; /* mcxo_set_murray_max_passes */
+  char errmsg[160];      /* why the last call returned MCXO_ERR_NONFINITE */
 };
 
 static void *zalloc(size_t n) { return calloc(n ? n : 1, 1); }
@@ -399,6 +402,7 @@ mcxo_engine *mcxo_create(int np, int nc, int nshards, int shard, float pl, float
   e->acounts = zalloc(4 * n);
   for (int i = 0; i < np; ++i) e->cov[i * (np + 1)] = 1.0f; /* identity until covar_setup */
   e->keep_samples = 1; e->keep_mask = 1; e->nthreads = 1; e->sample_stride = 1;
+  e->murray_max_passes = MCXO_MURRAY_MAX_PASSES_DEFAULT;
   return e;
 }
 
@@ -421,6 +425,8 @@ void mcxo_set_threads(mcxo_engine *e, int nthreads)
 }
 void mcxo_set_record(mcxo_engine *e, int ks, int km) { e->keep_samples = ks; e->keep_mask = km; }
 void mcxo_set_sample_stride(mcxo_engine *e, int k) { e->sample_stride = k > 0 ? k : 1; }
+void mcxo_set_murray_max_passes(mcxo_engine *e, int n) { e->murray_max_passes = n > 0 ? n : MCXO_MURRAY_MAX_PASSES_DEFAULT; }
+const char *mcxo_last_error(const mcxo_engine *e) { return e->errmsg; }
 
 /* src/mcpar.cc:454-484 */
 static int covar_setup(mcxo_engine *e, const float *incov)
@@ -612,9 +618,18 @@ int mcxo_gen_remote(mcxo_engine *e, uint32_t t, const float *pvals, const float 
 {
   const int d = e->nparam, n = e->nchain, N = e->tchains, nb = (d + 3) / 4;
   float *qpar = e->winvall; /* (mu, w) pairs, w = 1/sig2 */
+  size_t bad = (size_t)N * d; /* the first (mu, sig2) pair that holds a NaN */
   for (size_t i = 0; i < (size_t)N * d; ++i) {
     qpar[2 * i] = musigall[2 * i];
     qpar[2 * i + 1] = 1.0f / musigall[2 * i + 1];
+    if (bad == (size_t)N * d && (musigall[2 * i] != musigall[2 * i] || musigall[2 * i + 1] != musigall[2 * i + 1])) bad = i;
+  }
+  /* Every chain's sweep sums every Q_i: one NaN moment makes every pacpt NaN and no chain is ever taken.  Not the
+   * reference's behaviour (its loop at :443 then never ends): DESIGN.md section 3, "Non-finite values". */
+  if (bad < (size_t)N * d) {
+    snprintf(e->errmsg, sizeof e->errmsg, "Murray step %u: the moments of global chain %d hold a NaN", (unsigned)t, (int)(bad / (size_t)d));
+    if (npass_out) *npass_out = 0;
+    return MCXO_ERR_NONFINITE;
   }
   const int vec = use_avx2();
   float *qt = NULL;
@@ -674,9 +689,17 @@ int mcxo_gen_remote(mcxo_engine *e, uint32_t t, const float *pvals, const float 
     anyrjct = 0;
     for (int j = 0; j < n; ++j) anyrjct += e->rjct[j];
     ++pass;
-  } while (anyrjct); /* :443 */
+  } while (anyrjct && pass < e->murray_max_passes); /* :443, and the backstop */
 #undef SWEEP
   free(qt);
+  if (anyrjct) {
+    int first = 0;
+    while (!e->rjct[first]) ++first;
+    snprintf(e->errmsg, sizeof e->errmsg, "Murray step %u: %d chains still rejected after %d passes (the first: global chain %u)",
+             (unsigned)t, anyrjct, pass, (unsigned)gchain(e, first));
+    if (npass_out) *npass_out = pass;
+    return MCXO_ERR_NONFINITE;
+  }
   for (size_t i = 0; i < (size_t)n * d; ++i) sigtrial[i] = sigtrial[i] * sigtrial[i]; /* :447-448 */
   if (npass_out) *npass_out = pass;
   return 0;
@@ -728,7 +751,7 @@ static int run_begin(mcxo_engine *e, int nsamp, int nburn, const float *pinit, c
   if (st) return -3;
   e->L = L; e->nsamp = nsamp; e->nburn = nburn;
   e->tun_ntrial = e->tun_naccept = 0; e->irate = 50; e->ntrace = 0;
-  e->nacc_burn = e->nacc_main = 0; e->nremote_steps = e->nremote_passes = 0;
+  e->nacc_burn = e->nacc_main = 0; e->nremote_steps = e->nremote_passes = e->nremote_passes_max = 0;
   memset(e->acounts, 0, 4 * (size_t)e->nchain);
   if (e->keep_samples) ensure_rows(e, (size_t)((nsamp + e->sample_stride - 1) / e->sample_stride) * e->nchain); /* :31 */
   free(e->amask); e->amask = NULL;
@@ -768,7 +791,7 @@ static void burn_end(mcxo_engine *e)
 }
 
 /* one main-loop step without the exchange (src/mcpar.cc:142-209) */
-static void main_step(mcxo_engine *e, int isamp)
+static int main_step(mcxo_engine *e, int isamp)
 {
   const int d = e->nparam, n = e->nchain;
   const uint32_t t = e->tbase + (uint32_t)e->nburn + (uint32_t)isamp;
@@ -786,9 +809,11 @@ static void main_step(mcxo_engine *e, int isamp)
     remotep = 0;
   } else {
     int npass = 0;
-    mcxo_gen_remote(e, t, e->pvals, e->musigall, e->ptrial, e->cfac, e->mutrial, e->sigtrial, &npass);
+    int st = mcxo_gen_remote(e, t, e->pvals, e->musigall, e->ptrial, e->cfac, e->mutrial, e->sigtrial, &npass);
+    if (st) return st; /* the state is that of the step before */
     remotep = 1;
     e->nremote_steps += 1; e->nremote_passes += (uint64_t)npass;
+    if ((uint64_t)npass > e->nremote_passes_max) e->nremote_passes_max = (uint64_t)npass;
   }
   mcxo_vlfunc_eval(e->L, n, e->ptrial, e->lytrial); /* :160 */
   e->nacc_main += accept_all(e, t, (size_t)e->nburn + (size_t)isamp, remotep);
@@ -822,6 +847,7 @@ static void main_step(mcxo_engine *e, int isamp)
       slot[2 * i + 1] = e->sig[i];
     }
   }
+  return 0;
 }
 
 int mcxo_run(mcxo_engine *e, int nsamp, int nburn, const float *pinit, const mcxo_vlfunc *L,
@@ -837,7 +863,8 @@ int mcxo_run(mcxo_engine *e, int nsamp, int nburn, const float *pinit, const mcx
       st = e->xfn(e->xctx, e->musigall, 2 * (size_t)e->ntot, e->rank, e->size);
       if (st) return st;
     }
-    main_step(e, isamp);
+    st = main_step(e, isamp);
+    if (st) return st;
   }
   e->tbase += (uint32_t)(nburn + nsamp);
   return 0;
@@ -861,7 +888,12 @@ int mcxo_run_all(mcxo_engine **eng, int nshards, int nsamp, int nburn, const flo
         for (int r = 0; r < nshards; ++r)
           if (r != s)
             memcpy(eng[s]->musigall + slot * r, eng[r]->musigall + slot * r, sizeof(float) * slot);
-    for (int s = 0; s < nshards; ++s) main_step(eng[s], isamp);
+    int st = 0; /* every shard sees the same musigall: all fail at the same step, or none */
+    for (int s = 0; s < nshards; ++s) {
+      int ss = main_step(eng[s], isamp);
+      st = st ? st : ss;
+    }
+    if (st) return st;
   }
   for (int s = 0; s < nshards; ++s) eng[s]->tbase += (uint32_t)(nburn + nsamp);
   return 0;
@@ -878,6 +910,7 @@ uint64_t mcxo_naccept_burn(const mcxo_engine *e) { return e->nacc_burn; }
 uint64_t mcxo_naccept_main(const mcxo_engine *e) { return e->nacc_main; }
 uint64_t mcxo_remote_steps(const mcxo_engine *e) { return e->nremote_steps; }
 uint64_t mcxo_remote_passes(const mcxo_engine *e) { return e->nremote_passes; }
+uint64_t mcxo_remote_passes_max(const mcxo_engine *e) { return e->nremote_passes_max; }
 size_t mcxo_nsample_rows(const mcxo_engine *e) { return e->nrows; }
 const float *mcxo_samples(const mcxo_engine *e) { return e->samples; }
 const uint8_t *mcxo_accept_mask(const mcxo_engine *e) { return e->amask; }

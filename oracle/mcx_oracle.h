@@ -89,6 +89,13 @@ void mcxo_set_record(mcxo_engine *e, int keep_samples, int keep_accept_mask);
 /* keep only the rows of main-loop steps with isamp % k == 0 (k = 1: every step, the reference's behaviour);
  * lets a full-size job be compared on a strided sample of its rows without holding all of them */
 void mcxo_set_sample_stride(mcxo_engine *e, int k);
+/* A Murray call (mcxo_gen_remote, or a Murray step of a run) returns MCXO_ERR_NONFINITE instead of looping for ever
+ * ("Non-finite values"): at once when musigall holds a NaN, and when chains are still rejected
+ * after n passes.  The run stops before that step; mcxo_last_error names the step and the chain. */
+#define MCXO_ERR_NONFINITE 8
+#define MCXO_MURRAY_MAX_PASSES_DEFAULT 10000000 /* the longest call measured took 3 217 */
+void mcxo_set_murray_max_passes(mcxo_engine *e, int n); /* n <= 0: the default */
+const char *mcxo_last_error(const mcxo_engine *e);
 
 /* mirrors MCPar::run (src/mcpar.hh:36-37).  pinit[nc*np]; incov[np*np] or NULL */
 int mcxo_run(mcxo_engine *e, int nsamp, int nburn, const float *pinit, const mcxo_vlfunc *L,
@@ -109,6 +116,7 @@ uint64_t mcxo_naccept_burn(const mcxo_engine *e);
 uint64_t mcxo_naccept_main(const mcxo_engine *e);
 uint64_t mcxo_remote_steps(const mcxo_engine *e);
 uint64_t mcxo_remote_passes(const mcxo_engine *e);
+uint64_t mcxo_remote_passes_max(const mcxo_engine *e); /* the most passes one Murray step of the last run took */
 size_t mcxo_nsample_rows(const mcxo_engine *e);
 const float *mcxo_samples(const mcxo_engine *e);   /* rows of (np+1): step-major, chain, cols */
 const uint8_t *mcxo_accept_mask(const mcxo_engine *e); /* [(nburn+nsamp)][nc] of last run */

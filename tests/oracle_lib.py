@@ -14,6 +14,15 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
 VL_ROSENBROCK2_FIXED = 6
 
+ERR_NONFINITE = 8   # oracle/mcx_oracle.h MCXO_ERR_NONFINITE: a Murray call that could not end
+
+
+class OracleError(RuntimeError):
+    def __init__(self, status, message):
+        RuntimeError.__init__(self, "oracle status %d: %s" % (status, message))
+        self.status = status
+
+
 HOSTFN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
 XFN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.c_int)
 
@@ -65,6 +74,9 @@ def lib():
     L.mcxo_set_scalar_sweep.argtypes = [C.c_int]
     L.mcxo_set_record.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.mcxo_set_sample_stride.argtypes = [C.c_void_p, C.c_int]
+    L.mcxo_set_murray_max_passes.argtypes = [C.c_void_p, C.c_int]
+    L.mcxo_last_error.restype = C.c_char_p
+    L.mcxo_last_error.argtypes = [C.c_void_p]
     L.mcxo_run.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, C.POINTER(VLFunc), fp]
     L.mcxo_run_all.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(fp),
                                C.POINTER(VLFunc), fp]
@@ -76,7 +88,7 @@ def lib():
     L.mcxo_accept_counts.argtypes = [C.c_void_p]
     L.mcxo_accept_mask.restype = C.POINTER(C.c_uint8)
     L.mcxo_accept_mask.argtypes = [C.c_void_p]
-    for name in ("naccept_burn", "naccept_main", "remote_steps", "remote_passes"):
+    for name in ("naccept_burn", "naccept_main", "remote_steps", "remote_passes", "remote_passes_max"):
         f = getattr(L, "mcxo_" + name)
         f.restype = C.c_uint64
         f.argtypes = [C.c_void_p]
@@ -85,6 +97,7 @@ def lib():
     L.mcxo_tuner_trace.argtypes = [C.c_void_p, fp, C.c_int]
     L.mcxo_gen_local.argtypes = [C.c_void_p, C.c_uint32, fp, fp, fp]
     L.mcxo_gen_remote.argtypes = [C.c_void_p, C.c_uint32, fp, fp, fp, fp, fp, fp, C.POINTER(C.c_int)]
+    L.mcxo_gen_remote.restype = C.c_int
     _lib = L
     return L
 
@@ -146,6 +159,13 @@ class Engine:
         lib().mcxo_set_record(self.h, int(samples), int(mask))
         lib().mcxo_set_sample_stride(self.h, int(stride))
 
+    def set_murray_max_passes(self, n):
+        lib().mcxo_set_murray_max_passes(self.h, int(n))
+
+    @property
+    def last_error(self):
+        return lib().mcxo_last_error(self.h).decode()
+
     def set_exchange(self, pyfn):
         def tramp(ctx, musigall, slot, shard, nshards):
             arr = np.ctypeslib.as_array(musigall, shape=(nshards * slot,))
@@ -162,7 +182,7 @@ class Engine:
                             fptr(ic) if ic is not None else None)
         self.nburn, self.nsamp = nburn, nsamp
         if st:
-            raise RuntimeError("oracle run status %d" % st)
+            raise OracleError(st, self.last_error)
 
     def _arr(self, name, shape, dtype=np.float32):
         p = getattr(lib(), "mcxo_" + name)(self.h)
@@ -190,6 +210,8 @@ class Engine:
     def remote_steps(self): return int(lib().mcxo_remote_steps(self.h))
     @property
     def remote_passes(self): return int(lib().mcxo_remote_passes(self.h))
+    @property
+    def remote_passes_max(self): return int(lib().mcxo_remote_passes_max(self.h))
 
     @property
     def samples(self):
@@ -224,8 +246,10 @@ class Engine:
         sg = np.empty_like(pvals)
         cf = np.ones(self.nc, np.float32)
         npass = C.c_int(0)
-        lib().mcxo_gen_remote(self.h, t, fptr(pvals), fptr(ms), fptr(pt), fptr(cf), fptr(mt),
-                              fptr(sg), C.byref(npass))
+        st = lib().mcxo_gen_remote(self.h, t, fptr(pvals), fptr(ms), fptr(pt), fptr(cf), fptr(mt),
+                                   fptr(sg), C.byref(npass))
+        if st:
+            raise OracleError(st, self.last_error)
         return pt, cf, mt, sg, npass.value
 
 
@@ -239,7 +263,7 @@ def run_all(engines, nsamp, nburn, pinits, vl, incov=None):
     for e in engines:
         e.nburn, e.nsamp = nburn, nsamp
     if st:
-        raise RuntimeError("oracle run_all status %d" % st)
+        raise OracleError(st, engines[0].last_error)
 
 
 def default_pinit(d, n, g0=0):

@@ -166,7 +166,7 @@ def test_new_declarations_are_plain_c99(tmp_path):
                    ' cov[4] = 0.0;\n'
                    ' if (mcx_proposal_from_cov(2, cov, 3, 1.0, incov) != MCX_ERR_INVALID) return 4;\n'
                    ' if (mcx_rows_covariance(rows, 1, 1, 2, mean, cov, flags) != MCX_ERR_INVALID) return 6;\n'
-                   ' return mcx_abi_version() == MCX_ABI_VERSION && MCX_ABI_VERSION == 4 ? 0 : 1; }\n')
+                   ' return mcx_abi_version() == MCX_ABI_VERSION && MCX_ABI_VERSION == 5 ? 0 : 1; }\n')
     exe = tmp_path / "cov"
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
                            str(src), "-o", str(exe), "-L", os.path.join(ROOT, "mcpar_amd"), "-lmcx",

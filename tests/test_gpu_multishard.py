@@ -12,8 +12,11 @@ import oracle_lib as O
 pytestmark = pytest.mark.gpu
 
 
-def run_sharded_gpu(d, n, nshards, nburn, nsamp, pl, sync=10, eager=0, mask=1, vlspec=None, opts=None, runs=1, deferred=False):
-    """deferred: the hook does nothing but note the request in BEGIN and moves the data in WAIT -- a gather that is truly
+def run_sharded_gpu(d, n, nshards, nburn, nsamp, pl, sync=10, eager=0, mask=1, vlspec=None, opts=None, runs=1, deferred=False,
+                    pinits=None, errors=None):
+    """pinits: every shard's start (default: O.default_pinit); errors: a list that takes (shard, exception) of the shards whose
+    run raised, instead of the assertion that none did.
+    deferred: the hook does nothing but note the request in BEGIN and moves the data in WAIT -- a gather that is truly
     in flight between the two: an engine that rewrites its slot, or reads the peers', before its WAIT gets wrong bits"""
     import mcpar_amd as M
     from mcpar_amd import engine as E
@@ -53,17 +56,20 @@ def run_sharded_gpu(d, n, nshards, nburn, nsamp, pl, sync=10, eager=0, mask=1, v
                 engs[s].set_option(k, v)
             engs[s].set_exchange(make_hook(s))
             for _ in range(runs):
-                engs[s].run(nsamp, nburn, O.default_pinit(d, n, g0=s * n), vl)
+                engs[s].run(nsamp, nburn, O.default_pinit(d, n, g0=s * n) if pinits is None else pinits[s], vl)
             if deferred:  # a gather left in flight moves its data in WAIT: every shard's thread must get there together
                 engs[s].synchronize()
         except Exception as ex:  # pragma: no cover
-            errs.append(ex)
+            errs.append((s, ex) if errors is not None else ex)
             bar.abort()
 
     th = [threading.Thread(target=work, args=(s,)) for s in range(nshards)]
     [t.start() for t in th]
     [t.join() for t in th]
-    assert not errs, errs
+    if errors is not None:
+        errors.extend(errs)
+    else:
+        assert not errs, errs
     return engs
 
 
