@@ -383,6 +383,33 @@ int mcx_samples_summary(mcx_engine *e, int first_step, int nsteps, const double 
 int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs,
                      mcx_col_summary *cols, double *quantiles);
 
+/* ---- rank-normalised summaries of the sample store, on the device ----
+ * Vehtari, Gelman, Simpson, Carpenter & Buerkner (2021).  Columns, split chains, R-hat and ESS as above; N = nsteps * nc.
+ *   ranks      r(v) = the 1-based position of v among all N values of the column in ascending order, equal values (-0 and
+ *              +0 are equal) sharing the average of their positions; every step is ranked, the middle step of an odd
+ *              nsteps included
+ *   z(v)       = float(PPND16((r(v) - 0.375) / (N + 0.25))), Wichura's AS 241 in fp64
+ *   q05, median, q95   the type-7 quantiles of the column: mcx_samples_summary's for probs (0.05, 0.5, 0.95), bit for bit
+ *   rhat_bulk, ess_bulk, ess_bulk_lag   rhat, ess, ess_lag of the store of z(x)
+ *   rhat_folded   rhat of the store of z(f), f = float(|x - median|);  rhat = max(rhat_bulk, rhat_folded)
+ *   ess_q05, ess_q95   ess of the stores of the indicators x <= q05, x <= q95 (1.0f / 0.0f);  ess_tail = their min
+ * A max or min over a NaN is NaN.  A column holding an inf or NaN has MCX_SUMMARY_NONFINITE and NaN in every double,
+ * thresholds included; a transformed column that is constant within every half-chain gives NaN for what is built on it. */
+typedef struct mcx_col_rank_summary {
+  double rhat, rhat_bulk, rhat_folded;
+  double ess_bulk, ess_tail, ess_q05, ess_q95;
+  double q05, median, q95;      /* the thresholds used */
+  int ess_bulk_lag, flags;      /* MCX_SUMMARY_* */
+} mcx_col_rank_summary;
+/* Steps [first_step, first_step + nsteps) of the store, nsteps >= 4, cols[np + 1].  MCX_ERR_INVALID in the cases
+ * mcx_samples_summary refuses; MCX_ERR_ALLOC, with the bytes needed in mcx_last_error, when the scratch (4 N (np + 1) bytes
+ * of transformed store and 8 N bytes of keys per column sorted at a time) does not fit even one column at a time;
+ * MCX_ERR_UNSUPPORTED for N >= 2^31.  Works on the engine's stream after a queued MCX_OPT_ASYNC_RUN run is finished; the
+ * same store and arguments give the same bytes. */
+int mcx_samples_rank_summary(mcx_engine *e, int first_step, int nsteps, mcx_col_rank_summary *cols);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows) */
+int mcx_rows_rank_summary(const float *rows, int nsteps, int nc, int np, mcx_col_rank_summary *cols);
+
 /* ---- covariance of the sample store, on the device -----------------
  * Columns as above (the np parameters, then log L), N = nsteps * nc rows, nsteps >= 1 and N >= 2.
  *   mean[c]    = column sum / N: the number mcx_samples_summary reports, bit for bit
@@ -516,6 +543,17 @@ int mcx_debug_rows_acov(const float *rows, int nsteps, int nc, int np, int nlags
 /* mcx_samples_covariance with HIP events around its device passes, for tools/covariance_bench.py: ms[0] the column-sum
  * sweep (k_sum_moments, the pass mcx_samples_summary shares), ms[1] the covariance sweep, ms[2] the reducer of its partials */
 int mcx_debug_covariance_times(mcx_engine *e, int first_step, int nsteps, double *ms);
+/* tests only: one transformed store of mcx_rows_rank_summary back on the host, in MCout layout (out_rows[nsteps * nc * (np + 1)]).
+ * what = 0: z(x), 1: z(f), 2: the indicator x <= q05, 3: x <= q95.  ranks (may be NULL; only for what 0 / 1) receives the
+ * average ranks as doubles, in the same layout. */
+int mcx_debug_rows_rank_transform(const float *rows, int nsteps, int nc, int np, int what, double *ranks, float *out_rows);
+/* host only, no device: z[i] = PPND16(p[i]), the normal quantile function the device uses (NaN outside (0, 1)) */
+int mcx_debug_normal_quantile(const double *p, int n, double *z);
+/* mcx_samples_rank_summary with HIP events around its stages, for tools/rank_summary_bench.py.  ms[20]: for s = 0 (values)
+ * and 1 (folded): ms[7 s] key extraction, ms[7 s + 1 .. 7 s + 4] the sort passes, ms[7 s + 5] rank look-up and transform,
+ * ms[7 s + 6] the summary passes of the transformed store; ms[14], ms[15] the q05 indicator and its summary passes, ms[16],
+ * ms[17] the same for q95; ms[18] the thresholds (the order-statistics passes); ms[19] the whole call */
+int mcx_debug_rank_summary_times(mcx_engine *e, int first_step, int nsteps, double *ms);
 /* normals of stream `stream`, counter (t, g0+i, a, q) for i < n: out[n*4] */
 int mcx_debug_normals(uint32_t seed, uint32_t stream, uint32_t t, uint32_t g0, uint32_t a,
                       uint32_t q, int n, float *out);

@@ -103,6 +103,11 @@ def load():
         "mcx_rows_covariance": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int)],
         "mcx_proposal_from_cov": [C.c_int, dp, C.c_int, C.c_double, fp],
         "mcx_debug_covariance_times": [vp, C.c_int, C.c_int, dp],
+        "mcx_samples_rank_summary": [vp, C.c_int, C.c_int, vp],
+        "mcx_rows_rank_summary": [fp, C.c_int, C.c_int, C.c_int, vp],
+        "mcx_debug_rows_rank_transform": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, fp],
+        "mcx_debug_normal_quantile": [dp, C.c_int, dp],
+        "mcx_debug_rank_summary_times": [vp, C.c_int, C.c_int, dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

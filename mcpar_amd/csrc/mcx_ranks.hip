@@ -1,0 +1,513 @@
+// mcx_ranks.hip -- mcx_samples_rank_summary / mcx_rows_rank_summary: rank-normalised split R-hat, bulk-ESS and tail-ESS of a
+// step range of the sample store on the device (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021).
+//
+// The store is x[step][chain][np] plus ly[step][chain]; N = T * nc values per column.  What is new here is the exact pooled
+// rank of every value (ties averaged) and the stores made of it; R-hat and ESS of those stores are mcx_summary.hip's passes,
+// unchanged (summary_device_parts).  Per transform that needs ranks (the values, and their distance from the median):
+//   1. k_rank_keys       one sweep of the store in mcx_summary.hip's tiles: an order-preserving 32-bit key per value
+//                        (-0 and +0 the same key) into keys[column][N], index = step * nc + chain
+//   2. 4 x { k_rank_hist, k_rank_rowsum, k_rank_scan, k_rank_scatter }
+//                        LSD radix sort of every column's keys, 8 bits per pass, the column a grid dimension: digit counts
+//                        of each tile of RTILE keys, their exclusive scan in (digit, tile) order, a stable scatter.
+//                        Every kernel is a launch of its own and none waits for another workgroup: the order between the
+//                        steps of a pass is the stream's.  Counting uses integer LDS atomics only.
+//   3. k_rank_transform  the same sweep as 1: a value's key finds its lower and upper bound lo, hi in its column's sorted
+//                        keys, r = (lo + hi + 1) / 2, z = float(PPND16((r - 3/8) / (N + 1/4))) -> a store-shaped scratch
+// The tail indicators need no ranks (k_rank_transform, what = 2, 3).  No float atomics anywhere; the same store and arguments
+// give the same bytes.
+#include "mcx_summary_kernels.hpp"
+#include "mcx_ppnd16.hpp"
+
+#include <limits>
+
+namespace {
+
+constexpr int RKPT = 32;             // keys per thread of a sort tile
+constexpr int RTILE = SB * RKPT;     // keys per workgroup of a sort pass
+constexpr int RWAVES = SB / 64;      // a wavefront takes RTILE / RWAVES consecutive keys of the tile
+constexpr int64_t RCHUNK = 64;       // steps per workgroup of the key and transform sweeps (more when T > 2^21: grid.y stays below 2^15)
+static_assert(SB == 256, "a sort workgroup has one thread per digit value");
+
+enum { RANK_BULK = 0, RANK_FOLD = 1, RANK_I05 = 2, RANK_I95 = 3 };
+// mcx_debug_rank_summary_times: ms[s * RT_PER + ...] for s = bulk, fold; then the indicators, the thresholds, the whole call
+enum { RT_KEYS = 0, RT_PASS0 = 1, RT_TRANSFORM = 5, RT_SUMMARY = 6, RT_PER = 7, RT_I05 = 14, RT_I05_SUMMARY = 15, RT_I95 = 16,
+       RT_I95_SUMMARY = 17, RT_THRESHOLDS = 18, RT_TOTAL = 19, RT_N = 20 };
+
+// mcx_summary.hip's key with -0 canonicalised to +0: equal floats have equal keys, every NaN sorts last
+__device__ __forceinline__ uint32_t rkey(float v)
+{
+  uint32_t u = __float_as_uint(v);
+  if (v != v) return 0xffffffffu;
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// what is ranked: the value, or (RANK_FOLD) its distance from the column's median, rounded to float
+__device__ __forceinline__ float ranked_value(float v, int what, double med)
+{
+  return what == RANK_FOLD ? (float)fabs((double)v - med) : v;
+}
+
+// the lanes of this wavefront that are valid and hold the same 8-bit digit as this lane
+__device__ __forceinline__ unsigned long long match8(uint32_t d, bool valid)
+{
+  unsigned long long m = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const unsigned long long bm = __ballot(bit);
+    m &= bit ? bm : ~bm;
+  }
+  return m;
+}
+
+// 1. keys of columns [c0, c1) of a tile set.  grid = (nbc * ntiles, step chunks); thr[3][ncol] = q05, median, q95
+__global__ void __launch_bounds__(SB) k_rank_keys(TileSet t, int nc, int64_t T, int what, const double *thr, int ncol, int c0,
+                                                  int c1, uint32_t *keys, int64_t N, int64_t rchunk)
+{
+  const int tile = blockIdx.x % t.ntiles, bc = blockIdx.x / t.ntiles;
+  const Lane l = lane_of(t, tile, bc, nc);
+  const int col = t.col0 + l.lcol;
+  if (!l.ok || col < c0 || col >= c1) return;
+  const double med = thr[ncol + col];
+  const float *p = t.src + (size_t)l.chain * t.cs + l.lcol;
+  uint32_t *k = keys + (size_t)(col - c0) * (size_t)N + l.chain;
+  const int64_t s0 = (int64_t)blockIdx.y * rchunk, s1 = min(T, s0 + rchunk);
+  for (int64_t s = s0; s < s1; ++s) k[s * nc] = rkey(ranked_value(p[s * t.rs], what, med));
+}
+
+// 2a. digit counts of one tile.  grid = (tiles, columns); hist[(column * 256 + digit) * nblk + tile]
+__global__ void __launch_bounds__(SB) k_rank_hist(const uint32_t *keys, int64_t N, int shift, uint32_t nblk, uint32_t *hist)
+{
+  __shared__ uint32_t cnt[256];
+  cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t *k = keys + (size_t)blockIdx.y * (size_t)N;
+  const int64_t base = (int64_t)blockIdx.x * RTILE;
+  const int lane = threadIdx.x & 63;
+  for (int j = 0; j < RKPT; ++j) {
+    const int64_t i = base + (int64_t)j * SB + threadIdx.x;
+    const bool valid = i < N;
+    const uint32_t d = valid ? (k[i] >> shift) & 255u : 0u;
+    const unsigned long long peers = match8(d, valid);
+    // one add per digit and wavefront: most keys of a pass share their digit
+    if (valid && lane == __ffsll((long long)peers) - 1) atomicAdd(&cnt[d], (uint32_t)__popcll(peers));
+  }
+  __syncthreads();
+  hist[((size_t)blockIdx.y * 256 + threadIdx.x) * nblk + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// 2b. the keys of one (column, digit) over all tiles.  grid = (256, columns)
+__global__ void __launch_bounds__(SB) k_rank_rowsum(const uint32_t *hist, uint32_t nblk, uint32_t *rowsum)
+{
+  __shared__ uint32_t red[SB];
+  const size_t r = (size_t)blockIdx.y * 256 + blockIdx.x;
+  const uint32_t *row = hist + r * nblk;
+  uint32_t s = 0;
+  for (uint32_t i = threadIdx.x; i < nblk; i += SB) s += row[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = SB / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) rowsum[r] = red[0];
+}
+
+// 2c. hist -> where each tile's keys of each digit start in the column: the exclusive scan in (digit, tile) order.
+// grid = (256, columns): workgroup (digit, column) starts at the count of the smaller digits and scans its own row
+__global__ void __launch_bounds__(SB) k_rank_scan(uint32_t *hist, uint32_t nblk, const uint32_t *rowsum)
+{
+  __shared__ uint32_t sh[SB];
+  const int tid = threadIdx.x;
+  sh[tid] = tid < (int)blockIdx.x ? rowsum[(size_t)blockIdx.y * 256 + tid] : 0u;
+  __syncthreads();
+  for (int w = SB / 2; w > 0; w >>= 1) {
+    if (tid < w) sh[tid] += sh[tid + w];
+    __syncthreads();
+  }
+  uint32_t carry = sh[0];
+  __syncthreads();
+  uint32_t *row = hist + ((size_t)blockIdx.y * 256 + blockIdx.x) * nblk;
+  for (uint32_t b0 = 0; b0 < nblk; b0 += SB) {
+    const uint32_t i = b0 + tid;
+    const uint32_t v = i < nblk ? row[i] : 0u;
+    sh[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < SB; off <<= 1) {
+      const uint32_t a = tid >= off ? sh[tid - off] : 0u;
+      __syncthreads();
+      sh[tid] += a;
+      __syncthreads();
+    }
+    if (i < nblk) row[i] = carry + sh[tid] - v;
+    carry += sh[SB - 1];
+    __syncthreads();
+  }
+}
+
+// 2d. the stable scatter of one tile.  grid = (tiles, columns).  Wavefront w holds keys [w, w + 1) * RTILE / RWAVES of the
+// tile, 64 consecutive keys a round: (wavefront, round, lane) is index order, and so is the order within a digit
+__global__ void __launch_bounds__(SB) k_rank_scatter(const uint32_t *in, uint32_t *out, int64_t N, int shift, uint32_t nblk,
+                                                     const uint32_t *hist)
+{
+  __shared__ uint32_t woff[RWAVES][256];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  in += (size_t)blockIdx.y * (size_t)N;
+  out += (size_t)blockIdx.y * (size_t)N;
+  for (int i = tid; i < RWAVES * 256; i += SB) (&woff[0][0])[i] = 0u;
+  __syncthreads();
+  const int64_t wbase = (int64_t)blockIdx.x * RTILE + (int64_t)w * (RTILE / RWAVES);
+  uint32_t key[RKPT], local[RKPT];  // local: the key's place among its wavefront's keys of the same digit
+#pragma unroll
+  for (int j = 0; j < RKPT; ++j) {
+    const int64_t i = wbase + j * 64 + lane;
+    const bool valid = i < N;
+    key[j] = valid ? in[i] : 0xffffffffu;
+    const uint32_t d = (key[j] >> shift) & 255u;
+    const unsigned long long peers = match8(d, valid);
+    const int leader = valid ? __ffsll((long long)peers) - 1 : lane;
+    uint32_t old = 0u;
+    if (valid && lane == leader) old = atomicAdd(&woff[w][d], (uint32_t)__popcll(peers));
+    old = __shfl(old, leader);
+    local[j] = old + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+  }
+  __syncthreads();
+  {  // thread = digit: where each wavefront's keys of the digit start in the column
+    uint32_t run = hist[((size_t)blockIdx.y * 256 + tid) * nblk + blockIdx.x];
+    for (int v = 0; v < RWAVES; ++v) {
+      const uint32_t c = woff[v][tid];
+      woff[v][tid] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < RKPT; ++j) {
+    const int64_t i = wbase + j * 64 + lane;
+    if (i < N) out[woff[w][(key[j] >> shift) & 255u] + local[j]] = key[j];
+  }
+}
+
+// 3. the transformed store.  what = RANK_BULK / RANK_FOLD: normal scores of the ranks, columns [c0, c1), sorted[column - c0][N];
+// RANK_I05 / RANK_I95: the tail indicators, every column.  dst has the layout of t.src; ranks (may be NULL): [N][ncol]
+__global__ void __launch_bounds__(SB) k_rank_transform(TileSet t, int nc, int64_t T, int what, const double *thr, int ncol,
+                                                       int c0, int c1, const uint32_t *sorted, int64_t N, float *dst,
+                                                       double *ranks, int64_t rchunk)
+{
+  const int tile = blockIdx.x % t.ntiles, bc = blockIdx.x / t.ntiles;
+  const Lane l = lane_of(t, tile, bc, nc);
+  const int col = t.col0 + l.lcol;
+  if (!l.ok || col < c0 || col >= c1) return;
+  const size_t off = (size_t)l.chain * t.cs + l.lcol;
+  const float *p = t.src + off;
+  float *q = dst + off;
+  const int64_t s0 = (int64_t)blockIdx.y * rchunk, s1 = min(T, s0 + rchunk);
+  if (what >= RANK_I05) {
+    const double lim = thr[(what == RANK_I05 ? 0 : 2) * ncol + col];
+    for (int64_t s = s0; s < s1; ++s) q[s * t.rs] = (double)p[s * t.rs] <= lim ? 1.0f : 0.0f;
+    return;
+  }
+  const double med = thr[ncol + col];
+  const uint32_t *sk = sorted + (size_t)(col - c0) * (size_t)N;
+  const double denom = (double)N + 0.25;
+  for (int64_t s = s0; s < s1; ++s) {
+    const uint32_t key = rkey(ranked_value(p[s * t.rs], what, med));
+    int64_t lo = 0, hi = N;  // lo: the first index whose key is not below
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (sk[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    // the end of the tie run, galloping: a run is a chain's rejections, short against N
+    int64_t a = lo, step = 1;
+    while (a + step < N && sk[a + step] == key) {
+      a += step;
+      step <<= 1;
+    }
+    int64_t b = min(a + step, N);  // sk[a] == key; sk[b] > key or b == N
+    while (b - a > 1) {
+      const int64_t mid = (a + b) >> 1;
+      if (sk[mid] == key) a = mid; else b = mid;
+    }
+    hi = a + 1;
+    const double r = (double)(lo + hi + 1) * 0.5;
+    q[s * t.rs] = (float)mcx_ppnd16((r - 0.375) / denom);
+    if (ranks) ranks[((size_t)s * nc + l.chain) * ncol + col] = r;
+  }
+}
+
+struct RankDebug {
+  int what;
+  double *ranks;    // host [N][ncol], or NULL
+  float *out_rows;  // host [N][ncol]
+};
+
+struct StageTimer {
+  hipStream_t st;
+  double *ms;
+  struct Ev { int idx; hipEvent_t a, b; };
+  std::vector<Ev> evs;
+  template <class F> int run(int idx, F f)
+  {
+    if (!ms) return f();
+    Ev e{idx, nullptr, nullptr};
+    HIPCHK(hipEventCreate(&e.a));
+    HIPCHK(hipEventCreate(&e.b));
+    evs.push_back(e);
+    HIPCHK(hipEventRecord(e.a, st));
+    MCXCHK(f());
+    HIPCHK(hipEventRecord(e.b, st));
+    return MCX_OK;
+  }
+  int collect()
+  {
+    if (!ms) return MCX_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < RT_N; ++i) ms[i] = 0.0;
+    for (const Ev &e : evs) {
+      float t = 0.0f;
+      HIPCHK(hipEventElapsedTime(&t, e.a, e.b));
+      ms[e.idx] += (double)t;
+    }
+    return MCX_OK;
+  }
+  ~StageTimer()
+  {
+    for (const Ev &e : evs) {
+      if (e.a) (void)hipEventDestroy(e.a);
+      if (e.b) (void)hipEventDestroy(e.b);
+    }
+  }
+};
+
+// the scratch of one call, released when it is over: the transformed store, the keys (two arrays the sort passes alternate
+// between), the sort's counts, the thresholds
+struct RankScratch {
+  DevBuf<float> xs, lys;
+  DevBuf<uint32_t> ka, kb, hist, rowsum;
+  DevBuf<double> thr, ranks;
+  ~RankScratch()
+  {
+    xs.release(); lys.release(); ka.release(); kb.release(); hist.release(); rowsum.release(); thr.release(); ranks.release();
+  }
+};
+
+inline double nan_max(double a, double b) { return a != a || b != b ? std::numeric_limits<double>::quiet_NaN() : std::max(a, b); }
+inline double nan_min(double a, double b) { return a != a || b != b ? std::numeric_limits<double>::quiet_NaN() : std::min(a, b); }
+
+// the rank-normalised summary of x[T][nc][np], ly[T][nc] (device) on stream st.  dbg: stop behind that transform and copy
+// it out; ms (RT_N doubles): the stages' times
+int rank_device(hipStream_t st, Bufs B, const float *x, const float *ly, int nc, int np, int64_t T, mcx_col_rank_summary *out,
+                const RankDebug *dbg, double *ms)
+{
+  const int ncol = np + 1;
+  const int64_t N = T * (int64_t)nc;
+  if (N >= ((int64_t)1 << 31)) return fail(MCX_ERR_UNSUPPORTED, "rank summary: %lld values per column, fewer than 2^31 are supported", (long long)N);
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  const TileSet tx = tiles_x(x, nc, np), tl = tiles_l(ly, nc, np);
+  const int64_t rchunk = std::max(RCHUNK, (T + 32767) / 32768);
+  const unsigned chunks = (unsigned)((T + rchunk - 1) / rchunk);
+  const uint32_t nblk = (uint32_t)((N + RTILE - 1) / RTILE);
+  StageTimer tm{st, ms, {}};
+  RankScratch S;
+  std::vector<mcx_col_summary> c0s(ncol), cs(ncol);
+  std::vector<double> thr(3 * (size_t)ncol), q(3 * (size_t)ncol);
+
+  MCXCHK(tm.run(RT_TOTAL, [&]() -> int {
+    // ---- thresholds: the existing order-statistics pass, once
+    const double probs[3] = {0.05, 0.5, 0.95};
+    MCXCHK(tm.run(RT_THRESHOLDS, [&]() -> int {
+      return summary_device_parts(st, B.d, B.h, B.u, x, ly, nc, np, T, probs, 3, c0s.data(), q.data(), SUMM_OSTAT);
+    }));
+    for (int c = 0; c < ncol; ++c)
+      for (int k = 0; k < 3; ++k) thr[(size_t)k * ncol + c] = q[(size_t)c * 3 + k];
+    MCXCHK(S.thr.alloc(thr.size()));
+    HIPCHK(hipMemcpyAsync(S.thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, st));
+
+    // ---- scratch: the transformed store, and keys for as many columns at a time as fit
+    MCXCHK(S.xs.alloc((size_t)N * np));
+    MCXCHK(S.lys.alloc((size_t)N));
+    if (dbg && dbg->ranks) MCXCHK(S.ranks.alloc((size_t)N * ncol));
+    int G = ncol;
+    if (const char *cap = std::getenv("MCX_RANK_GROUP_COLS")) G = std::max(1, std::min(ncol, std::atoi(cap)));
+    for (;;) {
+      const bool ok = S.ka.alloc((size_t)G * N) == MCX_OK && S.kb.alloc((size_t)G * N) == MCX_OK &&
+                      S.hist.alloc((size_t)G * 256 * nblk) == MCX_OK && S.rowsum.alloc((size_t)G * 256) == MCX_OK;
+      if (ok) break;
+      if (G == 1)
+        return fail(MCX_ERR_ALLOC, "rank summary: %zu bytes of scratch are needed for one column at a time (DESIGN.md section 11)",
+                    (size_t)N * ncol * 4 + (size_t)N * 8 + ((size_t)nblk + 1) * 1024 + (size_t)ncol * 24);
+      S.ka.release(); S.kb.release(); S.hist.release(); S.rowsum.release();
+      G = (G + 1) / 2;
+    }
+
+    auto transform = [&](int what, int c0, int c1, int slot) -> int {
+      return tm.run(slot, [&]() -> int {
+        for (const TileSet *t : {&tx, &tl}) {
+          if (t->col0 + t->ncs <= c0 || t->col0 >= c1) continue;
+          hipLaunchKernelGGL(k_rank_transform, dim3((unsigned)(t->nbc * t->ntiles), chunks), dim3(SB), 0, st, *t, nc, T, what,
+                             (const double *)S.thr.p, ncol, c0, c1, (const uint32_t *)S.ka.p, N, t == &tx ? S.xs.p : S.lys.p,
+                             dbg && dbg->ranks ? S.ranks.p : (double *)nullptr, rchunk);
+          HIPCHK(hipGetLastError());
+        }
+        return MCX_OK;
+      });
+    };
+    // z of the ranks of the values (RANK_BULK) or of their distances from the median (RANK_FOLD) -> xs, lys
+    auto normal_scores = [&](int what) -> int {
+      const int t0 = what * RT_PER;
+      for (int c0 = 0; c0 < ncol; c0 += G) {
+        const int c1 = std::min(ncol, c0 + G), g = c1 - c0;
+        MCXCHK(tm.run(t0 + RT_KEYS, [&]() -> int {
+          for (const TileSet *t : {&tx, &tl}) {
+            if (t->col0 + t->ncs <= c0 || t->col0 >= c1) continue;
+            hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)(t->nbc * t->ntiles), chunks), dim3(SB), 0, st, *t, nc, T, what,
+                               (const double *)S.thr.p, ncol, c0, c1, S.ka.p, N, rchunk);
+            HIPCHK(hipGetLastError());
+          }
+          return MCX_OK;
+        }));
+        uint32_t *src = S.ka.p, *dst = S.kb.p;
+        for (int pass = 0; pass < 4; ++pass) {
+          MCXCHK(tm.run(t0 + RT_PASS0 + pass, [&]() -> int {
+            const int shift = 8 * pass;
+            hipLaunchKernelGGL(k_rank_hist, dim3(nblk, (unsigned)g), dim3(SB), 0, st, (const uint32_t *)src, N, shift, nblk, S.hist.p);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_rank_rowsum, dim3(256, (unsigned)g), dim3(SB), 0, st, (const uint32_t *)S.hist.p, nblk, S.rowsum.p);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_rank_scan, dim3(256, (unsigned)g), dim3(SB), 0, st, S.hist.p, nblk, (const uint32_t *)S.rowsum.p);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(k_rank_scatter, dim3(nblk, (unsigned)g), dim3(SB), 0, st, (const uint32_t *)src, dst, N, shift, nblk,
+                               (const uint32_t *)S.hist.p);
+            HIPCHK(hipGetLastError());
+            return MCX_OK;
+          }));
+          std::swap(src, dst);
+        }
+        // four passes: the sorted keys are back in ka
+        MCXCHK(transform(what, c0, c1, t0 + RT_TRANSFORM));
+      }
+      return MCX_OK;
+    };
+
+    if (dbg) {
+      if (dbg->what <= RANK_FOLD) MCXCHK(normal_scores(dbg->what));
+      else MCXCHK(transform(dbg->what, 0, ncol, RT_I05));
+      std::vector<float> hx((size_t)N * np), hl((size_t)N);
+      HIPCHK(hipMemcpyAsync(hx.data(), S.xs.p, hx.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(hl.data(), S.lys.p, hl.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+      if (dbg->ranks) HIPCHK(hipMemcpyAsync(dbg->ranks, S.ranks.p, (size_t)N * ncol * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (int64_t r = 0; r < N; ++r) {
+        std::memcpy(dbg->out_rows + (size_t)r * ncol, hx.data() + (size_t)r * np, (size_t)np * sizeof(float));
+        dbg->out_rows[(size_t)r * ncol + np] = hl[(size_t)r];
+      }
+      return MCX_OK;
+    }
+
+    auto summarise = [&](int slot) -> int {
+      return tm.run(slot, [&]() -> int {
+        return summary_device_parts(st, B.d, B.h, B.u, S.xs.p, S.lys.p, nc, np, T, nullptr, 0, cs.data(), nullptr, SUMM_ACOV);
+      });
+    };
+    for (int c = 0; c < ncol; ++c) {
+      mcx_col_rank_summary &o = out[c];
+      o.flags = c0s[c].flags;
+      o.q05 = thr[c];
+      o.median = thr[(size_t)ncol + c];
+      o.q95 = thr[2 * (size_t)ncol + c];
+    }
+    MCXCHK(normal_scores(RANK_BULK));
+    MCXCHK(summarise(RANK_BULK * RT_PER + RT_SUMMARY));
+    for (int c = 0; c < ncol; ++c) {
+      out[c].rhat_bulk = cs[c].rhat;
+      out[c].ess_bulk = cs[c].ess;
+      out[c].ess_bulk_lag = cs[c].ess_lag;
+    }
+    MCXCHK(normal_scores(RANK_FOLD));
+    MCXCHK(summarise(RANK_FOLD * RT_PER + RT_SUMMARY));
+    for (int c = 0; c < ncol; ++c) out[c].rhat_folded = cs[c].rhat;
+    MCXCHK(transform(RANK_I05, 0, ncol, RT_I05));
+    MCXCHK(summarise(RT_I05_SUMMARY));
+    for (int c = 0; c < ncol; ++c) out[c].ess_q05 = cs[c].ess;
+    MCXCHK(transform(RANK_I95, 0, ncol, RT_I95));
+    MCXCHK(summarise(RT_I95_SUMMARY));
+    for (int c = 0; c < ncol; ++c) out[c].ess_q95 = cs[c].ess;
+    for (int c = 0; c < ncol; ++c) {
+      mcx_col_rank_summary &o = out[c];
+      if (o.flags & MCX_SUMMARY_NONFINITE) {
+        o.rhat = o.rhat_bulk = o.rhat_folded = o.ess_bulk = o.ess_tail = o.ess_q05 = o.ess_q95 = o.q05 = o.median = o.q95 = qnan;
+        o.ess_bulk_lag = 0;
+        continue;
+      }
+      o.rhat = nan_max(o.rhat_bulk, o.rhat_folded);
+      o.ess_tail = nan_min(o.ess_q05, o.ess_q95);
+    }
+    return MCX_OK;
+  }));
+  return tm.collect();
+}
+
+int rank_args(int nsteps, const void *cols)
+{
+  if (!cols) return fail(MCX_ERR_INVALID, "cols is NULL");
+  if (nsteps < 4) return fail(MCX_ERR_INVALID, "a summary needs nsteps >= 4 (two half-chains of >= 2 steps), got %d", nsteps);
+  return MCX_OK;
+}
+
+int rank_engine(mcx_engine *e, int first_step, int nsteps, mcx_col_rank_summary *cols, double *ms)
+{
+  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
+  MCXCHK(rank_args(nsteps, cols));
+  MCXCHK(enter(e));
+  if (e->samp_steps == 0)
+    return fail(MCX_ERR_INVALID, "the sample store is empty (no run yet, MCX_OPT_SAMPLES = 0, or a run into a sink)");
+  if (first_step < 0 || (int64_t)first_step + nsteps > e->samp_steps)
+    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
+                (long long)first_step + nsteps, e->samp_steps);
+  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
+  return rank_device(e->stream, Bufs{&e->summ_d, &e->summ_h, &e->summ_u}, e->samp_x.p + (size_t)first_step * nc * np,
+                     e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np, nsteps, cols, nullptr, ms);
+}
+
+}  // namespace
+
+extern "C" int mcx_samples_rank_summary(mcx_engine *e, int first_step, int nsteps, mcx_col_rank_summary *cols)
+{
+  return rank_engine(e, first_step, nsteps, cols, nullptr);
+}
+
+extern "C" int mcx_rows_rank_summary(const float *rows, int nsteps, int nc, int np, mcx_col_rank_summary *cols)
+{
+  MCXCHK(rank_args(nsteps, cols));
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
+    return rank_device(st, B, x, ly, nc, np, nsteps, cols, nullptr, nullptr);
+  });
+}
+
+extern "C" int mcx_debug_rows_rank_transform(const float *rows, int nsteps, int nc, int np, int what, double *ranks,
+                                             float *out_rows)
+{
+  MCXCHK(rank_args(nsteps, out_rows));
+  if (what < RANK_BULK || what > RANK_I95) return fail(MCX_ERR_INVALID, "what = %d: 0 z(x), 1 z(f), 2 I05, 3 I95", what);
+  if (ranks && what > RANK_FOLD) return fail(MCX_ERR_INVALID, "ranks only exist for what = 0 and 1");
+  const RankDebug dbg{what, ranks, out_rows};
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
+    return rank_device(st, B, x, ly, nc, np, nsteps, nullptr, &dbg, nullptr);
+  });
+}
+
+extern "C" int mcx_debug_rank_summary_times(mcx_engine *e, int first_step, int nsteps, double *ms)
+{
+  if (!ms) return fail(MCX_ERR_INVALID, "ms is NULL");
+  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
+  std::vector<mcx_col_rank_summary> cols((size_t)e->nparam + 1);
+  return rank_engine(e, first_step, nsteps, cols.data(), ms);
+}
+
+extern "C" int mcx_debug_normal_quantile(const double *p, int n, double *z)
+{
+  if (n < 0 || (n > 0 && (!p || !z))) return fail(MCX_ERR_INVALID, "bad arguments");
+  for (int i = 0; i < n; ++i) z[i] = mcx_ppnd16(p[i]);
+  return MCX_OK;
+}

@@ -156,10 +156,13 @@ inline float key_float(uint32_t k)
 // the summary of x[T][nc][np], ly[T][nc] (device) on stream st.  force_lags > 0 (mcx_debug_rows_acov): every finite
 // column takes windows until it holds force_lags lags instead of stopping where its Geyer loop does; the raw lag sums go to
 // acov_out[ncol][force_lags] and the centred sums of squares to sumsq_out[ncol] (NaN for a column that is not finite),
-// and cols / quantiles are not computed.
+// and cols / quantiles are not computed.  parts (SUMM_*) leaves out what a pass of mcx_samples_rank_summary does not need:
+// without SUMM_OSTAT no order statistics (min, max and quantiles are not valid), without SUMM_ACOV no autocovariance
+// windows (rhat, ess, ess_lag and mcse_mean are not valid); flags, mean and sd always are.
 static int summary_device(hipStream_t st, Bufs B, const float *x, const float *ly, int nc, int np, int64_t T,
                           const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles, int *nwin_out,
-                          int force_lags = 0, double *acov_out = nullptr, double *sumsq_out = nullptr)
+                          int force_lags = 0, double *acov_out = nullptr, double *sumsq_out = nullptr,
+                          int parts = SUMM_OSTAT | SUMM_ACOV)
 {
   const int ncol = np + 1;
   const int64_t n = T / 2, M = 2 * (int64_t)nc, N = T * (int64_t)nc;
@@ -207,7 +210,7 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
   std::vector<uint32_t> gp;
   std::vector<int> gc(ncol);
   std::vector<unsigned long long> hh;
-  for (int pass = 0; pass < 4; ++pass) {
+  for (int pass = 0; pass < ((parts & SUMM_OSTAT) ? 4 : 0); ++pass) {
     const int shift = 32 - 8 * pass;
     // the distinct prefixes of each column's targets, sorted
     int G = 1;
@@ -264,7 +267,7 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
   std::vector<int> active(ncol), need(ncol, 0);
   std::vector<std::vector<double>> acov(ncol);  // sums over half-chains and steps of c_i c_{i+t}
   std::vector<double> ss(ncol, 0.0);
-  for (int c = 0; c < ncol; ++c) active[c] = std::isfinite(cs[c]) ? 1 : 0;
+  for (int c = 0; c < ncol; ++c) active[c] = (parts & SUMM_ACOV) && std::isfinite(cs[c]) ? 1 : 0;
   const int nwin_max = (int)((n + WLAG - 1) / WLAG);
   int k0 = 0, KW = 2, nwin = 0;
   std::vector<float> os(nt);
@@ -337,9 +340,16 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
     MCXCHK(mcx_debug_summary_finish((int)n, (int)M, mean, va, vm, a.data(), (int)a.size(), os.data(), N, probs, nprobs,
                                     fin ? 0 : MCX_SUMMARY_NONFINITE, &cols[c], quantiles ? quantiles + (size_t)c * nprobs : nullptr,
                                     &more));
-    if (more) return fail(MCX_ERR_INVALID, "internal: column %d still wants %d lags", c, more);
+    if (more && (parts & SUMM_ACOV)) return fail(MCX_ERR_INVALID, "internal: column %d still wants %d lags", c, more);
   }
   return MCX_OK;
+}
+
+int summary_device_parts(hipStream_t st, DevBuf<double> *d, DevBuf<unsigned long long> *h, DevBuf<uint32_t> *u, const float *x,
+                         const float *ly, int nc, int np, int64_t T, const double *probs, int nprobs, mcx_col_summary *cols,
+                         double *quantiles, int parts)
+{
+  return summary_device(st, Bufs{d, h, u}, x, ly, nc, np, T, probs, nprobs, cols, quantiles, nullptr, 0, nullptr, nullptr, parts);
 }
 
 static int summary_args(int nsteps, const double *probs, int nprobs, const mcx_col_summary *cols, const double *quantiles)

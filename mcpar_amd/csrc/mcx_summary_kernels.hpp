@@ -1,9 +1,15 @@
-// mcx_summary_kernels.hpp -- what mcx_summary.hip and mcx_covariance.hip both need: the column tiles of the sample store,
+// mcx_summary_kernels.hpp -- what mcx_summary.hip, mcx_covariance.hip and mcx_ranks.hip need: the column tiles of the sample store,
 // pass 1 of every summary (k_sum_moments: per-series fp64 sums), the fixed-order reducer k_sum_rows that every cross-chain
-// or cross-workgroup sum goes through, and the upload of host rows to a scratch store (on_rows).  Internal to those two
+// or cross-workgroup sum goes through, and the upload of host rows to a scratch store (on_rows).  Internal to those three
 // translation units (each gets its own copy of the kernels); nothing here is part of the library's interface.
 #pragma once
 #include "mcx_engine_internal.hpp"
+
+// mcx_summary.hip's device passes for mcx_ranks.hip: summary_device with the parts (SUMM_*) a pass needs
+enum { SUMM_OSTAT = 1, SUMM_ACOV = 2 };
+MCXI int summary_device_parts(hipStream_t st, DevBuf<double> *d, DevBuf<unsigned long long> *h, DevBuf<uint32_t> *u,
+                              const float *x, const float *ly, int nc, int np, int64_t T, const double *probs, int nprobs,
+                              mcx_col_summary *cols, double *quantiles, int parts);
 
 namespace {
 

@@ -2,7 +2,8 @@
 // only through its library API: SURVEY fact 3).
 //   mcpar-run [--func rosen1|rosen2|rosen2fixed|gauss|dgauss|mix | --func-source FILE.hip [--par a,b,...]] [--np D]
 //             [--nc CHAINS] [--nsamp N] [--nburn B] [--pl P] [--sync S] [--ncomp K] [--quiet] [--iter] [--binary]
-//             [--stream-text] [--out FILE] [--summary FILE] [--covariance FILE] [--proposal FILE] [--incov FILE]
+//             [--stream-text] [--out FILE] [--summary FILE] [--rank-summary FILE] [--covariance FILE] [--proposal FILE]
+//             [--incov FILE]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -10,6 +11,9 @@
 // text goes to FILE, every rank writing its own share at its place (MCout::text_file) instead of through rank 0.
 // --summary FILE: one row per column (p0 .. p{np-1}, then LL) of the kept rows' summary on the GPU (mcx_rows_summary):
 // name mean sd q01 q50 q99 rhat ess mcse.  Needs the rows on the host: not with --stream-text, and one rank only.
+// --rank-summary FILE: the rank-normalised diagnostics of the same rows (mcx_rows_rank_summary), one row per column: name
+// rhat rhat_bulk rhat_folded ess_bulk ess_tail ess_q05 ess_q95 q05 q50 q95 ess_bulk_lag flags.  Under the conditions of
+// --summary.
 // --covariance FILE: mean and covariance matrix of the kept rows on the GPU (mcx_rows_covariance): header `name mean p0 ..
 // LL`, then one row per column: name, mean, the matrix row.  --proposal FILE: np rows of np numbers, that matrix's
 // parameter block as the proposal covariance of a next run (mcx_proposal_from_cov, scale 2.38^2 / np).  Both under the
@@ -57,6 +61,33 @@ static int write_summary(const char *path, MCout &rows, int nsamp, int nc, int n
     std::string name = c < np ? "p" + std::to_string(c) : "LL";
     fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", name.c_str(), s.mean, s.sd, qc[0], qc[1], qc[2],
             s.rhat, s.ess, s.mcse_mean);
+  }
+  return fclose(f) == 0 ? 0 : 1;
+}
+
+// --rank-summary: the rank-normalised R-hat, bulk-ESS and tail-ESS of MCout's rows, one row per column
+static int write_rank_summary(const char *path, MCout &rows, int nsamp, int nc, int np)
+{
+  std::vector<mcx_col_rank_summary> cols((size_t)np + 1);
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 4) {
+    std::cerr << "--rank-summary: " << rows.size() << " rows stored, a summary needs nsamp * nc of them and nsamp >= 4\n";
+    return 1;
+  }
+  if (mcx_rows_rank_summary(rows.getpset(0), nsamp, nc, np, cols.data()) != MCX_OK) {
+    std::cerr << "--rank-summary: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "name rhat rhat_bulk rhat_folded ess_bulk ess_tail ess_q05 ess_q95 q05 q50 q95 ess_bulk_lag flags\n");
+  for (int c = 0; c <= np; ++c) {
+    const mcx_col_rank_summary &s = cols[c];
+    std::string name = c < np ? "p" + std::to_string(c) : "LL";
+    fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %d\n", name.c_str(), s.rhat, s.rhat_bulk,
+            s.rhat_folded, s.ess_bulk, s.ess_tail, s.ess_q05, s.ess_q95, s.q05, s.median, s.q95, s.ess_bulk_lag, s.flags);
   }
   return fclose(f) == 0 ? 0 : 1;
 }
@@ -142,7 +173,7 @@ int main(int argc, char *argv[])
   int np = 16, nc = 4096, nsamp = 100, nburn = 500, sync = 10, ncomp = 8;
   float pl = 1.0f;
   bool quiet = false, iter = false, binary = false, stream_text = false;
-  std::string out_file, func_source, summary_file, covariance_file, proposal_file, incov_file;
+  std::string out_file, func_source, summary_file, rank_summary_file, covariance_file, proposal_file, incov_file;
   std::vector<float> user_par;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -166,6 +197,7 @@ int main(int argc, char *argv[])
     else if (a == "--stream-text") stream_text = true;  // the same text, formatted on the GPU, nothing kept on the host
     else if (a == "--out") out_file = val();
     else if (a == "--summary") summary_file = val();
+    else if (a == "--rank-summary") rank_summary_file = val();
     else if (a == "--covariance") covariance_file = val();
     else if (a == "--proposal") proposal_file = val();
     else if (a == "--incov") incov_file = val();
@@ -178,6 +210,13 @@ int main(int argc, char *argv[])
   if (!summary_file.empty() && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--summary needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!rank_summary_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--rank-summary needs the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -269,6 +308,10 @@ int main(int argc, char *argv[])
   }
   rslts.text_file(0);
   if (!summary_file.empty() && write_summary(summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (!rank_summary_file.empty() && write_rank_summary(rank_summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

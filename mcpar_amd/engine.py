@@ -33,6 +33,13 @@ SUMMARY_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("min", np.f
                           ("rhat", np.float64), ("ess", np.float64), ("mcse_mean", np.float64), ("ess_lag", np.int32),
                           ("flags", np.int32)], align=True)
 assert SUMMARY_DTYPE.itemsize == 56
+# include/mcx.h mcx_col_rank_summary
+RANK_SUMMARY_DTYPE = np.dtype([("rhat", np.float64), ("rhat_bulk", np.float64), ("rhat_folded", np.float64),
+                               ("ess_bulk", np.float64), ("ess_tail", np.float64), ("ess_q05", np.float64),
+                               ("ess_q95", np.float64), ("q05", np.float64), ("median", np.float64), ("q95", np.float64),
+                               ("ess_bulk_lag", np.int32), ("flags", np.int32)], align=True)
+assert RANK_SUMMARY_DTYPE.itemsize == 88
+RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 
 
 def _fp(a):
@@ -141,6 +148,41 @@ def rows_summary(rows, nsteps, nc, probs=(0.01, 0.5, 0.99)):
     check(load().mcx_rows_summary(_fp(rows), nsteps, nc, ncol - 1, pp, len(p), cols.ctypes.data_as(C.c_void_p),
                                   q.ctypes.data_as(C.POINTER(C.c_double))))
     return _summary_dict(cols, q)
+
+
+def _rank_summary_dict(cols):
+    return {name: cols[name].copy() for name in RANK_SUMMARY_DTYPE.names}
+
+
+def rows_rank_summary(rows, nsteps, nc):
+    """mcx_rows_rank_summary: Engine.rank_summary's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    cols = np.zeros(ncol, RANK_SUMMARY_DTYPE)
+    check(load().mcx_rows_rank_summary(_fp(rows), nsteps, nc, ncol - 1, cols.ctypes.data_as(C.c_void_p)))
+    return _rank_summary_dict(cols)
+
+
+def debug_rows_rank_transform(rows, nsteps, nc, what, want_ranks=False):
+    """mcx_debug_rows_rank_transform: one transformed store of rows_rank_summary as rows [nsteps * nc, np + 1] (what =
+    RANK_Z, RANK_Z_FOLDED, RANK_I05 or RANK_I95); with want_ranks (RANK_Z / RANK_Z_FOLDED) also the average ranks as
+    float64 in the same layout: (out_rows, ranks)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    out = np.zeros_like(rows)
+    ranks = np.zeros(rows.shape, np.float64) if want_ranks else None
+    check(load().mcx_debug_rows_rank_transform(_fp(rows), nsteps, nc, rows.shape[1] - 1, what,
+                                               None if ranks is None else ranks.ctypes.data_as(C.POINTER(C.c_double)),
+                                               _fp(out)))
+    return (out, ranks) if want_ranks else out
+
+
+def debug_normal_quantile(p):
+    """mcx_debug_normal_quantile (host only): PPND16 of every p, float64"""
+    p = np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1))
+    z = np.zeros_like(p)
+    check(load().mcx_debug_normal_quantile(p.ctypes.data_as(C.POINTER(C.c_double)), p.size,
+                                           z.ctypes.data_as(C.POINTER(C.c_double))))
+    return z
 
 
 def debug_rows_acov(rows, nsteps, nc, nlags):
@@ -547,6 +589,28 @@ class Engine:
         check(load().mcx_samples_summary(self.h, first_step, nsteps, pp, len(p), cols.ctypes.data_as(C.c_void_p),
                                          q.ctypes.data_as(C.POINTER(C.c_double))))
         return _summary_dict(cols, q)
+
+    def rank_summary(self, first_step=0, nsteps=None):
+        """mcx_samples_rank_summary: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps)
+        -- a dict of arrays [np + 1]: rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, q05, median, q95,
+        ess_bulk_lag, flags"""
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        cols = np.zeros(self.np + 1, RANK_SUMMARY_DTYPE)
+        check(load().mcx_samples_rank_summary(self.h, first_step, nsteps, cols.ctypes.data_as(C.c_void_p)))
+        return _rank_summary_dict(cols)
+
+    def rank_summary_times(self, first_step=0, nsteps=None):
+        """mcx_debug_rank_summary_times: the 20 stage times of one rank_summary() call in ms (include/mcx.h lists them)"""
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        ms = np.zeros(20)
+        check(load().mcx_debug_rank_summary_times(self.h, first_step, nsteps, _dp(ms)))
+        return ms
 
     def covariance(self, first_step=0, nsteps=None):
         """mcx_samples_covariance of kept steps [first_step, first_step + nsteps): a dict of mean [np + 1] (summary()'s,
