@@ -493,6 +493,18 @@ int mcx_debug_copy_bandwidth(size_t bytes, int reps, double *gbps);
  * wavefronts per workgroup of lpc2 lanes per chain x bpl blocks per lane, and who generates what: tab[3][16][24] item
  * codes (0xffffffff ends a wavefront's list; kind << 14 | step pair << 4 | (owner, block)) */
 int mcx_debug_persist_deal(int lpc2, int bpl, int own, int *rec, int *ksteps, uint32_t *tab, int max_words);
+/* The step-kernel template instances.  An id packs what the launcher's own template arguments say, formed next to the
+ * launch: bits 0-3 family (1 k_fused_fast, 2 k_fused_fastb, 3 k_fused_fast full covariance, 4 k_fused_fastb full
+ * covariance (mirrored), 5 k_fused_fast with pre-generated normals, 6 k_gen_normals, 7 k_fused_steps, 8 k_run_small, 9 a
+ * user's source compiled at run time), bits 4-10 lanes per chain (LPC or LPC2), 11-13 blocks per lane, 14-17 the likelihood
+ * (LikKind; 0 none), 18 MAIN, 19-20 EmitMode (0 where the instance has no such argument), 21 REC.
+ * mcx_debug_step_instances: the distinct instances launched since the last mcx_run began, in order of first launch (*n of
+ * them, the first `cap` in ids).  Kept on the host in a fixed array of the engine: no device call, nothing launched differently.
+ * mcx_debug_step_instance_list: every instance the launchers can launch (no device, like mcx_plan): their own dispatch
+ * code run over lanes 1..64, blocks per lane 1/2/4, every likelihood, both loops, rows or none, stride 1 or 3, one or two
+ * owner wavefronts and either recorder choice, stopping where it would launch. */
+int mcx_debug_step_instances(mcx_engine *e, uint32_t *ids, int cap, int *n);
+int mcx_debug_step_instance_list(uint32_t *ids, int cap, int *n);
 /* host logic of mcx_run in small-n mode, for tests (no device): the stretch of a plan (mcx_plan) that one launch of the
  * one-launch kernel takes when the executor stands at items[index] -- items [index, *end) -- and out5 = its burn-in steps,
  * main-loop steps, 1 if it starts the moments, its first main-loop step, and the step of its main loop after which the

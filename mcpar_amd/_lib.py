@@ -131,6 +131,8 @@ def load():
         "mcx_debug_exchange": [vp],
         "mcx_debug_fill_slot": [vp, C.c_float],
         "mcx_debug_persist_deal": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), u32p, C.c_int],
+        "mcx_debug_step_instances": [vp, u32p, C.c_int, C.POINTER(C.c_int)],
+        "mcx_debug_step_instance_list": [u32p, C.c_int, C.POINTER(C.c_int)],
         "mcx_debug_small_stretch": [C.POINTER(PlanItem), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int)],
         "mcx_debug_copy_bandwidth": [C.c_size_t, C.c_int, C.POINTER(C.c_double)],

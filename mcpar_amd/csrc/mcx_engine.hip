@@ -471,6 +471,67 @@ extern "C" int mcx_debug_persist_deal(int lpc2, int bpl, int own, int *rec, int 
   return MCX_OK;
 }
 
+extern "C" int mcx_debug_step_instances(mcx_engine *e, uint32_t *ids, int cap, int *n)
+{
+  if (!e || !n || cap < 0 || (cap > 0 && !ids)) return fail(MCX_ERR_INVALID, "bad arguments");
+  if (e->steps.lost) return fail(MCX_ERR_UNSUPPORTED, "more than %d distinct step-kernel instances in one run", StepLedger::CAP);
+  *n = e->steps.n;
+  for (int i = 0; i < e->steps.n && i < cap; ++i) ids[i] = e->steps.ids[i];
+  return MCX_OK;
+}
+
+// Every instance the launchers can launch: their own switches, driven over the whole small argument space with a dry
+// ledger (mcx_launch.hpp), which makes each launcher return where it would launch.  No table is kept here: an
+// instantiation added to a launcher shows up by itself.  No device call on the way.
+extern "C" int mcx_debug_step_instance_list(uint32_t *ids, int cap, int *n)
+{
+  if (!n || cap < 0 || (cap > 0 && !ids)) return fail(MCX_ERR_INVALID, "bad arguments");
+  std::vector<uint32_t> all;
+  auto take = [&](StepLedger &l) {
+    for (int i = 0; i < l.n; ++i)
+      if (std::find(all.begin(), all.end(), l.ids[i]) == all.end()) all.push_back(l.ids[i]);
+    l.n = 0;
+  };
+  static float somewhere[4];  // (never dereferenced: the launchers only ask whether rows / a trash row are wanted)
+  StepLedger l;
+  l.dry = true;
+  for (int lpc = 1; lpc <= 64; lpc <<= 1) {
+    for (int lik = 0; lik <= LIK_USER; ++lik)
+      for (int main = 0; main < 2; ++main) {
+        for (int rows = 0; rows < 2; ++rows)
+          for (int stride = 1; stride <= 3; stride += 2) {
+            SegArgs a{};
+            a.n = 1; a.d = 4 * lpc; a.nsteps = 1;
+            a.samp_x = a.samp_ly = rows ? somewhere : nullptr;
+            a.samp_stride = stride;
+            a.trash = somewhere;
+            (void)mcxk_launch_fast(lpc, lik, main != 0, a, nullptr, &l);
+            for (int bpl = 1; bpl <= 4; bpl <<= 1) (void)mcxk_launch_fastb(lpc, bpl, lik, main != 0, a, nullptr, &l);
+            (void)mcxk_launch_fast_full(lpc, lik, main != 0, a, nullptr, &l);
+            (void)mcxk_launch_fastb_full(lpc, lik, main != 0, a, nullptr, &l);
+            (void)mcxk_launch_fast_pregen(lpc, lik, main != 0, a, nullptr, &l);
+            (void)(main ? mcxk_launch_generic_main(lpc, lik, a, nullptr, &l) : mcxk_launch_generic_burn(lpc, lik, a, nullptr, &l));
+            take(l);
+          }
+        for (int bpl = 1; bpl <= 4; bpl <<= 1)
+          for (int own = 1; own <= 2; ++own)
+            for (int rec = -1; rec <= 1; ++rec) {  // the launcher's own rule, and both forced choices (MCX_PERSIST_REC)
+              RunArgs r{};
+              r.n = 1; r.d = 4 * lpc; r.own = own; r.nown = own; r.nburn = main ? 0 : 1; r.nmain = main;
+              l.force_rec = rec;
+              (void)mcxk_launch_persist(lpc, bpl, lik, r, nullptr, &l);
+              take(l);
+            }
+        l.force_rec = -1;
+      }
+    (void)mcxk_launch_gen(lpc, nullptr, nullptr, 1, 4 * lpc, 1, 0, 0, 0, nullptr, &l);
+    take(l);
+  }
+  *n = (int)all.size();
+  for (int i = 0; i < *n && i < cap; ++i) ids[i] = all[i];
+  return MCX_OK;
+}
+
 extern "C" int mcx_device_count(int *n)
 {
   if (!n) return fail(MCX_ERR_INVALID, "n is NULL");

@@ -150,12 +150,12 @@ struct PinBuf {
 // mcx_user.hip: a user's likelihood source compiled into the step kernels at run time (MCX_VL_SOURCE)
 struct UserLik;
 int user_lik_get(const char *source, int np, std::shared_ptr<UserLik> *out);  // compiled once per (source, np)
-int user_lik_launch_fused(const UserLik &u, bool main, const SegArgs &a, hipStream_t st);
+int user_lik_launch_fused(const UserLik &u, bool main, const SegArgs &a, hipStream_t st, StepLedger *led);
 int user_lik_launch_eval(const UserLik &u, const float *x, float *y, int n, int d, const float *par, int ncomp, hipStream_t st);
 int user_lik_variant(int lpc, const SegArgs &a);  // 0 hot-path kernel, 1 its full-covariance form, 2 the generic kernel
 double user_lik_compile_ms(const UserLik &u);
 bool user_lik_small_ok(const UserLik &u);  // block form, <= 8 lanes per chain: the one-launch small-n kernel can be built for it
-hipError_t user_lik_launch_small(UserLik &u, int bpl, const RunArgs &a, hipStream_t st);  // (mcxk_launch_persist's role)
+hipError_t user_lik_launch_small(UserLik &u, int bpl, const RunArgs &a, hipStream_t st, StepLedger *led);  // (mcxk_launch_persist's role)
 
 struct LikDev {
   int kind = 0;  // LikKind, or MCX_VL_HOST / MCX_VL_DEVICE
@@ -354,6 +354,7 @@ struct mcx_engine {
   DevBuf<float> best_row;            // running maximum-likelihood sample: [0] = log-likelihood, [1..np] = parameters
   DevBuf<unsigned long long> best_key;  // scratch of the arg-max reduction
   mcx_counters cnt{};
+  StepLedger steps;                  // the step-kernel instances launched since the last mcx_run began (mcx_launch.hpp)
   DevBuf<unsigned long long> trace_clk;  // MCX_PERSIST_TRACE (debug builds): per-wavefront phase clocks of the last small-n launch
   DevBuf<uint32_t> deal_tab;         // RunArgs::deal of the one-launch small-n kernel, for the configuration in deal_key
   std::vector<uint32_t> h_deal;

@@ -160,8 +160,9 @@ bool mcxk_persist_deal_fits(int lpc2, int bpl, int own, int rec, int K)
 }
 
 template <int LPC2, int BPL, int LIK, bool REC>
-static hipError_t go2(const RunArgs &a, hipStream_t st)
+static hipError_t go2(const RunArgs &a, hipStream_t st, StepLedger *led)
 {
+  if (led && led->dry) MCX_STEP_NOTE(led, SF_PERSIST, LPC2, BPL, LIK, false, EMIT_ANY, REC);  // (before any device call)
   {  // per instantiation and device; the value is the largest the kernel can be launched with
     static std::mutex amu;
     static std::vector<int> adevs;
@@ -206,40 +207,43 @@ static hipError_t go2(const RunArgs &a, hipStream_t st)
     }
     if (resident < (long long)nwg) return hipErrorCooperativeLaunchTooLarge;
   }
+  MCX_STEP_NOTE(led, SF_PERSIST, LPC2, BPL, LIK, false, EMIT_ANY, REC);
   hipLaunchKernelGGL((k_run_small<LPC2, BPL, LIK, REC>), dim3(nwg), dim3(PBLOCK), lds, st, a);
   return hipGetLastError();
 }
 
 template <int LPC2, int BPL, int LIK>
-static hipError_t go(const RunArgs &a, hipStream_t st)
+static hipError_t go(const RunArgs &a, hipStream_t st, StepLedger *led)
 {
-  return mcxk_persist_recorders(a.own, BPL) ? go2<LPC2, BPL, LIK, true>(a, st) : go2<LPC2, BPL, LIK, false>(a, st);
+  // (a dry ledger may force the choice, as the MCX_PERSIST_REC tuning variable can: the list holds both)
+  const bool rec = led && led->dry && led->force_rec >= 0 ? led->force_rec != 0 : mcxk_persist_recorders(a.own, BPL);
+  return rec ? go2<LPC2, BPL, LIK, true>(a, st, led) : go2<LPC2, BPL, LIK, false>(a, st, led);
 }
 
 template <int LPC2, int BPL>
-static hipError_t by_lik(int lik, const RunArgs &a, hipStream_t st)
+static hipError_t by_lik(int lik, const RunArgs &a, hipStream_t st, StepLedger *led)
 {
   switch (lik) {
-  case LIK_ROSEN1: return go<LPC2, BPL, LIK_ROSEN1>(a, st);
-  case LIK_GAUSS: return go<LPC2, BPL, LIK_GAUSS>(a, st);
-  case LIK_MIX: return go<LPC2, BPL, LIK_MIX>(a, st);
+  case LIK_ROSEN1: return go<LPC2, BPL, LIK_ROSEN1>(a, st, led);
+  case LIK_GAUSS: return go<LPC2, BPL, LIK_GAUSS>(a, st, led);
+  case LIK_MIX: return go<LPC2, BPL, LIK_MIX>(a, st, led);
   default: return hipErrorInvalidValue;
   }
 }
 
 // lpc = 4-parameter blocks per chain (a power of two), bpl of them per lane
-hipError_t mcxk_launch_persist(int lpc, int bpl, int lik, const RunArgs &a, hipStream_t st)
+hipError_t mcxk_launch_persist(int lpc, int bpl, int lik, const RunArgs &a, hipStream_t st, StepLedger *led)
 {
   switch (bpl * 16 + lpc / bpl) {
-  case 16 + 1: return by_lik<1, 1>(lik, a, st);
-  case 16 + 2: return by_lik<2, 1>(lik, a, st);
-  case 16 + 4: return by_lik<4, 1>(lik, a, st);
-  case 16 + 8: return by_lik<8, 1>(lik, a, st);
-  case 32 + 1: return by_lik<1, 2>(lik, a, st);
-  case 32 + 2: return by_lik<2, 2>(lik, a, st);
-  case 32 + 4: return by_lik<4, 2>(lik, a, st);
-  case 64 + 1: return by_lik<1, 4>(lik, a, st);
-  case 64 + 2: return by_lik<2, 4>(lik, a, st);
+  case 16 + 1: return by_lik<1, 1>(lik, a, st, led);
+  case 16 + 2: return by_lik<2, 1>(lik, a, st, led);
+  case 16 + 4: return by_lik<4, 1>(lik, a, st, led);
+  case 16 + 8: return by_lik<8, 1>(lik, a, st, led);
+  case 32 + 1: return by_lik<1, 2>(lik, a, st, led);
+  case 32 + 2: return by_lik<2, 2>(lik, a, st, led);
+  case 32 + 4: return by_lik<4, 2>(lik, a, st, led);
+  case 64 + 1: return by_lik<1, 4>(lik, a, st, led);
+  case 64 + 2: return by_lik<2, 4>(lik, a, st, led);
   default: return hipErrorInvalidValue;
   }
 }

@@ -69,13 +69,13 @@ static bool fused_takes_epilogue(const mcx_engine *e, const SegArgs &a)
 
 // The fused-kernel families are compiled in their own translation units (mcx_k_fast.hip,
 // mcx_k_pregen.hip, mcx_k_generic_*.hip) so that the library builds in parallel; see mcx_launch.hpp.
-static int launch_fused_plain(int lpc, int lik, bool main, const SegArgs &a, hipStream_t st, FusedChoice c)
+static int launch_fused_plain(int lpc, int lik, bool main, const SegArgs &a, hipStream_t st, FusedChoice c, StepLedger *led)
 {
   hipError_t err;
   switch (c.kernel) {
-  case FUSED_HOT: err = c.bpl > 1 ? mcxk_launch_fastb(lpc, c.bpl, lik, main, a, st) : mcxk_launch_fast(lpc, lik, main, a, st); break;
-  case FUSED_HOT_FULLCOV: err = c.bpl == 2 ? mcxk_launch_fastb_full(lpc, lik, main, a, st) : mcxk_launch_fast_full(lpc, lik, main, a, st); break;
-  default: err = main ? mcxk_launch_generic_main(lpc, lik, a, st) : mcxk_launch_generic_burn(lpc, lik, a, st);
+  case FUSED_HOT: err = c.bpl > 1 ? mcxk_launch_fastb(lpc, c.bpl, lik, main, a, st, led) : mcxk_launch_fast(lpc, lik, main, a, st, led); break;
+  case FUSED_HOT_FULLCOV: err = c.bpl == 2 ? mcxk_launch_fastb_full(lpc, lik, main, a, st, led) : mcxk_launch_fast_full(lpc, lik, main, a, st, led); break;
+  default: err = main ? mcxk_launch_generic_main(lpc, lik, a, st, led) : mcxk_launch_generic_burn(lpc, lik, a, st, led);
   }
   if (err == hipErrorInvalidValue) return fail(MCX_ERR_UNSUPPORTED, "no fused kernel for lanes/chain = %d, likelihood %d", lpc, lik);
   HIPCHK(err);
@@ -85,16 +85,16 @@ static int launch_fused_plain(int lpc, int lik, bool main, const SegArgs &a, hip
 static int launch_fused(mcx_engine *e, bool main, const SegArgs &a, hipStream_t st)
 {
   const int lik = e->lik.kind, lpc = e->lpc;
-  if (lik == LIK_USER) return user_lik_launch_fused(*e->lik.user, main, a, st);  // MCX_VL_SOURCE: mcx_user.hip
+  if (lik == LIK_USER) return user_lik_launch_fused(*e->lik.user, main, a, st, &e->steps);  // MCX_VL_SOURCE: mcx_user.hip
   const FusedChoice c = fused_choice(e, a);
   if (c.kernel != FUSED_SPLIT) {
     if (c.kernel == FUSED_HOT && a.samp_x && a.d < 4 * lpc) {  // the plain hot-path kernel's lanes without parameters store their rows here
       MCXCHK(e->trash.alloc(4 * (size_t)a.n * lpc));
       SegArgs b = a;
       b.trash = e->trash.p;
-      return launch_fused_plain(lpc, lik, main, b, st, c);
+      return launch_fused_plain(lpc, lik, main, b, st, c, &e->steps);
     }
-    return launch_fused_plain(lpc, lik, main, a, st, c);
+    return launch_fused_plain(lpc, lik, main, a, st, c, &e->steps);
   }
   // generator and step kernel alternate on the engine's stream (overlapping them on two streams was
   // measured slower: the cross-stream event waits cost more than the generator, which is ~10 % of a chunk)
@@ -108,7 +108,7 @@ static int launch_fused(mcx_engine *e, bool main, const SegArgs &a, hipStream_t 
     const int ns = std::min(SPLIT_CHUNK, a.nsteps - c0);
     {
       ProfScope pg(e, MCX_K_GEN_NORMALS, (uint64_t)ns * (uint64_t)a.n);
-      HIPCHK(mcxk_launch_gen(lpc, e->zpre.p, e->upre.p, a.n, a.d, ns, a.t0 + (uint32_t)c0, a.g0, a.seed, st));
+      HIPCHK(mcxk_launch_gen(lpc, e->zpre.p, e->upre.p, a.n, a.d, ns, a.t0 + (uint32_t)c0, a.g0, a.seed, st, &e->steps));
     }
     SegArgs b = a;
     b.nsteps = ns;
@@ -122,7 +122,7 @@ static int launch_fused(mcx_engine *e, bool main, const SegArgs &a, hipStream_t 
     b.zpre = e->zpre.p;
     b.upre = e->upre.p;
     b.trash = e->trash.p;
-    HIPCHK(mcxk_launch_fast_pregen(lpc, lik, main, b, st));
+    HIPCHK(mcxk_launch_fast_pregen(lpc, lik, main, b, st, &e->steps));
     e->cnt.kernel_launches += 1;  // (the generator's scope counted itself)
   }
   return MCX_OK;
@@ -438,6 +438,8 @@ extern "C" int mcx_run(mcx_engine *e, int nsamp, int nburn, const float *pinit, 
   static const int verbose = getenv("MCX_VERBOSE") ? atoi(getenv("MCX_VERBOSE")) : 0;
   const auto ht0 = std::chrono::steady_clock::now();
   e->ht_mark[0] = e->ht_mark[1] = e->ht_mark[2] = ht0;
+  e->steps.n = 0;  // the ledger of step-kernel instances (mcx_debug_step_instances) starts over
+  e->steps.lost = false;
   int rc = run_once(e, nsamp, nburn, pinit, L, incov);
   if (verbose >= 2) {  // where the host's share of a run goes: set-up / queued everything / stream idle / done
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -746,8 +748,8 @@ static int launch_small_stretch(Run &r, const SmallStretch &s)
   // at the end of the run
   if (pb > 0) MCXCHK(meet_lock_take(e));
   ProfScope ps(e, MCX_K_RUN_SMALL, (uint64_t)(pb + pm) * r.n);
-  const hipError_t le = e->lik.kind == LIK_USER ? user_lik_launch_small(*e->lik.user, r.pbpl, ra, st)
-                                                : mcxk_launch_persist(e->lpc, r.pbpl, e->lik.kind, ra, st);
+  const hipError_t le = e->lik.kind == LIK_USER ? user_lik_launch_small(*e->lik.user, r.pbpl, ra, st, &e->steps)
+                                                : mcxk_launch_persist(e->lpc, r.pbpl, e->lik.kind, ra, st, &e->steps);
   if (le != hipSuccess) (void)meet_release(e, true);
   if (le == hipErrorCooperativeLaunchTooLarge) {  // the grid cannot be resident at once on this device
     (void)hipGetLastError();

@@ -256,7 +256,7 @@ int user_lik_variant(int lpc, const mcx::SegArgs &a)
   return 2;                                                   // generic kernel: any d, accept mask
 }
 
-int user_lik_launch_fused(const UserLik &u, bool main, const mcx::SegArgs &a, hipStream_t st)
+int user_lik_launch_fused(const UserLik &u, bool main, const mcx::SegArgs &a, hipStream_t st, mcx::StepLedger *led)
 {
   const int v = user_lik_variant(u.lpc, a);
   hipFunction_t f = v == 0 ? u.fast[main ? 1 : 0] : (v == 1 ? u.full[main ? 1 : 0] : u.steps[main ? 1 : 0]);
@@ -269,6 +269,8 @@ int user_lik_launch_fused(const UserLik &u, bool main, const mcx::SegArgs &a, hi
   mcx::SegArgs arg = a;
   void *args[] = {&arg};
   const unsigned grid = (unsigned)(((size_t)a.n * lanes + mcx::BLOCK - 1) / mcx::BLOCK);
+  // (compiled at run time: the ledger knows the family, the lanes and blocks per lane, and which loop)
+  if (led) (void)led->note(mcx::step_id(mcx::SF_USER, lanes, lanes == u.lpc ? 1 : u.bpl, mcx::LIK_USER, main, mcx::EMIT_ANY, false));
   HIPCHK(hipModuleLaunchKernel(f, grid, 1, 1, mcx::BLOCK, 1, 1, 0, st, args, nullptr));
   return MCX_OK;
 }
@@ -288,7 +290,7 @@ double user_lik_compile_ms(const UserLik &u) { return u.compile_ms; }
 bool user_lik_small_ok(const UserLik &u) { return u.block_form && u.lpc <= 8; }
 
 // mcxk_launch_persist for LIK_USER: the kernel for (blocks per lane, recorders) is built on first use
-hipError_t user_lik_launch_small(UserLik &u, int bpl, const mcx::RunArgs &a, hipStream_t st)
+hipError_t user_lik_launch_small(UserLik &u, int bpl, const mcx::RunArgs &a, hipStream_t st, mcx::StepLedger *led)
 {
   const int lpc2 = u.lpc / bpl, rec = mcxk_persist_recorders(a.own, bpl) ? 1 : 0;
   UserLik::Small *k = nullptr;
@@ -329,6 +331,7 @@ hipError_t user_lik_launch_small(UserLik &u, int bpl, const mcx::RunArgs &a, hip
   }
   mcx::RunArgs arg = a;
   void *args[] = {&arg};
+  if (led) (void)led->note(mcx::step_id(mcx::SF_USER, lpc2, bpl, mcx::LIK_USER, false, mcx::EMIT_ANY, rec != 0));
   return hipModuleLaunchKernel(k->fn, nwg, 1, 1, mcx::PBLOCK, 1, 1, (unsigned)lds, st, args, nullptr);
 }
 

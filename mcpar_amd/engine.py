@@ -1,4 +1,5 @@
 """Host-side mirror of the reference's MCPar interface (src/mcpar.hh:32-42) over the C ABI."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -125,6 +126,64 @@ def small_stretch(items, index, nsamp, gather_in_flight=False):
     end, out = C.c_int(0), (C.c_int * 5)()
     check(load().mcx_debug_small_stretch(arr, len(items), index, nsamp, int(bool(gather_in_flight)), C.byref(end), out))
     return (end.value,) + tuple(out)
+
+
+# ---- the step-kernel template instances (include/mcx.h: mcx_debug_step_instances) ----
+STEP_FAMILIES = {1: "fast", 2: "fastb", 3: "fast_full", 4: "fastb_full", 5: "pregen", 6: "gen_normals", 7: "generic",
+                 8: "persist", 9: "user"}
+LIK_NAMES = {0: "", 1: "LIK_ROSEN1", 2: "LIK_ROSEN2", 3: "LIK_GAUSS", 5: "LIK_MIX", 6: "LIK_ROSEN2F", 7: "LIK_USER"}
+EMIT_NAMES = {0: "", 1: "EMIT_NONE", 2: "EMIT_EVERY", 3: "EMIT_THIN"}
+StepInstance = collections.namedtuple("StepInstance", "family lanes bpl lik main emit rec")
+
+
+def step_instance_decode(word):
+    """the id of one compiled step-kernel instance -> StepInstance(family, lanes, bpl, lik, main, emit, rec), names for
+    family, lik and emit"""
+    w = int(word)
+    return StepInstance(STEP_FAMILIES[w & 15], (w >> 4) & 127, (w >> 11) & 7, LIK_NAMES[(w >> 14) & 15], bool((w >> 18) & 1),
+                        EMIT_NAMES[(w >> 19) & 3], bool((w >> 21) & 1))
+
+
+def step_instance_encode(rec):
+    inv = lambda m, v: next(k for k, name in m.items() if name == v)  # noqa: E731
+    return (inv(STEP_FAMILIES, rec.family) | rec.lanes << 4 | rec.bpl << 11 | inv(LIK_NAMES, rec.lik) << 14 | int(rec.main) << 18 |
+            inv(EMIT_NAMES, rec.emit) << 19 | int(rec.rec) << 21)
+
+
+def step_instance_name(r):
+    """the record as the C++ instance the launcher names, e.g. k_fused_fastb<2,4,true,LIK_MIX>"""
+    b = lambda v: "true" if v else "false"  # noqa: E731
+    f = r.family
+    if f == "fast":
+        return "k_fused_fast<%d,%s,%s,false,false,%s>" % (r.lanes, b(r.main), r.lik, r.emit)
+    if f == "fastb":
+        return "k_fused_fastb<%d,%d,%s,%s>" % (r.lanes, r.bpl, b(r.main), r.lik)
+    if f == "fast_full":
+        return "k_fused_fast<%d,%s,%s,false,true>" % (r.lanes, b(r.main), r.lik)
+    if f == "fastb_full":
+        return "k_fused_fastb<%d,%d,%s,%s,true>" % (r.lanes, r.bpl, b(r.main), r.lik)
+    if f == "pregen":
+        return "k_fused_fast<%d,%s,%s,true>" % (r.lanes, b(r.main), r.lik)
+    if f == "gen_normals":
+        return "k_gen_normals<%d>" % r.lanes
+    if f == "generic":
+        return "k_fused_steps<%d,%s,%s>" % (r.lanes, r.lik, b(r.main))
+    if f == "persist":
+        return "k_run_small<%d,%d,%s,%s>" % (r.lanes, r.bpl, r.lik, b(r.rec))
+    return "user<lanes=%d,bpl=%d,main=%s,rec=%s>" % (r.lanes, r.bpl, b(r.main), b(r.rec))
+
+
+def _step_ids(call):
+    n = C.c_int(0)
+    check(call(None, 0, C.byref(n)))
+    ids = np.zeros(max(n.value, 1), np.uint32)
+    check(call(ids.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
+    return [step_instance_decode(w) for w in ids[:n.value]]
+
+
+def step_instance_list():
+    """every step-kernel instance the launchers can launch (mcx_debug_step_instance_list; host logic only, needs no GPU)"""
+    return _step_ids(load().mcx_debug_step_instance_list)
 
 
 def _probs(probs):
@@ -522,6 +581,12 @@ class Engine:
         c = Counters()
         check(load().mcx_get_counters(self.h, C.byref(c)))
         return {n: int(getattr(c, n)) for n, _ in Counters._fields_}
+
+    @property
+    def step_instances(self):
+        """the distinct step-kernel instances launched since the last run() began, in order of first launch
+        (mcx_debug_step_instances): StepInstance records"""
+        return _step_ids(lambda ids, cap, n: load().mcx_debug_step_instances(self.h, ids, cap, n))
 
     @property
     def tuner_trace(self):

@@ -10,6 +10,22 @@ from test_gpu_configs import mix_params, same_bits
 pytestmark = pytest.mark.gpu
 
 
+LIK = {"rosen": "LIK_ROSEN1", "gauss": "LIK_GAUSS", "mix": "LIK_MIX"}
+
+
+def blocks(d):
+    """4-parameter blocks per chain, rounded up to a power of two (lpc_for)"""
+    return max(1, 1 << ((d + 3) // 4 - 1).bit_length())
+
+
+def assert_launched(eg, want, what):
+    """the library's ledger of template instances (Engine.step_instances): exactly these ran, by name"""
+    from mcpar_amd import engine as E
+    got = set(eg.step_instances)
+    assert got == set(want), "%s launched %s, not %s" % (what, sorted(map(E.step_instance_name, got)),
+                                                          sorted(map(E.step_instance_name, want)))
+
+
 def specs(kind, d):
     import mcpar_amd as M
     if kind == "rosen":
@@ -40,6 +56,11 @@ def test_blocks_per_lane_same_bits_as_oracle(kind, d, n, bpl):
     eg.set_option(E.OPT_PERSIST, 0)
     eg.set_option(E.OPT_SPLIT_RNG, 0)  # the plain hot-path kernel, not the small-n modes
     eg.run(nsamp, nburn, p, vg)
+    # fused_choice halves a forced bpl while it exceeds the blocks per chain -- d = 8 with four runs two -- and takes it
+    # otherwise, ragged chains included
+    ran = {(8, 4): 2}.get((d, bpl), bpl)
+    assert ran <= blocks(d) and (ran == bpl or bpl > blocks(d))
+    assert_launched(eg, [E.StepInstance("fastb", blocks(d) // ran, ran, LIK[kind], m, "", False) for m in (False, True)], (kind, d, bpl))
     c = eg.counters
     assert c["naccept_burn"] == eo.naccept_burn and c["naccept_main"] == eo.naccept_main
     assert np.array_equal(eg.accept_counts, eo.accept_counts)
@@ -65,6 +86,7 @@ def test_blocks_per_lane_thinned_store_and_second_run(bpl):
     for rep in range(2):
         eo.run(nsamp, nburn, p, vo)
         eg.run(nsamp, nburn, p, vg)
+        assert_launched(eg, [E.StepInstance("fastb", 4 // bpl, bpl, "LIK_ROSEN1", m, "", False) for m in (False, True)], (rep, bpl))
         kept = (nsamp + stride - 1) // stride
         assert same_bits(eg.samples, eo.samples[-kept * n:]), rep
         for name in ("state", "mean", "var"):
@@ -116,6 +138,15 @@ def test_small_n_blocks_per_lane_same_bits_as_oracle(kind, d, n, bpl):
         eg.run(nsamp, nburn, p, vg)
         c = eg.counters
         assert c["kernel_launches"] <= 3 and c["meet_timeouts"] == 0, c
+        # mcxk_persist_bpl takes a forced bpl where bpl <= blocks per chain and d % (4 bpl) == 0; the illegal ones run one
+        # block per lane: d = 12 with two or four, d = 8 with four, d = 24 with four
+        ran = 1 if (d, bpl) in ((12, 2), (12, 4), (8, 4), (24, 4)) else bpl
+        assert (ran == bpl) == (bpl <= blocks(d) and d % (4 * bpl) == 0)
+        lanes = blocks(d) // ran
+        nown = (n * lanes + 63) // 64
+        own = -(-nown // min(nown, E.device_info()[1]))
+        assert_launched(eg, [E.StepInstance("persist", lanes, ran, LIK[kind], False, "", own * ran <= 1)], (kind, d, bpl, rep))
+        assert c["small_n_blocks_per_lane"] == ran, c
         assert c["naccept_burn"] == eo.naccept_burn and c["naccept_main"] == eo.naccept_main
         assert np.array_equal(eg.accept_counts, eo.accept_counts)
         assert np.array_equal(eg.tuner_trace, eo.tuner_trace)
@@ -200,6 +231,10 @@ def test_full_covariance_kernels_same_bits_as_oracle(kind, d, n, pl, bpl):
     eg.set_option(E.OPT_PERSIST, 0)
     eg.set_option(E.OPT_SPLIT_RNG, 0)
     eg.run(nsamp, nburn, p, vg, cov)
+    # fused_choice: the mirrored kernel where two blocks per lane are forced, or left to the engine at 8 blocks per chain
+    mirrored = bpl == 2 or (bpl == 0 and blocks(d) == 8)
+    assert_launched(eg, [E.StepInstance("fastb_full", blocks(d) // 2, 2, LIK[kind], m, "", False) if mirrored else
+                         E.StepInstance("fast_full", blocks(d), 1, LIK[kind], m, "", False) for m in (False, True)], (kind, d, bpl))
     c = eg.counters
     assert (c["naccept_burn"], c["naccept_main"]) == (eo.naccept_burn, eo.naccept_main)
     assert (c["remote_steps"], c["remote_passes"]) == (eo.remote_steps, eo.remote_passes)

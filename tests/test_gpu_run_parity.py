@@ -21,7 +21,7 @@ def mix_params(d, K):
 
 
 def run_pair(kind, d, n, nburn, nsamp, pl, params=None, ncomp=0, incov=None, fuse=1, sync=10,
-             pinit=None, maxseg=None, host=False):
+             pinit=None, maxseg=None, host=False, mask=1):
     import mcpar_amd as M
     from mcpar_amd import engine as E
     p = O.default_pinit(d, n) if pinit is None else pinit
@@ -35,7 +35,7 @@ def run_pair(kind, d, n, nburn, nsamp, pl, params=None, ncomp=0, incov=None, fus
     else:
         vg, keep_g = M.make_vlfunc(kind, d, params, ncomp)
     eg = M.Engine(d, n, pl=pl, sync=sync)
-    eg.set_option(E.OPT_ACCEPT_MASK, 1)
+    eg.set_option(E.OPT_ACCEPT_MASK, mask)
     eg.set_option(E.OPT_FUSE, fuse)
     if maxseg:
         eg.set_option(E.OPT_MAX_SEGMENT, maxseg)
@@ -43,10 +43,11 @@ def run_pair(kind, d, n, nburn, nsamp, pl, params=None, ncomp=0, incov=None, fus
     return eo, eg
 
 
-def assert_same(eo, eg, what=""):
-    mo, mg = eo.accept_mask, eg.accept_mask
-    bad = np.argwhere(mo != mg)
-    assert bad.size == 0, "%s accept mask differs first at (step, chain) %s" % (what, bad[:3])
+def assert_same(eo, eg, what="", mask=True):
+    if mask:
+        mo, mg = eo.accept_mask, eg.accept_mask
+        bad = np.argwhere(mo != mg)
+        assert bad.size == 0, "%s accept mask differs first at (step, chain) %s" % (what, bad[:3])
     c = eg.counters
     assert c["naccept_burn"] == eo.naccept_burn and c["naccept_main"] == eo.naccept_main
     assert c["remote_steps"] == eo.remote_steps and c["remote_passes"] == eo.remote_passes
@@ -156,20 +157,43 @@ def test_full_covariance():
 @pytest.mark.parametrize("d", [4, 8, 12, 16, 20, 24, 28, 32])
 def test_full_covariance_fast_kernel(d):
     """k_fused_fast<..., FULL>: the Cholesky factor staged in LDS, z by DPP (<= 4 lanes per chain) or through LDS
-    (8 lanes), every likelihood of the fast path, burn-in (tuner rescales the factor) + main loop."""
+    (8 lanes), every likelihood of the fast path, burn-in (tuner rescales the factor) + main loop.
+
+    The full-covariance hot path does not record the accept mask (fused_choice: lanes_ok needs the mask off), and run_pair
+    turns the mask on: those runs take the generic kernel, as this test did unnoticed until the library could say which
+    instance ran.  They stay, named for what they are; the same jobs with the mask off run the kernel the test is about:
+    one block per lane up to 4 blocks per chain, the mirrored two blocks per lane at 8 (the engine's own choice)."""
+    from mcpar_amd import engine as E
     rng = np.random.default_rng(100 + d)
     a = rng.normal(size=(d, d)).astype(np.float32)
     cov = (0.3 * (a @ a.T / d + 0.5 * np.eye(d))).astype(np.float32)
     n = 3 * 64 + 5  # several wavefronts, the last one ragged
-    eo, eg = run_pair(O.VL_ROSENBROCK1, d, n, 160, 45, 1.0, incov=cov)
-    assert_same(eo, eg, "fullcov fast rosen1 d%d" % d)
+    lpc = max(1, 1 << ((d + 3) // 4 - 1).bit_length())
+
+    def check(eg, lik, mask, what):
+        if mask:
+            want = [E.StepInstance("generic", lpc, 1, lik, m, "", False) for m in (False, True)]
+        elif lpc == 8:
+            want = [E.StepInstance("fastb_full", 4, 2, lik, m, "", False) for m in (False, True)]
+        else:
+            want = [E.StepInstance("fast_full", lpc, 1, lik, m, "", False) for m in (False, True)]
+        got = set(eg.step_instances)
+        assert got == set(want), "%s launched %s, not %s" % (what, sorted(map(E.step_instance_name, got)),
+                                                              sorted(map(E.step_instance_name, want)))
+
     g = np.concatenate([rng.normal(size=d), rng.uniform(0.5, 2.0, size=d)]).astype(np.float32)
-    eo, eg = run_pair(O.VL_GAUSSIAN, d, n, 110, 30, 0.9, params=g, incov=cov)
-    assert_same(eo, eg, "fullcov fast gauss d%d" % d)
     K = 3
     m = np.concatenate([rng.normal(size=K * d), [2.0, 1.0, 1.0]]).astype(np.float32)
-    eo, eg = run_pair(O.VL_GAUSSMIX, d, n, 60, 30, 1.0, params=m, ncomp=K, incov=cov)
-    assert_same(eo, eg, "fullcov fast mix d%d" % d)
+    for mask in (1, 0):
+        eo, eg = run_pair(O.VL_ROSENBROCK1, d, n, 160, 45, 1.0, incov=cov, mask=mask)
+        check(eg, "LIK_ROSEN1", mask, "rosen1 d%d" % d)
+        assert_same(eo, eg, "fullcov fast rosen1 d%d" % d, mask=bool(mask))
+        eo, eg = run_pair(O.VL_GAUSSIAN, d, n, 110, 30, 0.9, params=g, incov=cov, mask=mask)
+        check(eg, "LIK_GAUSS", mask, "gauss d%d" % d)
+        assert_same(eo, eg, "fullcov fast gauss d%d" % d, mask=bool(mask))
+        eo, eg = run_pair(O.VL_GAUSSMIX, d, n, 60, 30, 1.0, params=m, ncomp=K, incov=cov, mask=mask)
+        check(eg, "LIK_MIX", mask, "mix d%d" % d)
+        assert_same(eo, eg, "fullcov fast mix d%d" % d, mask=bool(mask))
 
 
 def test_second_run_continues_rng():
