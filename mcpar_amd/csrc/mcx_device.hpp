@@ -16,6 +16,7 @@
 //   burn-in tuner       src/mcpar.cc:77-96     -> k_tuner
 #pragma once
 #include "mcx_numerics.hpp"
+#include "mcx_block.hpp"
 
 namespace mcx {
 
@@ -634,7 +635,7 @@ __global__ __launch_bounds__(BLOCK) void k_gen_normals(float *__restrict__ Z, fl
   if (4 * q < d) {
     f32x2 ze, zo;
     normal4_packed(philox4x32_10(t, g, (uint32_t)q, 0u, seed, ST_LOCAL), ze, zo);
-    *reinterpret_cast<float4 *>(Z + ((size_t)s * n + chain) * d + 4 * q) = make_float4(ze.x, zo.x, ze.y, zo.y);
+    pk_store(Z + ((size_t)s * n + chain) * d + 4 * q, ze, zo);
   }
   if (q == 0 && ((t & 3u) == 0u || s == 0)) {
     const u32x4 aw = philox4x32_10(t >> 2, g, 0u, 0u, seed, ST_ACCEPT);
@@ -766,42 +767,22 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
   static_assert(LIK == LIK_ROSEN1 || LIK == LIK_GAUSS || LIK == LIK_MIX || (LIK == LIK_ROSEN2F && !PREGEN && !FULL) || (LIK == LIK_USER && !PREGEN),
                 "fast path: Rosenbrock1, diagonal Gaussian, a mixture of <= 8 unit Gaussians, (plain kernel only) the overlapping Rosenbrock, or a user's source");
   static_assert(!(FULL && PREGEN), "the pre-generated normals are laid out for diagonal proposals");
-  // MCX_FULL_T_REGS: up to 16-D (<= 64 registers) a lane's four rows of the factor live in REGISTERS for the whole launch
+  // TREGS: up to 16-D (<= 64 registers) a lane's four rows of the factor live in REGISTERS for the whole launch
   // instead of being re-read from LDS every step: 16-D 2.78 -> 2.73 ms per job (tools/fullcov_ab.sh).  At 32-D the same
   // takes 128 registers -- two wavefronts per SIMD instead of four -- and LOSES: 6.31 -> 6.91 ms, although 32 of the
   // lane's 41 LDS reads per step go away; there the factor stays in LDS and the work is cut by k_fused_fastb's mirrored
-  // layout instead (mcx_fastb.hpp).  0: the factor in LDS everywhere (the round-2 kernel), for A/B.
-#ifndef MCX_FULL_T_REGS
-#define MCX_FULL_T_REGS 1
-#endif
-#ifndef MCX_FAST_UNROLL4
-#define MCX_FAST_UNROLL4 1
-#endif
-// MCX_TAKE_SELECT: the acceptance as selects (1) or as the compiler's branch (0) -- see the step
-#ifndef MCX_TAKE_SELECT
-#define MCX_TAKE_SELECT 0
-#endif
-  constexpr bool TREGS = FULL && LPC <= 4 && (MCX_FULL_T_REGS != 0);
+  // layout instead (mcx_fastb.hpp).
+  constexpr bool TREGS = FULL && LPC <= 4;
   __shared__ __attribute__((aligned(16))) float4 lds_T[FULL && !TREGS ? 4 * LPC * LPC : 1];
   __shared__ __attribute__((aligned(16))) float4 lds_z[FULL && LPC == 8 ? (BLOCK / 8) * 9 : 1];
   if (FULL && !TREGS) {
-    const int dd = a.d;
-    // slot [(qq * 4 + c) * LPC + qv] = column 4 qq + c of the four rows of lane qv, as (row 0, row 2, row 1, row 3):
-    // the two halves are the packed operands of the lane's (x0, x2) / (x1, x3) accumulators
-    for (int i = threadIdx.x; i < 16 * LPC * LPC; i += BLOCK) {
-      const int h = i & 3, qv = (i >> 2) % LPC, c = ((i >> 2) / LPC) & 3, qq = (i >> 2) / (4 * LPC);
-      const int row = 4 * qv + (h == 0 ? 0 : (h == 1 ? 2 : (h == 2 ? 1 : 3))), col = 4 * qq + c;
-      reinterpret_cast<float *>(lds_T)[i] = (row < dd && col < dd) ? a.T[row * dd + col] : 0.0f;
-    }
+    stage_factor_columns<LPC, BLOCK>(lds_T, a.T, a.d);
     if (LIK != LIK_MIX) __syncthreads();
   }
-  // mixture: component means and log-weights staged in LDS (every lane group reads the same rows)
   __shared__ __attribute__((aligned(16))) float lds_means[LIK == LIK_MIX ? 8 * MAXD_LDS : 4];
   __shared__ float lds_logw[8];
   if (LIK == LIK_MIX) {
-    const int kd = a.ncomp * a.d;
-    for (int i = threadIdx.x; i < kd; i += BLOCK) lds_means[i] = a.lik[i];
-    if (threadIdx.x < (unsigned)a.ncomp) lds_logw[threadIdx.x] = a.lik[kd + threadIdx.x];
+    stage_mixture<BLOCK>(lds_means, lds_logw, a.lik, a.ncomp, a.d);
     __syncthreads();
   }
   const int d = a.d;
@@ -816,17 +797,12 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
 
   f32x2 xe = {0, 0}, xo = {0, 0}, me = {0, 0}, mo = {0, 0}, se = {0, 0}, so = {0, 0}, te = {0, 0}, to = {0, 0};
   if (live) {
-    const float4 f = *reinterpret_cast<const float4 *>(a.x + off);
-    xe = f32x2{f.x, f.z}; xo = f32x2{f.y, f.w};
-    te = f32x2{a.T[(k0 + 0) * d + k0 + 0], a.T[(k0 + 2) * d + k0 + 2]};
-    to = f32x2{a.T[(k0 + 1) * d + k0 + 1], a.T[(k0 + 3) * d + k0 + 3]};
+    pk_load(a.x + off, xe, xo);
+    pk_load_tdiag(a.T, d, k0, te, to);
     if (MAIN && a.init_moments) {  // src/mcpar.cc:99-104
       se = f32x2{FPEPS, FPEPS}; so = f32x2{FPEPS, FPEPS};
     } else if (MAIN) {
-      const float4 m = *reinterpret_cast<const float4 *>(a.mu + off);
-      const float4 p = *reinterpret_cast<const float4 *>(a.psum2 + off);
-      me = f32x2{m.x, m.z}; mo = f32x2{m.y, m.w};
-      se = f32x2{p.x, p.z}; so = f32x2{p.y, p.w};
+      pk_load_moments(a.mu, a.psum2, off, me, mo, se, so);
     }
   }
   // FULL, factor in registers: column col of this lane's rows (0, 2) and (1, 3) -- the packed operands of the two
@@ -842,12 +818,9 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
 #pragma unroll
     for (int col = 0; col < 4 * LPC; ++col) asm volatile("" ::"v"(tre[col]), "v"(tro[col]));  // (awaited here, once: see below)
   }
-  f32x2 gme = {0, 0}, gmo = {0, 0};  // Gaussian: this lane's means and 1/sigma^2 (lik = mu[d], s2inv[d])
-  float gs0 = 0, gs1 = 0, gs2 = 0, gs3 = 0;
-  if (LIK == LIK_GAUSS && live) {
-    gme = f32x2{a.lik[k0 + 0], a.lik[k0 + 2]}; gmo = f32x2{a.lik[k0 + 1], a.lik[k0 + 3]};
-    gs0 = a.lik[d + k0 + 0]; gs1 = a.lik[d + k0 + 1]; gs2 = a.lik[d + k0 + 2]; gs3 = a.lik[d + k0 + 3];
-  }
+  f32x2 gme = {0, 0}, gmo = {0, 0};  // Gaussian: this lane's means and 1/sigma^2
+  float gs[4] = {0, 0, 0, 0};
+  if (LIK == LIK_GAUSS && live) pk_load_gauss(a.lik, d, k0, gme, gmo, gs);
   float ly = a.ly[chain];
   uint32_t cnt = 0, wacc = 0;
   f32x2 al01 = {0, 0}, al23 = {0, 0};  // log of the four acceptance draws of this lane's current ACCEPT block
@@ -869,15 +842,7 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
   }
   // snapshot for the next exchange after step snap_after (src/mcpar.cc:202-208), winv_s = that step's 1/pwgt
   auto snapshot = [&](float winv_s) {
-    if (live) {
-      const f32x2 w2 = splat2(winv_s);
-      const f32x2 ve = se * w2, vo = so * w2;
-      float4 *slot = reinterpret_cast<float4 *>(a.musig_own + 2 * off);
-      slot[0] = make_float4(me.x, ve.x, mo.x, vo.x);
-      slot[1] = make_float4(me.y, ve.y, mo.y, vo.y);
-      // the run's last step: the variances as mcx_get_var returns them (k_variance otherwise)
-      if (a.sig_out) *reinterpret_cast<float4 *>(a.sig_out + off) = make_float4(ve.x, vo.x, ve.y, vo.y);
-    }
+    if (live) pk_snapshot(se, so, splat2(winv_s), a.musig_own, a.sig_out, off, me, mo);
   };
 
   // one Metropolis step given this lane's four normals (ze = z0,z2; zo = z1,z3) and the log of the acceptance draw
@@ -922,11 +887,7 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
     }
     float acc = 0.0f;
     if (LIK == LIK_ROSEN1) {
-      // src/rosenbrock.cc:4-21 on the pairs (x0,x1), (x2,x3)
-      const f32x2 t1 = splat2(1.0f) - pe;
-      const f32x2 t2 = fma2(-pe, pe, po);
-      const f32x2 term = fma2(splat2(100.0f) * t2, t2, t1 * t1);
-      if (live) acc = term.x + term.y;  // == (0 + term.x) + term.y: the terms are >= +0
+      acc = pk_rosen1(pe, po, live);
     } else if (LIK == LIK_ROSEN2F) {
       // the overlapping Rosenbrock (MCX_VL_ROSENBROCK2_FIXED): terms k = k0 .. k0+3 on the pairs (x0,x1), (x1,x2),
       // (x2,x3), (x3, x4) with x4 = the first parameter of the chain's next lane (DPP row_shl 1); the chain's last
@@ -942,15 +903,7 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
         if (k0 + 4 < d) acc = acc + to_.y;
       }
     } else if (LIK == LIK_GAUSS) {
-      // src/rosenbrock.cc:44-61: acc = fma((0.5 a) a, 1/sigma^2, acc) for k = 0..3 in order
-      const f32x2 ae = pe - gme, ao = po - gmo;
-      const f32x2 he = (splat2(0.5f) * ae) * ae, ho = (splat2(0.5f) * ao) * ao;
-      if (live) {
-        acc = __builtin_fmaf(he.x, gs0, 0.0f);
-        acc = __builtin_fmaf(ho.x, gs1, acc);
-        acc = __builtin_fmaf(he.y, gs2, acc);
-        acc = __builtin_fmaf(ho.y, gs3, acc);
-      }
+      acc = pk_gauss(pe, po, gme, gmo, gs, live);
     }
     float lyt;
 #ifdef MCX_USER_LIK
@@ -962,49 +915,23 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
     } else
 #endif
     if (LIK == LIK_MIX) {
-      // log sum_c w_c exp(-|x - m_c|^2 / 2) as a log-sum-exp (DualGaussian: src/rosenbrock.cc:63-78)
       const int K = a.ncomp;
       float e[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         e[c] = 0.0f;
-        if (c < K) {
-          float s2 = 0.0f;
-          if (live) {
-            const float4 m = *reinterpret_cast<const float4 *>(&lds_means[c * d + k0]);
-            const f32x2 ae = pe - f32x2{m.x, m.z}, ao = po - f32x2{m.y, m.w};
-            s2 = __builtin_fmaf(ae.x, ae.x, 0.0f);
-            s2 = __builtin_fmaf(ao.x, ao.x, s2);
-            s2 = __builtin_fmaf(ae.y, ae.y, s2);
-            s2 = __builtin_fmaf(ao.y, ao.y, s2);
-          }
-          e[c] = __builtin_fmaf(-0.5f, group_sum<LPC>(s2), lds_logw[c]);
-        }
+        if (c < K) e[c] = __builtin_fmaf(-0.5f, group_sum<LPC>(pk_mix_dist2(pe, po, &lds_means[c * d + k0], live)), lds_logw[c]);
       }
-      float emax = e[0];
-#pragma unroll
-      for (int c = 1; c < 8; ++c)
-        if (c < K) emax = e[c] > emax ? e[c] : emax;
-      float ssum = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 8; c += 2) {  // exp two components at a time, add them in component order
-        if (c < K) {
-          const f32x2 ex = expf_v2x2(f32x2{e[c] - emax, e[c + 1] - emax});
-          ssum = ssum + ex.x;
-          if (c + 1 < K) ssum = ssum + ex.y;
-        }
-      }
-      lyt = emax + logf_v1(ssum);
+      lyt = mix_logsumexp(e, K);
     } else {
       lyt = 0.0f - group_sum<LPC>(acc);
     }
     // src/mcpar.cc:62-75 (cfac = 1 for local proposals): log u < ly' - ly
     // The acceptance: left to itself the compiler makes a divergent branch of it -- one exec-mask region per step, the
-    // taken side moving (pe, po, lyt) into place and computing the Welford differences from them.  With the pin
-    // (MCX_TAKE_SELECT=1) the trial values are opaque, there is nothing to move, and the step is one basic block of
+    // taken side moving (pe, po, lyt) into place and computing the Welford differences from them.  With a register pin
+    // on (pe, po, lyt) the trial values are opaque, there is nothing to move, and the step is one basic block of
     // selects: 7 more VALU instructions per 4 steps, v_cndmask at 4.4 cycles where the moves cost 2.6.  Timed in turn
     // on one MI355X (headline job, 4 runs each): selects 2.00 ms, branch 1.98 ms -- the branch stays.
-    if (MCX_TAKE_SELECT && EMIT != EMIT_ANY) asm volatile("" : "+v"(pe), "+v"(po), "+v"(lyt));
     const bool take = accept_local(lyt, ly, u);
     xe = take ? pe : xe;
     xo = take ? po : xo;
@@ -1012,22 +939,17 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
     cnt += take ? 1u : 0u;
     wacc += (uint32_t)__popcll(__ballot(take && q == 0));
     if (MAIN) {
-      const f32x2 w2 = splat2(winv_s);               // src/mcpar.cc:186-187
-      const f32x2 de = xe - me, dO = xo - mo;         // src/mcpar.cc:199-202
-      me = fma2(de, w2, me);
-      mo = fma2(dO, w2, mo);
-      se = fma2(de, xe - me, se);
-      so = fma2(dO, xo - mo, so);
+      pk_welford(xe, xo, splat2(winv_s), me, mo, se, so);
       // (the step-loop drivers without pre-generated normals split the launch's steps at snap_after instead)
       if (PREGEN && s == a.snap_after) snapshot(winv_s);
       if (EMIT == EMIT_EVERY) {  // src/mcpar.cc:177-182
-        *reinterpret_cast<float4 *>(sxv) = make_float4(xe.x, xo.x, xe.y, xo.y);
+        pk_store(sxv, xe, xo);
         *slv = ly;
         sxv += sxv_stride;
         slv += sl_stride;
       } else if (EMIT == EMIT_THIN) {
         if (thin_wait == 0) {  // (wave-uniform)
-          *reinterpret_cast<float4 *>(sxv) = make_float4(xe.x, xo.x, xe.y, xo.y);
+          pk_store(sxv, xe, xo);
           *slv = ly;
           sxv += sxv_stride;
           slv += sl_stride;
@@ -1038,18 +960,18 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
         if (PREGEN && a.samp_stride <= 1) {
           // latency-bound mode: no exec-mask regions -- idle lanes store to their trash slot, every lane
           // of the chain stores the (same) log-likelihood
-          *reinterpret_cast<float4 *>(sxv) = make_float4(xe.x, xo.x, xe.y, xo.y);
+          pk_store(sxv, xe, xo);
           *sl = ly;
           sxv += sxv_stride;
           sl += sl_stride;
         } else if (a.samp_stride <= 1) {
-          if (live) *reinterpret_cast<float4 *>(sx) = make_float4(xe.x, xo.x, xe.y, xo.y);
+          if (live) pk_store(sx, xe, xo);
           if (q == 0) *sl = ly;
           sx += sx_stride;
           sl += sl_stride;
         } else if ((a.isamp0 + s) % a.samp_stride == 0) {  // thinned store: row = isamp / stride
           const size_t row = (size_t)((a.isamp0 + s) / a.samp_stride);
-          if (live) *reinterpret_cast<float4 *>(sx + row * sx_stride) = make_float4(xe.x, xo.x, xe.y, xo.y);
+          if (live) pk_store(sx + row * sx_stride, xe, xo);
           if (q == 0) sl[row * sl_stride] = ly;
         }
       }
@@ -1059,8 +981,8 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
   // Every load of the chain state is awaited here, once: the compiler's s_waitcnt bookkeeping is path-insensitive, so
   // a wait left to the first use inside the step loop stays there for every later step -- where the only vector-memory
   // operations in flight are the previous step's sample STORES, and "vmcnt(0)" means "until they have reached HBM".
-  asm volatile("" ::"v"(xe), "v"(xo), "v"(te), "v"(to), "v"(me), "v"(mo), "v"(se), "v"(so), "v"(gme), "v"(gmo), "v"(gs0),
-               "v"(gs1), "v"(gs2), "v"(gs3), "v"(ly));
+  asm volatile("" ::"v"(xe), "v"(xo), "v"(te), "v"(to), "v"(me), "v"(mo), "v"(se), "v"(so), "v"(gme), "v"(gmo), "v"(gs[0]),
+               "v"(gs[1]), "v"(gs[2]), "v"(gs[3]), "v"(ly));
   // 1/pwgt of the launch's steps: read through the CONSTANT address space, i.e. by scalar loads.  As a plain global
   // load (what the compiler made of the uniform address) it sat in the vector-memory queue behind the previous
   // step's sample stores, and the wait for it was a wait for those stores to reach HBM: 21 % of the wavefronts'
@@ -1068,16 +990,7 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
   const __attribute__((address_space(4))) float *wtab = (const __attribute__((address_space(4))) float *)a.winv;
   if (!PREGEN) {
     float wnext = MAIN ? wtab[a.isamp0] : 1.0f;  // requested one step ahead (the table is padded past nsamp)
-    // accept threshold: Philox block (t >> 2) of the ACCEPT stream serves steps 4b..4b+3.  The LPC
-    // lanes of a chain split the work: lane q draws block b for b % LPC == q, once per 4*LPC steps.
-    auto refresh = [&](uint32_t blk) {
-      if ((blk & ~(uint32_t)(LPC - 1)) != ablk) {  // the four logs are taken here, once per 4*LPC steps per lane
-        ablk = blk & ~(uint32_t)(LPC - 1);
-        const u32x4 aw = philox4x32_10(ablk + (uint32_t)q, g, 0u, 0u, a.seed, ST_ACCEPT);
-        al01 = accept_lu_x2(aw.x, aw.y);
-        al23 = accept_lu_x2(aw.z, aw.w);
-      }
-    };
+    auto refresh = [&](uint32_t blk) { accept_refresh<LPC>(blk, q, g, a.seed, ablk, al01, al23); };
     auto one_step = [&](int s) {
       const uint32_t t = a.t0 + (uint32_t)s;
       const float wthis = wnext;
@@ -1086,9 +999,7 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
       normal4_packed(philox4x32_10(t, g, (uint32_t)q, 0u, a.seed, ST_LOCAL), ze, zo);
       const uint32_t blk = t >> 2;
       refresh(blk);
-      const uint32_t wi = t & 3u;
-      const float mine = wi == 0u ? al01.x : (wi == 1u ? al01.y : (wi == 2u ? al23.x : al23.y));
-      const float lu = as_f32(group_bcast<LPC>(as_u32(mine), blk & (uint32_t)(LPC - 1), q));
+      const float lu = as_f32(group_bcast<LPC>(as_u32(accept_word(&al01, &al23, t & 3u)), blk & (uint32_t)(LPC - 1), q));
       step(s, ze, zo, lu, wthis);
     };
     // The snapshot is taken between two runs of the step loop, [0, snap_after] and the rest, rather than tested for in
@@ -1098,7 +1009,6 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
 #pragma nounroll
     for (int pass = 0; pass < (MAIN ? 2 : 1); ++pass) {
       const int hi = (pass == 0 && snap) ? a.snap_after + 1 : a.nsteps;
-#if MCX_FAST_UNROLL4
       // Four steps at a time from a step index that is a multiple of 4 on: which of the block's four logs a step takes is then
       // known at compile time, and the lane that holds them is looked up once per block instead of once per step (two
       // wave-uniform switches per step otherwise: some ten scalar branches and two moves)
@@ -1120,7 +1030,6 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
           }
         }
       }
-#endif
       for (; s < hi; ++s) one_step(s);
       if (pass == 0 && snap) snapshot(wtab[a.isamp0 + a.snap_after]);
     }
@@ -1160,21 +1069,29 @@ __device__ __forceinline__ uint32_t fused_fast_body(const SegArgs &a)
       }
       fetch();
 #pragma unroll
-      for (int k = 0; k < P; ++k) step(s0 + k, f32x2{cur[k].x, cur[k].z}, f32x2{cur[k].y, cur[k].w}, cuu[k], cuw[k]);
+      for (int k = 0; k < P; ++k) {
+        f32x2 ze, zo;
+        pk_pairs(cur[k], ze, zo);
+        step(s0 + k, ze, zo, cuu[k], cuw[k]);
+      }
     }
 #pragma unroll
     for (int k = 0; k < P; ++k)  // the last, partial batch
-      if (s0 + k < a.nsteps) step(s0 + k, f32x2{nxt[k].x, nxt[k].z}, f32x2{nxt[k].y, nxt[k].w}, nxu[k], nxw[k]);
+      if (s0 + k < a.nsteps) {
+        f32x2 ze, zo;
+        pk_pairs(nxt[k], ze, zo);
+        step(s0 + k, ze, zo, nxu[k], nxw[k]);
+      }
   }
 
-  if (live) *reinterpret_cast<float4 *>(a.x + off) = make_float4(xe.x, xo.x, xe.y, xo.y);
+  if (live) pk_store(a.x + off, xe, xo);
   if (q == 0) {
     a.ly[chain] = ly;
     a.acc_cnt[chain] += cnt;
   }
   if (MAIN && live) {
-    *reinterpret_cast<float4 *>(a.mu + off) = make_float4(me.x, mo.x, me.y, mo.y);
-    *reinterpret_cast<float4 *>(a.psum2 + off) = make_float4(se.x, so.x, se.y, so.y);
+    pk_store(a.mu + off, me, mo);
+    pk_store(a.psum2 + off, se, so);
   }
   // one slot per wavefront, owned by it: no atomics (4096 same-address atomics cost ~40 us per launch); with the tuner
   // inside the launch the count travels through tuner_epilogue instead

@@ -46,25 +46,18 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
   static_assert(BPL == 2 || BPL == 4, "two or four blocks per lane");
   static_assert(!FULL || (BPL == 2 && LPC2 <= 4), "full covariance: two mirrored blocks per lane, z by DPP quad permutes");
   constexpr int NB = LPC2 * BPL;  // blocks per chain
-  // FULL: the factor by column, [(4 qq + c) * NB + row block] = column 4 qq + c of the block's rows (0, 2, 1, 3): one
-  // read is the pair of packed operands of the two multiply-adds a column costs a block (k_fused_fast's table)
+  // FULL: the factor by column (stage_factor_columns): one read is the pair of packed operands of the two multiply-adds a
+  // column costs a block (k_fused_fast's table)
   __shared__ __attribute__((aligned(16))) float4 lds_T[FULL ? 4 * NB * NB : 1];
   if (FULL) {
-    const int dd = a.d;
-    for (int i = threadIdx.x; i < 16 * NB * NB; i += BLOCK) {
-      const int h = i & 3, qv = (i >> 2) % NB, c = ((i >> 2) / NB) & 3, qq = (i >> 2) / (4 * NB);
-      const int row = 4 * qv + (h == 0 ? 0 : (h == 1 ? 2 : (h == 2 ? 1 : 3))), col = 4 * qq + c;
-      reinterpret_cast<float *>(lds_T)[i] = (row < dd && col < dd) ? a.T[row * dd + col] : 0.0f;
-    }
+    stage_factor_columns<NB, BLOCK>(lds_T, a.T, a.d);
     if (LIK != LIK_MIX) __syncthreads();
   }
   static_assert(LIK == LIK_ROSEN1 || LIK == LIK_GAUSS || LIK == LIK_MIX || LIK == LIK_USER, "hot-path likelihoods (or a user's source)");
   __shared__ __attribute__((aligned(16))) float lds_means[LIK == LIK_MIX ? 8 * MAXD_LDS : 4];
   __shared__ float lds_logw[8];
   if (LIK == LIK_MIX) {
-    const int kd = a.ncomp * a.d;
-    for (int i = threadIdx.x; i < kd; i += BLOCK) lds_means[i] = a.lik[i];
-    if (threadIdx.x < (unsigned)a.ncomp) lds_logw[threadIdx.x] = a.lik[kd + threadIdx.x];
+    stage_mixture<BLOCK>(lds_means, lds_logw, a.lik, a.ncomp, a.d);
     __syncthreads();
   }
   const int d = a.d;
@@ -100,24 +93,14 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
     xe[b] = xo[b] = me[b] = mo[b] = se[b] = so[b] = te[b] = to[b] = gme[b] = gmo[b] = f32x2{0, 0};
     gs[b][0] = gs[b][1] = gs[b][2] = gs[b][3] = 0.0f;
     if (live[b]) {
-      const float4 f = *reinterpret_cast<const float4 *>(a.x + offb[b]);
-      xe[b] = f32x2{f.x, f.z}; xo[b] = f32x2{f.y, f.w};
-      if (!FULL) {
-        te[b] = f32x2{a.T[(k0 + 0) * d + k0 + 0], a.T[(k0 + 2) * d + k0 + 2]};
-        to[b] = f32x2{a.T[(k0 + 1) * d + k0 + 1], a.T[(k0 + 3) * d + k0 + 3]};
-      }
+      pk_load(a.x + offb[b], xe[b], xo[b]);
+      if (!FULL) pk_load_tdiag(a.T, d, k0, te[b], to[b]);
       if (MAIN && a.init_moments) {  // src/mcpar.cc:99-104
         se[b] = f32x2{FPEPS, FPEPS}; so[b] = f32x2{FPEPS, FPEPS};
       } else if (MAIN) {
-        const float4 m = *reinterpret_cast<const float4 *>(a.mu + offb[b]);
-        const float4 p = *reinterpret_cast<const float4 *>(a.psum2 + offb[b]);
-        me[b] = f32x2{m.x, m.z}; mo[b] = f32x2{m.y, m.w};
-        se[b] = f32x2{p.x, p.z}; so[b] = f32x2{p.y, p.w};
+        pk_load_moments(a.mu, a.psum2, offb[b], me[b], mo[b], se[b], so[b]);
       }
-      if (LIK == LIK_GAUSS) {  // lik = mu[d], 1/sigma^2[d]
-        gme[b] = f32x2{a.lik[k0 + 0], a.lik[k0 + 2]}; gmo[b] = f32x2{a.lik[k0 + 1], a.lik[k0 + 3]};
-        gs[b][0] = a.lik[d + k0 + 0]; gs[b][1] = a.lik[d + k0 + 1]; gs[b][2] = a.lik[d + k0 + 2]; gs[b][3] = a.lik[d + k0 + 3];
-      }
+      if (LIK == LIK_GAUSS) pk_load_gauss(a.lik, d, k0, gme[b], gmo[b], gs[b]);
     }
   }
   float ly = a.ly[chain];
@@ -129,10 +112,9 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
   const size_t sx_stride = (size_t)a.n * d, sl_stride = (size_t)a.n;
 
   // the first log2(BPL) stages of the butterfly over the block index, inside the lane; the lane group does the rest
-  auto blocks_sum = [&](const float p[BPL]) -> float {
+  auto blocks_sum = [&](const float (&p)[BPL]) -> float {
     if (FULL) return group_sum<LPC2>(p[0]) + group_sum<LPC2>(p[1]);  // mirrored blocks: two butterflies, then the last stage
-    if (BPL == 2) return group_sum<LPC2>(p[0] + p[1]);
-    return group_sum<LPC2>((p[0] + p[1]) + (p[BPL == 4 ? 2 : 0] + p[BPL == 4 ? 3 : 1]));
+    return mcx::blocks_sum<LPC2, BPL>(p);
   };
 
   // every load of the chain state is awaited here, once (see k_fused_fast): no vmcnt wait may end up in the step loop
@@ -143,16 +125,7 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
   asm volatile("" ::"v"(ly));
   // 1/pwgt by scalar loads (constant address space): a plain global load would queue behind the sample stores
   const __attribute__((address_space(4))) float *wtab = (const __attribute__((address_space(4))) float *)a.winv;
-  // acceptance draw: Philox block (t >> 2) of the ACCEPT stream serves steps 4b..4b+3; lane q2 draws block b for
-  // b % LPC2 == q2, once per 4 * LPC2 steps
-  auto refresh = [&](uint32_t blk) {
-    if ((blk & ~(uint32_t)(LPC2 - 1)) != ablk) {
-      ablk = blk & ~(uint32_t)(LPC2 - 1);
-      const u32x4 aw = philox4x32_10(ablk + (uint32_t)q2, g, 0u, 0u, a.seed, ST_ACCEPT);
-      al01 = accept_lu_x2(aw.x, aw.y);
-      al23 = accept_lu_x2(aw.z, aw.w);
-    }
-  };
+  auto refresh = [&](uint32_t blk) { accept_refresh<LPC2>(blk, q2, g, a.seed, ablk, al01, al23); };
   auto step = [&](const int s, const float lu) {
     const uint32_t t = a.t0 + (uint32_t)s;
     f32x2 pe[BPL], po[BPL];
@@ -233,7 +206,6 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
     } else
 #endif
     if (LIK == LIK_MIX) {
-      // log sum_c w_c exp(-|x - m_c|^2 / 2) as a log-sum-exp (DualGaussian: src/rosenbrock.cc:63-78)
       const int K = a.ncomp;
       float e[8];
 #pragma unroll
@@ -242,55 +214,16 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
         if (c < K) {
           float s2[BPL];
 #pragma unroll
-          for (int b = 0; b < BPL; ++b) {
-            s2[b] = 0.0f;
-            if (live[b]) {
-              const float4 m = *reinterpret_cast<const float4 *>(&lds_means[c * d + kb[b]]);
-              const f32x2 ae = pe[b] - f32x2{m.x, m.z}, ao = po[b] - f32x2{m.y, m.w};
-              s2[b] = __builtin_fmaf(ae.x, ae.x, 0.0f);
-              s2[b] = __builtin_fmaf(ao.x, ao.x, s2[b]);
-              s2[b] = __builtin_fmaf(ae.y, ae.y, s2[b]);
-              s2[b] = __builtin_fmaf(ao.y, ao.y, s2[b]);
-            }
-          }
+          for (int b = 0; b < BPL; ++b) s2[b] = pk_mix_dist2(pe[b], po[b], &lds_means[c * d + kb[b]], live[b]);
           e[c] = __builtin_fmaf(-0.5f, blocks_sum(s2), lds_logw[c]);
         }
       }
-      float emax = e[0];
-#pragma unroll
-      for (int c = 1; c < 8; ++c)
-        if (c < K) emax = e[c] > emax ? e[c] : emax;
-      float ssum = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 8; c += 2) {  // exp two components at a time, add them in component order
-        if (c < K) {
-          const f32x2 ex = expf_v2x2(f32x2{e[c] - emax, e[c + 1] - emax});
-          ssum = ssum + ex.x;
-          if (c + 1 < K) ssum = ssum + ex.y;
-        }
-      }
-      lyt = emax + logf_v1(ssum);
+      lyt = mix_logsumexp(e, K);
     } else {
       float acc[BPL];
 #pragma unroll
-      for (int b = 0; b < BPL; ++b) {
-        acc[b] = 0.0f;
-        if (LIK == LIK_ROSEN1) {  // src/rosenbrock.cc:4-21 on the pairs (x0,x1), (x2,x3)
-          const f32x2 t1 = splat2(1.0f) - pe[b];
-          const f32x2 t2 = fma2(-pe[b], pe[b], po[b]);
-          const f32x2 term = fma2(splat2(100.0f) * t2, t2, t1 * t1);
-          if (live[b]) acc[b] = term.x + term.y;
-        } else {  // src/rosenbrock.cc:44-61: acc = fma((0.5 a) a, 1/sigma^2, acc) for k = 0..3 in order
-          const f32x2 ae = pe[b] - gme[b], ao = po[b] - gmo[b];
-          const f32x2 he = (splat2(0.5f) * ae) * ae, ho = (splat2(0.5f) * ao) * ao;
-          if (live[b]) {
-            acc[b] = __builtin_fmaf(he.x, gs[b][0], 0.0f);
-            acc[b] = __builtin_fmaf(ho.x, gs[b][1], acc[b]);
-            acc[b] = __builtin_fmaf(he.y, gs[b][2], acc[b]);
-            acc[b] = __builtin_fmaf(ho.y, gs[b][3], acc[b]);
-          }
-        }
-      }
+      for (int b = 0; b < BPL; ++b)
+        acc[b] = LIK == LIK_ROSEN1 ? pk_rosen1(pe[b], po[b], live[b]) : pk_gauss(pe[b], po[b], gme[b], gmo[b], gs[b], live[b]);
       lyt = 0.0f - blocks_sum(acc);
     }
     // src/mcpar.cc:62-75 (cfac = 1 for local proposals): log u < ly' - ly
@@ -306,29 +239,17 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
     if (MAIN) {
       const f32x2 w2 = splat2(wtab[a.isamp0 + s]);  // src/mcpar.cc:186-187
 #pragma unroll
-      for (int b = 0; b < BPL; ++b) {
-        const f32x2 de = xe[b] - me[b], dO = xo[b] - mo[b];  // src/mcpar.cc:199-202
-        me[b] = fma2(de, w2, me[b]);
-        mo[b] = fma2(dO, w2, mo[b]);
-        se[b] = fma2(de, xe[b] - me[b], se[b]);
-        so[b] = fma2(dO, xo[b] - mo[b], so[b]);
-      }
-      if (s == a.snap_after) {  // snapshot for the next exchange (src/mcpar.cc:202-208)
+      for (int b = 0; b < BPL; ++b) pk_welford(xe[b], xo[b], w2, me[b], mo[b], se[b], so[b]);
+      if (s == a.snap_after) {
 #pragma unroll
         for (int b = 0; b < BPL; ++b)
-          if (live[b]) {
-            const f32x2 ve = se[b] * w2, vo = so[b] * w2;
-            float4 *slot = reinterpret_cast<float4 *>(a.musig_own + 2 * offb[b]);
-            slot[0] = make_float4(me[b].x, ve.x, mo[b].x, vo.x);
-            slot[1] = make_float4(me[b].y, ve.y, mo[b].y, vo.y);
-            if (a.sig_out) *reinterpret_cast<float4 *>(a.sig_out + offb[b]) = make_float4(ve.x, vo.x, ve.y, vo.y);
-          }
+          if (live[b]) pk_snapshot(se[b], so[b], w2, a.musig_own, a.sig_out, offb[b], me[b], mo[b]);
       }
       if (sx) {  // src/mcpar.cc:177-182
         if (a.samp_stride <= 1) {
 #pragma unroll
           for (int b = 0; b < BPL; ++b)
-            if (live[b]) *reinterpret_cast<float4 *>(sx + rowk[b]) = make_float4(xe[b].x, xo[b].x, xe[b].y, xo[b].y);
+            if (live[b]) pk_store(sx + rowk[b], xe[b], xo[b]);
           if (q2 == 0) *sl = ly;
           sx += sx_stride;
           sl += sl_stride;
@@ -336,7 +257,7 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
           const size_t row = (size_t)((a.isamp0 + s) / a.samp_stride);
 #pragma unroll
           for (int b = 0; b < BPL; ++b)
-            if (live[b]) *reinterpret_cast<float4 *>(sx + row * sx_stride + rowk[b]) = make_float4(xe[b].x, xo[b].x, xe[b].y, xo[b].y);
+            if (live[b]) pk_store(sx + row * sx_stride + rowk[b], xe[b], xo[b]);
           if (q2 == 0) sl[row * sl_stride] = ly;
         }
       }
@@ -345,12 +266,9 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
   auto one_step = [&](const int s) {
     const uint32_t t = a.t0 + (uint32_t)s, blk = t >> 2;
     refresh(blk);
-    const uint32_t wi = t & 3u;
-    const float mine = wi == 0u ? al01.x : (wi == 1u ? al01.y : (wi == 2u ? al23.x : al23.y));
-    step(s, as_f32(group_bcast<LPC2>(as_u32(mine), blk & (uint32_t)(LPC2 - 1), q2)));
+    step(s, as_f32(group_bcast<LPC2>(as_u32(accept_word(&al01, &al23, t & 3u)), blk & (uint32_t)(LPC2 - 1), q2)));
   };
   int s = 0;
-#if MCX_FAST_UNROLL4
   // (four steps per iteration from an aligned step on: k_fused_fast's driver loop, mcx_device.hpp)
   for (; s < a.nsteps && ((a.t0 + (uint32_t)s) & 3u); ++s) one_step(s);
   for (; s + 4 <= a.nsteps; s += 4) {
@@ -362,16 +280,15 @@ __device__ __forceinline__ uint32_t fused_fastb_body(const SegArgs &a)
 #pragma unroll
     for (int u = 0; u < 4; ++u) step(s + u, lu4[u]);
   }
-#endif
   for (; s < a.nsteps; ++s) one_step(s);
 
 #pragma unroll
   for (int b = 0; b < BPL; ++b)
     if (live[b]) {
-      *reinterpret_cast<float4 *>(a.x + offb[b]) = make_float4(xe[b].x, xo[b].x, xe[b].y, xo[b].y);
+      pk_store(a.x + offb[b], xe[b], xo[b]);
       if (MAIN) {
-        *reinterpret_cast<float4 *>(a.mu + offb[b]) = make_float4(me[b].x, mo[b].x, me[b].y, mo[b].y);
-        *reinterpret_cast<float4 *>(a.psum2 + offb[b]) = make_float4(se[b].x, so[b].x, se[b].y, so[b].y);
+        pk_store(a.mu + offb[b], me[b], mo[b]);
+        pk_store(a.psum2 + offb[b], se[b], so[b]);
       }
     }
   if (q2 == 0) {

@@ -46,13 +46,6 @@
 #pragma once
 #include "mcx_device.hpp"
 
-// How an abandoned tuner meeting is handled inside the step loop (an A/B switch for tools/meet_ab.sh; 2 ships):
-//   0  meetings wait without a bound (round 2; not safe -- measurement only)
-//   2  bounded wait; after an abandoned meeting the owner goes on to the end of its phase with a zero count
-#ifndef MCX_MEET_VARIANT
-#define MCX_MEET_VARIANT 2
-#endif
-
 namespace mcx {
 
 constexpr int PBLOCK = 1024;          // 16 wavefronts: 4 per SIMD of one CU
@@ -168,7 +161,6 @@ __device__ __forceinline__ unsigned long long owners_meet(unsigned long long *le
       arr = __builtin_amdgcn_readfirstlane(arr);
       abort = __ballot((v & MEET_ABORT_BIT) != 0ull) != 0ull;
       if ((int)arr >= nwg || abort) break;
-#if MCX_MEET_VARIANT != 0
       if ((++polls & 63u) == 0u) {
         const unsigned long long now = __builtin_amdgcn_s_memrealtime();
         if (t_start == 0) t_start = now;
@@ -181,7 +173,6 @@ __device__ __forceinline__ unsigned long long owners_meet(unsigned long long *le
           break;
         }
       }
-#endif
       __builtin_amdgcn_s_sleep(2);
     }
     sum += (unsigned)__builtin_amdgcn_update_dpp(0, (int)sum, 0x128, 0xF, 0xF, true);
@@ -233,11 +224,7 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
   __shared__ unsigned lds_sum, lds_cnt, lds_abort;
   __shared__ unsigned long long lds_out[PEVENTS];  // one result word per tuner event (never reused within a launch)
   __shared__ float wbuf[4 * PKMAX];  // 1/pwgt of a phase's main-loop steps, by phase % 4 (written 1 ahead, read 1 behind)
-  if (LIK == LIK_MIX) {
-    const int kd = a.ncomp * a.d;
-    for (int i = threadIdx.x; i < kd; i += PBLOCK) lds_means[i] = a.lik[i];
-    if (threadIdx.x < (unsigned)a.ncomp) lds_logw[threadIdx.x] = a.lik[kd + threadIdx.x];
-  }
+  if (LIK == LIK_MIX) stage_mixture<PBLOCK>(lds_means, lds_logw, a.lik, a.ncomp, a.d);
   if (threadIdx.x == 0) { lds_sum = 0; lds_cnt = 0; lds_abort = 0; }
   if (threadIdx.x < PEVENTS) lds_out[threadIdx.x] = ~0ull;
   constexpr bool NEGSUM = LIK == LIK_ROSEN1 || LIK == LIK_GAUSS;  // (see loglike)
@@ -349,22 +336,11 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
     gs[b][0] = gs[b][1] = gs[b][2] = gs[b][3] = 0.0f;
     const int kb = k0 + 4 * b;
     if (live && owner) {
-      const float4 f = *reinterpret_cast<const float4 *>((a.x0 ? a.x0 : a.x) + off + 4 * b);
-      xe[b] = f32x2{f.x, f.z}; xo[b] = f32x2{f.y, f.w};
-      const float *Tsrc = a.T0 ? a.T0 : a.T;
-      te[b] = f32x2{Tsrc[(kb + 0) * d + kb + 0], Tsrc[(kb + 2) * d + kb + 2]};
-      to[b] = f32x2{Tsrc[(kb + 1) * d + kb + 1], Tsrc[(kb + 3) * d + kb + 3]};
-      if (LIK == LIK_GAUSS) {
-        gme[b] = f32x2{a.lik[kb + 0], a.lik[kb + 2]}; gmo[b] = f32x2{a.lik[kb + 1], a.lik[kb + 3]};
-        gs[b][0] = a.lik[d + kb + 0]; gs[b][1] = a.lik[d + kb + 1]; gs[b][2] = a.lik[d + kb + 2]; gs[b][3] = a.lik[d + kb + 3];
-      }
+      pk_load((a.x0 ? a.x0 : a.x) + off + 4 * b, xe[b], xo[b]);
+      pk_load_tdiag(a.T0 ? a.T0 : a.T, d, kb, te[b], to[b]);
+      if (LIK == LIK_GAUSS) pk_load_gauss(a.lik, d, kb, gme[b], gmo[b], gs[b]);
     }
-    if (live && (REC ? recorder : owner) && a.nmain > 0 && !a.init_moments) {
-      const float4 m = *reinterpret_cast<const float4 *>(a.mu + off + 4 * b);
-      const float4 p = *reinterpret_cast<const float4 *>(a.psum2 + off + 4 * b);
-      me[b] = f32x2{m.x, m.z}; mo[b] = f32x2{m.y, m.w};
-      se[b] = f32x2{p.x, p.z}; so[b] = f32x2{p.y, p.w};
-    }
+    if (live && (REC ? recorder : owner) && a.nmain > 0 && !a.init_moments) pk_load_moments(a.mu, a.psum2, off + 4 * b, me[b], mo[b], se[b], so[b]);
   }
   // owner lanes that hold no chain never accept: log u < ly' - (+inf) is false for every ly'
   if (mine && owner && !a.x0) ly = a.ly[chain];
@@ -391,13 +367,6 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
   };
   auto wave_accepts = [&](uint32_t mark) -> uint32_t { return wave_sum_chains(cnt - mark); };
 
-  // the first log2(BPL) stages of the butterfly over the block index, inside the lane; the lane group does the rest
-  auto blocks_sum = [&](const float p[BPL]) -> float {
-    if (BPL == 1) return group_sum<LPC2>(p[0]);
-    if (BPL == 2) return group_sum<LPC2>(p[0] + p[BPL > 1 ? 1 : 0]);
-    return group_sum<LPC2>((p[0] + p[BPL > 1 ? 1 : 0]) + (p[BPL == 4 ? 2 : 0] + p[BPL == 4 ? 3 : 0]));
-  };
-
   // likelihood of the proposal (pe, po), same arithmetic as k_fused_fast
   auto loglike = [&](const f32x2 pe[BPL], const f32x2 po[BPL]) -> float {
 #ifdef MCX_USER_LIK
@@ -408,7 +377,7 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
         const float xb[4] = {pe[b].x, po[b].x, pe[b].y, po[b].y};
         acc[b] = live ? ::mcx_user_block(xb, 4, k0 + 4 * b, d, a.lik) : 0.0f;
       }
-      return ::mcx_user_finish(blocks_sum(acc), d, a.lik);
+      return ::mcx_user_finish(blocks_sum<LPC2, BPL>(acc), d, a.lik);
     }
 #endif
     if (LIK == LIK_MIX) {
@@ -420,63 +389,27 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
         if (c < Kc) {
           float s2[BPL];
 #pragma unroll
-          for (int b = 0; b < BPL; ++b) {
-            s2[b] = 0.0f;
-            if (live) {
-              const float4 m = *reinterpret_cast<const float4 *>(&lds_means[c * d + k0 + 4 * b]);
-              const f32x2 ae = pe[b] - f32x2{m.x, m.z}, ao = po[b] - f32x2{m.y, m.w};
-              s2[b] = __builtin_fmaf(ae.x, ae.x, 0.0f);
-              s2[b] = __builtin_fmaf(ao.x, ao.x, s2[b]);
-              s2[b] = __builtin_fmaf(ae.y, ae.y, s2[b]);
-              s2[b] = __builtin_fmaf(ao.y, ao.y, s2[b]);
-            }
-          }
-          e[c] = __builtin_fmaf(-0.5f, blocks_sum(s2), lds_logw[c]);
+          for (int b = 0; b < BPL; ++b) s2[b] = pk_mix_dist2(pe[b], po[b], &lds_means[c * d + k0 + 4 * b], live);
+          e[c] = __builtin_fmaf(-0.5f, blocks_sum<LPC2, BPL>(s2), lds_logw[c]);
         }
       }
-      float emax = e[0];
-#pragma unroll
-      for (int c = 1; c < 8; ++c)
-        if (c < Kc) emax = e[c] > emax ? e[c] : emax;
-      float ssum = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 8; c += 2) {
-        if (c < Kc) {
-          const f32x2 ex = expf_v2x2(f32x2{e[c] - emax, e[c + 1] - emax});
-          ssum = ssum + ex.x;
-          if (c + 1 < Kc) ssum = ssum + ex.y;
-        }
-      }
-      return emax + logf_v1(ssum);
+      return mix_logsumexp(e, Kc);
     }
     float acc[BPL];
 #pragma unroll
     for (int b = 0; b < BPL; ++b) {
       acc[b] = 0.0f;
-      if (LIK == LIK_ROSEN1) {
-        const f32x2 t1 = splat2(1.0f) - pe[b];
-        const f32x2 t2 = fma2(-pe[b], pe[b], po[b]);
-        const f32x2 term = fma2(splat2(100.0f) * t2, t2, t1 * t1);
-        // (the select stays: a lane without parameters is never dealt normals, its slots of zbuf hold whatever LDS held, and
-        // 0 x inf is a NaN.  Parking such lanes at x = 1, T = 0 -- term +0 by itself -- needs the slots zeroed once per launch,
-        // which costs 6 us of a 0.36 ms job: more than the select)
-        if (live) acc[b] = term.x + term.y;
-      } else if (LIK == LIK_GAUSS) {
-        const f32x2 ae = pe[b] - gme[b], ao = po[b] - gmo[b];
-        const f32x2 he = (splat2(0.5f) * ae) * ae, ho = (splat2(0.5f) * ao) * ao;
-        if (live) {
-          acc[b] = __builtin_fmaf(he.x, gs[b][0], 0.0f);
-          acc[b] = __builtin_fmaf(ho.x, gs[b][1], acc[b]);
-          acc[b] = __builtin_fmaf(he.y, gs[b][2], acc[b]);
-          acc[b] = __builtin_fmaf(ho.y, gs[b][3], acc[b]);
-        }
-      }
+      // (`live` stays in the Rosenbrock partial: a lane without parameters is never dealt normals, its slots of zbuf hold
+      // whatever LDS held, and 0 x inf is a NaN.  Parking such lanes at x = 1, T = 0 -- term +0 by itself -- needs the slots
+      // zeroed once per launch, which costs 6 us of a 0.36 ms job: more than the select)
+      if (LIK == LIK_ROSEN1) acc[b] = pk_rosen1(pe[b], po[b], live);
+      else if (LIK == LIK_GAUSS) acc[b] = pk_gauss(pe[b], po[b], gme[b], gmo[b], gs[b], live);
     }
     // Rosenbrock1 / Gaussian (NEGSUM): the sum S itself, L = 0 - S.  The owners keep S_cur = -ly instead of ly: the test
     // log u < ly' - ly is log u < S_cur - S' -- the same difference, rounded once either way -- and the negation leaves
     // the step loop, where every instruction costs this lone wavefront 5.7 cycles: ly = 0 - S_cur where it is wanted
-    if (NEGSUM) return blocks_sum(acc);
-    return 0.0f - blocks_sum(acc);
+    if (NEGSUM) return blocks_sum<LPC2, BPL>(acc);
+    return 0.0f - blocks_sum<LPC2, BPL>(acc);
   };
 
   __syncthreads();  // the mixture's means and log-weights are staged
@@ -514,28 +447,17 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
   // Welford (src/mcpar.cc:184-209), the exchange snapshot (:202-208) and the sample emission (:177-182) of one main-loop
   // step, from the post-step state (ce, co, lyv): the recorder's work, or the owner's when there are no recorders
   auto record = [&](const f32x2 ce[BPL], const f32x2 co[BPL], float lyv, float w, bool snap) {
-    const f32x2 w2 = splat2(w);  // 1/pwgt, src/mcpar.cc:186-187
+    const f32x2 w2 = splat2(w);
 #pragma unroll
-    for (int b = 0; b < BPL; ++b) {
-      const f32x2 de = ce[b] - me[b], dO = co[b] - mo[b];  // src/mcpar.cc:199-202
-      me[b] = fma2(de, w2, me[b]);
-      mo[b] = fma2(dO, w2, mo[b]);
-      se[b] = fma2(de, ce[b] - me[b], se[b]);
-      so[b] = fma2(dO, co[b] - mo[b], so[b]);
-    }
-    if (snap && live) {  // snapshot for the next exchange (src/mcpar.cc:202-208)
+    for (int b = 0; b < BPL; ++b) pk_welford(ce[b], co[b], w2, me[b], mo[b], se[b], so[b]);
+    if (snap && live) {
 #pragma unroll
-      for (int b = 0; b < BPL; ++b) {
-        const f32x2 ve = se[b] * w2, vo = so[b] * w2;
-        float4 *slot = reinterpret_cast<float4 *>(a.musig_own + 2 * (off + 4 * b));
-        slot[0] = make_float4(me[b].x, ve.x, mo[b].x, vo.x);
-        slot[1] = make_float4(me[b].y, ve.y, mo[b].y, vo.y);
-      }
+      for (int b = 0; b < BPL; ++b) pk_snapshot(se[b], so[b], w2, a.musig_own, nullptr, off + 4 * b, me[b], mo[b]);
     }
     if (emit) {  // src/mcpar.cc:177-182
       if (kmod == 0) {
 #pragma unroll
-        for (int b = 0; b < BPL; ++b) *reinterpret_cast<float4 *>(sxv + 4 * b) = make_float4(ce[b].x, co[b].x, ce[b].y, co[b].y);
+        for (int b = 0; b < BPL; ++b) pk_store(sxv + 4 * b, ce[b], co[b]);
         *slv = lyv;  // every lane of the chain stores the same value
         sxv += sxs;
         slv += sls;
@@ -650,10 +572,6 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
             }
             const uint32_t wacc = wave_accepts(cnt_mark);
             cnt_mark = cnt;
-#if MCX_MEET_VARIANT == 0
-            const unsigned long long seg = owners_meet(a.bar + (size_t)nevent * PLEAVES, wacc, own_here, nwg, &lds_sum, &lds_cnt, &lds_out[nevent],
-                                                       a.meet_timeout);
-#else
             // An abandoned meeting (wave-uniform) does not cut the phase short: the wave goes on with a count of zero,
             // skips later meetings, and the flag makes the launch skip its epilogue; what an abandoned launch may have
             // dirtied on the way (sample rows, the slot snapshot, trace[]) is listed at the top of this file.
@@ -669,7 +587,6 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
                 seg = 0;
               }
             }
-#endif
             ++nevent;
             tun_na += seg;
             tun_nt += (unsigned long long)steps * (unsigned long long)a.n;
@@ -792,7 +709,7 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
 #pragma unroll
       for (int b = 0; b < BPL; ++b) {
         const int kb = k0 + 4 * b;
-        *reinterpret_cast<float4 *>(a.x + off + 4 * b) = make_float4(xe[b].x, xo[b].x, xe[b].y, xo[b].y);
+        pk_store(a.x + off + 4 * b, xe[b], xo[b]);
         if ((a.nburn > 0 || a.T0) && chain == 0) {  // the (rescaled) diagonal; off-diagonal entries are zero on this path
           a.T[(kb + 0) * d + kb + 0] = te[b].x; a.T[(kb + 2) * d + kb + 2] = te[b].y;
           a.T[(kb + 1) * d + kb + 1] = to[b].x; a.T[(kb + 3) * d + kb + 3] = to[b].y;
@@ -812,15 +729,9 @@ __device__ __forceinline__ void run_small_body(const RunArgs &a)
     const f32x2 w2 = splat2(a.winv[a.isamp0 + a.nmain - 1]);
 #pragma unroll
     for (int b = 0; b < BPL; ++b) {
-      *reinterpret_cast<float4 *>(a.mu + off + 4 * b) = make_float4(me[b].x, mo[b].x, me[b].y, mo[b].y);
-      *reinterpret_cast<float4 *>(a.psum2 + off + 4 * b) = make_float4(se[b].x, so[b].x, se[b].y, so[b].y);
-      if (a.final_publish) {  // src/mcpar.cc:202-208 after the last step
-        const f32x2 ve = se[b] * w2, vo = so[b] * w2;
-        *reinterpret_cast<float4 *>(a.sig + off + 4 * b) = make_float4(ve.x, vo.x, ve.y, vo.y);
-        float4 *slot = reinterpret_cast<float4 *>(a.musig_own + 2 * (off + 4 * b));
-        slot[0] = make_float4(me[b].x, ve.x, mo[b].x, vo.x);
-        slot[1] = make_float4(me[b].y, ve.y, mo[b].y, vo.y);
-      }
+      pk_store(a.mu + off + 4 * b, me[b], mo[b]);
+      pk_store(a.psum2 + off + 4 * b, se[b], so[b]);
+      if (a.final_publish) pk_snapshot(se[b], so[b], w2, a.musig_own, a.sig, off + 4 * b, me[b], mo[b]);  // after the last step
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {

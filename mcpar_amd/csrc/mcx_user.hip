@@ -73,11 +73,11 @@ int rtc_compile(const std::string &src, const char *name, const std::vector<std:
   if (!rtc_load()) return fail(MCX_ERR_UNSUPPORTED, "run-time compilation unavailable: %s", g_rtc.why.c_str());
   // (a user's text may well start with #include <hip/hip_runtime.h>: hiprtc has the runtime's declarations built in and no
   // such file, so an empty one stands in)
-  const char *hn[] = {"mcx_numerics.hpp", "mcx_device.hpp", "mcx_fastb.hpp", "mcx_persist.hpp", "hip/hip_runtime.h"};
-  const char *hs[] = {k_hdr_mcx_numerics, k_hdr_mcx_device, k_hdr_mcx_fastb, k_hdr_mcx_persist,
+  const char *hn[] = {"mcx_numerics.hpp", "mcx_block.hpp", "mcx_device.hpp", "mcx_fastb.hpp", "mcx_persist.hpp", "hip/hip_runtime.h"};
+  const char *hs[] = {k_hdr_mcx_numerics, k_hdr_mcx_block, k_hdr_mcx_device, k_hdr_mcx_fastb, k_hdr_mcx_persist,
                       "// the HIP runtime declarations are built into hiprtc\n"};
   rtcProgram prog = nullptr;
-  int r = g_rtc.CreateProgram(&prog, src.c_str(), name, 5, hs, hn);
+  int r = g_rtc.CreateProgram(&prog, src.c_str(), name, 6, hs, hn);
   if (r != 0) return fail(MCX_ERR_HIP, "hiprtcCreateProgram: %s", g_rtc.GetErrorString(r));
   std::vector<const char *> opts(std::begin(RTC_FLAGS), std::end(RTC_FLAGS));
   for (const std::string &d : defs) opts.push_back(d.c_str());

@@ -1,7 +1,7 @@
 """Codegen guard of the hot-path kernel (no GPU): the four-steps-per-iteration loop of k_fused_fast<4, MAIN, Rosenbrock1>
 -- the headline job's main-loop and burn-in kernels -- compiled for gfx950 with the Makefile's flags holds no exec-mask
 region but the acceptance's, one per step (sample rows stored by every lane, the snapshot outside the step; the
-acceptance stays a branch because it timed faster than selects: mcx_device.hpp, MCX_TAKE_SELECT), and few VGPR copies."""
+acceptance stays a branch because it timed faster than selects: the comment at the acceptance in mcx_device.hpp), and few VGPR copies."""
 import importlib.util
 import os
 import shutil

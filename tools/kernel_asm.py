@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Compile the translation units of libmcx with -save-temps and summarise one kernel: registers and the instruction
 mix of its biggest loop.  usage: tools/kernel_asm.py <mangled-name-substring> [--dump]
+       tools/kernel_asm.py --compare DIR_A DIR_B: two sets of <unit>.s files (hipcc <Makefile's flags> --cuda-device-only -S),
+       kernel by kernel: how many instruction streams are the same, and size / registers / LDS / scratch / occupancy of the rest
 
 The biggest loop is the biggest INNERMOST one (a backward branch whose span holds no other): the hot kernels' step
 loops sit inside an outer loop of passes (k_fused_fast's snapshot split), and the outer one would count the prologue and
@@ -71,7 +73,52 @@ def loop_ops(body, loop):
     return ops, vcopies
 
 
+STEP_UNITS = ("mcx_k_fast", "mcx_k_fast_full", "mcx_k_fastb", "mcx_k_fastb_full", "mcx_k_pregen", "mcx_k_generic_burn",
+              "mcx_k_generic_main", "mcx_k_persist")
+
+
+KEYS = ("NumVgprs", "TotalNumSgprs", "LDSByteSize", "ScratchSize", "Occupancy")
+
+
+def instruction_stream(body):
+    """the instructions alone: no comments, directives or blank lines, every .LBB label one token"""
+    out = []
+    for l in body[1:]:
+        l = re.sub(r"\.LBB\d+_\d+", ".LBB", l.split(";")[0].strip())
+        if l and (not l.startswith(".") or l.startswith(".LBB")):
+            out.append(l)
+    return out
+
+
+def compare(dir_a, dir_b):
+    """one markdown table per translation unit; returns the number of kernels with new scratch or lower occupancy"""
+    bad = 0
+    for tu in STEP_UNITS:
+        a, b = (open(os.path.join(d, tu + ".s")).read() for d in (dir_a, dir_b))
+        names = re.findall(r"\.amdhsa_kernel (\w+)", a)
+        assert names == re.findall(r"\.amdhsa_kernel (\w+)", b), tu + ": the two sets hold different kernels"
+        rows = []
+        for n in names:
+            sa, sb = instruction_stream(kernel_body(a, n)), instruction_stream(kernel_body(b, n))
+            if sa == sb:
+                continue
+            # (the resource comments that follow the kernel's code)
+            ma, mb = ({k: re.search("; %s: (\\d+)" % k, t[t.index("\n" + n + ":"):]).group(1) for k in KEYS} for t in (a, b))
+            flag = (ma["ScratchSize"] == "0" and mb["ScratchSize"] != "0") or int(mb["Occupancy"]) < int(ma["Occupancy"])
+            bad += flag
+            demangled = subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip() or n
+            rows.append("| `%s` | %d → %d | %s |%s" % (re.sub(r"^void mcx::|\(.*$", "", demangled), len(sa), len(sb),
+                                                     " | ".join("%s → %s" % (ma[k], mb[k]) for k in KEYS), " **worse**" if flag else ""))
+        print("\n`%s`: %d of %d kernels instruction-identical\n" % (tu, len(names) - len(rows), len(names)))
+        if rows:
+            print("| kernel | instructions | VGPRs | SGPRs | LDS bytes | scratch bytes | occupancy |\n|---|---|---|---|---|---|---|")
+            print("\n".join(rows))
+    return bad
+
+
 def main():
+    if sys.argv[1] == "--compare":
+        return 1 if compare(sys.argv[2], sys.argv[3]) else 0
     pat = sys.argv[1]
     s = ""
     for tu in ("mcx_k_fast", "mcx_k_fast_full", "mcx_k_fastb", "mcx_k_fastb_full", "mcx_k_pregen", "mcx_k_generic_main", "mcx_k_generic_burn", "mcx_engine"):
@@ -97,4 +144,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""A/B of the one-launch small-n kernel's meeting logic on ONE box: the libraries tools/meet_ab.sh
-built (build/ab/libmcx_v{0,1,2}.so) time the same jobs in turn, several rounds, each in a process of its own
-(MCX_LIBMCX picks the library).  Prints the job time and the kernel's own time (HIP events, MCX_OPT_PROFILE) per variant."""
+"""A/B of the one-launch small-n kernel on ONE box: builds of libmcx.so, given as paths, time the same jobs in turn
+(A B A B ...), several rounds, each run in a process of its own (MCX_LIBMCX picks the library).  Prints the job time and the
+kernel's own time (HIP events, MCX_OPT_PROFILE) per library, and for every library after the first whether its median job
+time stays within the first one's median plus the spread (max - min) of the first one's own repeats.
+usage: tools/persist_ab.py ROUNDS LIB_A LIB_B [LIB_C ...]"""
 import json
 import os
 import subprocess
@@ -44,13 +46,14 @@ print(json.dumps(out))
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    variants = sys.argv[2:] or ["r3", "v0", "v2"]  # build/ab/libmcx_<name>.so: round 3's library, unbounded meetings, what ships
+    if len(sys.argv) < 4:
+        print(__doc__)
+        return 2
+    rounds, variants = int(sys.argv[1]), [os.path.abspath(v) for v in sys.argv[2:]]
     res = {}
     for r in range(rounds):
         for v in variants:
-            lib = os.path.join(ROOT, "build", "ab", "libmcx_%s.so" % v)
-            env = dict(os.environ, MCX_LIBMCX=lib)
+            env = dict(os.environ, MCX_LIBMCX=v)
             o = subprocess.run([sys.executable, "-c", CHILD], env=env, capture_output=True, text=True, timeout=600)
             if o.returncode != 0:
                 print("variant %s failed:\n%s" % (v, o.stderr[-2000:]))
@@ -59,9 +62,14 @@ def main():
             for k, val in got.items():
                 res.setdefault(k, {}).setdefault(v, []).append(val)
             print("round %d variant %s: %s" % (r, v, got), flush=True)
-    print("\nshape: variant -> min job ms / min kernel ms over %d rounds" % rounds)
+    print("\nshape: library -> job ms median (min .. max) / kernel ms median over %d rounds" % rounds)
+    med = lambda xs: sorted(xs)[len(xs) // 2] if len(xs) % 2 else 0.5 * (sorted(xs)[len(xs) // 2 - 1] + sorted(xs)[len(xs) // 2])
     for k, byv in res.items():
-        print(k, {v: (min(x[0] for x in xs), min(x[1] for x in xs)) for v, xs in byv.items()})
+        ref = [x[0] for x in byv[variants[0]]]
+        for v, xs in byv.items():
+            job = [x[0] for x in xs]
+            verdict = "" if v == variants[0] else ("  within" if med(job) <= med(ref) + (max(ref) - min(ref)) else "  SLOWER") + " (first + spread)"
+            print("%s %s: job %.4f (%.4f .. %.4f) kernel %.4f%s" % (k, v, med(job), min(job), max(job), med([x[1] for x in xs]), verdict))
     return 0
 
 
