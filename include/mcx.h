@@ -546,6 +546,10 @@ int mcx_debug_summary_finish(int n, int M, double mean, double var_all, double v
                              mcx_col_summary *col, double *quantiles, int *need_lags);
 /* mcx_samples_summary without quantiles, reporting the number of 32-lag autocovariance windows it computed */
 int mcx_debug_summary_windows(mcx_engine *e, int first_step, int nsteps, int *nwin);
+/* host only, no device: one digit of mcx_samples_summary's radix select for one target.  hist[256] counts, by their next 8
+ * bits, the keys under the prefix found so far; rem is the target's rank among them.  *digit = the bucket that holds it (the
+ * walk stops at 255 whatever the counts say), *rem_out = its rank within that bucket. */
+int mcx_debug_select_step(const unsigned long long hist[256], long long rem, int *digit, long long *rem_out);
 /* the autocovariance sums of mcx_rows_summary's device passes, for tests: the same kernels and launches, but every finite
  * column takes lag windows until it holds nlags lags (1 <= nlags <= n) instead of stopping where its Geyer loop does.
  * acov[(np + 1) * nlags], row = column: sum over the M half-chains of sum_{i<n-t} c_i c_{i+t}, c = the half-chain centred

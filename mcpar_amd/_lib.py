@@ -98,6 +98,7 @@ def load():
         "mcx_debug_summary_finish": [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.c_int, fp,
                                      C.c_longlong, dp, C.c_int, C.c_int, vp, dp, C.POINTER(C.c_int)],
         "mcx_debug_summary_windows": [vp, C.c_int, C.c_int, C.POINTER(C.c_int)],
+        "mcx_debug_select_step": [C.POINTER(C.c_ulonglong), C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_longlong)],
         "mcx_debug_rows_acov": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp],
         "mcx_samples_covariance": [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int)],
         "mcx_rows_covariance": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int)],

@@ -110,33 +110,40 @@ __global__ void __launch_bounds__(SB) k_cov_tiles(const float *x, const float *l
 
 static_assert(CWAVES == 4, "k_cov_tiles adds four wavefronts");
 
-// mean, covariance and flags of x[T][nc][np], ly[T][nc] (device) on stream st.  ms (mcx_debug_covariance_times): HIP events
-// around the passes -> ms[0] k_sum_moments, ms[1] k_cov_tiles, ms[2] the reducer of its partials
-static int covariance_device(hipStream_t st, DevBuf<double> *buf, const float *x, const float *ly, int nc, int np, int64_t T,
-                             double *mean, double *cov, int *flags, double *ms = nullptr)
+// the matrix from the reduced sums out (k_cov_tiles' row layout): the upper triangle as computed, mirrored; NaN in the row
+// and column of a column that is not finite
+static void cov_matrix(const std::vector<double> &out, const std::vector<char> &fin, int np, double dof, double *cov)
 {
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard {
-    hipEvent_t *ev;
-    ~EvGuard()
-    {
-      for (int k = 0; k < 6; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    }
-  } guard{ev};
-  if (ms)
-    for (int k = 0; k < 6; ++k) HIPCHK(hipEventCreate(&ev[k]));
-  auto mark = [&](int k) -> int {
-    if (ms) HIPCHK(hipEventRecord(ev[k], st));
-    return MCX_OK;
-  };
   const int ncol = np + 1, nt = (np + CTILE - 1) / CTILE, npairs = nt * (nt + 1) / 2;
-  const size_t N = (size_t)T * nc;
+  auto put = [&](int i, int j, double s) {
+    const double v = fin[i] && fin[j] ? s / dof : std::numeric_limits<double>::quiet_NaN();
+    cov[(size_t)i * ncol + j] = v;
+    cov[(size_t)j * ncol + i] = v;
+  };
+  int off = nt;
+  for (int ti = 0; ti < nt; ++ti)
+    for (int tj = ti; tj < nt; ++tj) {
+      const int pair = ti == tj ? ti : off++;
+      for (int i = 0; i < CTILE && ti * CTILE + i < np; ++i)
+        for (int j = ti == tj ? i : 0; j < CTILE && tj * CTILE + j < np; ++j)
+          put(ti * CTILE + i, tj * CTILE + j, out[(size_t)pair * CENT + i * CTILE + j]);
+    }
+  for (int c = 0; c < np; ++c) put(c, np, out[(size_t)npairs * CENT + c]);
+  put(np, np, out[(size_t)npairs * CENT + (size_t)nt * CTILE]);
+}
+
+// mean, covariance and flags of a view on stream st.  ms (mcx_debug_covariance_times, else NULL): ms[0] k_sum_moments,
+// ms[1] k_cov_tiles, ms[2] the reducer of its partials; the column sums and the host round trip between them are not timed
+static int covariance_device(hipStream_t st, DevBuf<double> *buf, const StoreView &v, double *mean, double *cov, int *flags,
+                             double *ms)
+{
+  StageTimer tm{st, ms, 3, {}};
+  const int nc = v.nc, np = v.np, ncol = v.ncol, nt = (np + CTILE - 1) / CTILE, npairs = nt * (nt + 1) / 2;
+  const size_t N = (size_t)v.N;
   // workgroups over the rows: a function of N and np alone (the partials' order is part of the result's bytes)
   const size_t nwg_max = std::max<size_t>(128, 2048 / (size_t)npairs);
   const size_t rpw = ((N + nwg_max - 1) / nwg_max + CROWS - 1) / CROWS * CROWS, nwg = (N + rpw - 1) / rpw;
   const size_t R = (size_t)npairs * CENT + (size_t)nt * CTILE + 1;
-  const TileSet tx = tiles_x(x, nc, np), tl = tiles_l(ly, nc, np);
   // device double scratch: hm[ncol][2][nc] | tot[ncol][nc] | colsum[ncol] | centre[ncol] | part[R][nwg] | out[R]
   const size_t o_hm = 0, o_tot = o_hm + (size_t)ncol * 2 * nc, o_cs = o_tot + (size_t)ncol * nc, o_ctr = o_cs + ncol,
                o_part = o_ctr + ncol, o_out = o_part + R * nwg, nd = o_out + R;
@@ -144,15 +151,8 @@ static int covariance_device(hipStream_t st, DevBuf<double> *buf, const float *x
   double *D = buf->p;
 
   // ---- 1. column sums -> mean (the expression of mcx_samples_summary), flags
-  MCXCHK(mark(0));
-  for (const TileSet *t : {&tx, &tl}) {
-    hipLaunchKernelGGL(k_sum_moments, dim3((unsigned)(t->nbc * t->ntiles)), dim3(SB), 0, st, *t, nc, T, T / 2, D + o_hm, D + o_tot);
-    HIPCHK(hipGetLastError());
-  }
-  MCXCHK(mark(1));
-  hipLaunchKernelGGL(k_sum_rows, dim3((unsigned)ncol), dim3(SB), 0, st, D + o_tot, (size_t)nc, 1, ncol, np, (size_t)nc, (size_t)nc,
-                     (const double *)nullptr, 0.0, D + o_cs);
-  HIPCHK(hipGetLastError());
+  MCXCHK(tm.run(0, [&]() -> int { return sweep_moments(st, v, D + o_hm, D + o_tot); }));
+  MCXCHK(column_sums(st, v, D + o_tot, D + o_cs));
   std::vector<double> cs(ncol), ctr(ncol);
   HIPCHK(hipMemcpyAsync(cs.data(), D + o_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -167,47 +167,29 @@ static int covariance_device(hipStream_t st, DevBuf<double> *buf, const float *x
   HIPCHK(hipMemcpyAsync(D + o_ctr, ctr.data(), ctr.size() * sizeof(double), hipMemcpyHostToDevice, st));
 
   // ---- 2. the sweep, 3. its partials
-  MCXCHK(mark(2));
-  hipLaunchKernelGGL(k_cov_tiles<true>, dim3((unsigned)nwg, (unsigned)nt), dim3(SB), 0, st, x, ly, np, nt, N, rpw,
-                     (const double *)(D + o_ctr), D + o_part, nwg);
-  HIPCHK(hipGetLastError());
-  if (npairs > nt) {
-    hipLaunchKernelGGL(k_cov_tiles<false>, dim3((unsigned)nwg, (unsigned)(npairs - nt)), dim3(SB), 0, st, x, ly, np, nt, N, rpw,
+  MCXCHK(tm.run(1, [&]() -> int {
+    hipLaunchKernelGGL(k_cov_tiles<true>, dim3((unsigned)nwg, (unsigned)nt), dim3(SB), 0, st, v.x, v.ly, np, nt, N, rpw,
                        (const double *)(D + o_ctr), D + o_part, nwg);
     HIPCHK(hipGetLastError());
-  }
-  MCXCHK(mark(3));
-  hipLaunchKernelGGL(k_sum_rows, dim3((unsigned)R), dim3(SB), 0, st, D + o_part, nwg, 1, 1, 1, nwg, nwg, (const double *)nullptr,
-                     0.0, D + o_out);
-  HIPCHK(hipGetLastError());
-  MCXCHK(mark(4));
+    if (npairs > nt) {
+      hipLaunchKernelGGL(k_cov_tiles<false>, dim3((unsigned)nwg, (unsigned)(npairs - nt)), dim3(SB), 0, st, v.x, v.ly, np, nt, N, rpw,
+                         (const double *)(D + o_ctr), D + o_part, nwg);
+      HIPCHK(hipGetLastError());
+    }
+    return MCX_OK;
+  }));
+  MCXCHK(tm.run(2, [&]() -> int {
+    hipLaunchKernelGGL(k_sum_rows, dim3((unsigned)R), dim3(SB), 0, st, D + o_part, nwg, 1, 1, 1, nwg, nwg, (const double *)nullptr,
+                       0.0, D + o_out);
+    HIPCHK(hipGetLastError());
+    return MCX_OK;
+  }));
   std::vector<double> out(R);
   HIPCHK(hipMemcpyAsync(out.data(), D + o_out, R * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));  // (ctr is read by the upload until here)
-  if (ms)
-    for (int k = 0; k < 3; ++k) {
-      float t = 0.0f;
-      HIPCHK(hipEventElapsedTime(&t, ev[k == 0 ? 0 : k + 1], ev[k == 0 ? 1 : k + 2]));
-      ms[k] = t;
-    }
+  MCXCHK(tm.collect());
 
-  // ---- the matrix: the upper triangle as computed, mirrored
-  const double dof = (double)(N - 1);
-  auto put = [&](int i, int j, double s) {
-    const double v = fin[i] && fin[j] ? s / dof : qnan;
-    cov[(size_t)i * ncol + j] = v;
-    cov[(size_t)j * ncol + i] = v;
-  };
-  int off = nt;
-  for (int ti = 0; ti < nt; ++ti)
-    for (int tj = ti; tj < nt; ++tj) {
-      const int pair = ti == tj ? ti : off++;
-      for (int i = 0; i < CTILE && ti * CTILE + i < np; ++i)
-        for (int j = ti == tj ? i : 0; j < CTILE && tj * CTILE + j < np; ++j)
-          put(ti * CTILE + i, tj * CTILE + j, out[(size_t)pair * CENT + i * CTILE + j]);
-    }
-  for (int c = 0; c < np; ++c) put(c, np, out[(size_t)npairs * CENT + c]);
-  put(np, np, out[(size_t)npairs * CENT + (size_t)nt * CTILE]);
+  cov_matrix(out, fin, np, (double)(N - 1), cov);
   return MCX_OK;
 }
 
@@ -221,39 +203,31 @@ static int covariance_args(int nsteps, int nc, const double *mean, const double 
 
 extern "C" int mcx_samples_covariance(mcx_engine *e, int first_step, int nsteps, double *mean, double *cov, int *flags)
 {
-  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
-  MCXCHK(enter(e));
-  MCXCHK(covariance_args(nsteps, e->nchain, mean, cov));
-  if (e->samp_steps == 0)
-    return fail(MCX_ERR_INVALID, "the sample store is empty (no run yet, MCX_OPT_SAMPLES = 0, or a run into a sink)");
-  if (first_step < 0 || (int64_t)first_step + nsteps > e->samp_steps)
-    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
-                (long long)first_step + nsteps, e->samp_steps);
-  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
-  return covariance_device(e->stream, &e->summ_d, e->samp_x.p + (size_t)first_step * nc * np,
-                           e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np, nsteps, mean, cov, flags);
+  return on_store(
+      e, first_step, nsteps, [&] { return covariance_args(nsteps, e->nchain, mean, cov); },
+      [&](hipStream_t st, Bufs B, const StoreView &v) { return covariance_device(st, B.d, v, mean, cov, flags, nullptr); });
 }
 
 extern "C" int mcx_debug_covariance_times(mcx_engine *e, int first_step, int nsteps, double *ms)
 {
-  if (!e || !ms) return fail(MCX_ERR_INVALID, "bad arguments");
-  MCXCHK(enter(e));
-  if (e->samp_steps == 0 || first_step < 0 || nsteps < 1 || (int64_t)nsteps * e->nchain < 2 ||
-      (int64_t)first_step + nsteps > e->samp_steps)
-    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
-                (long long)first_step + nsteps, e->samp_steps);
-  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
-  std::vector<double> mean(np + 1), cov((np + 1) * (np + 1));
-  return covariance_device(e->stream, &e->summ_d, e->samp_x.p + (size_t)first_step * nc * np,
-                           e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np, nsteps, mean.data(), cov.data(), nullptr, ms);
+  std::vector<double> mean, cov;
+  return on_store(
+      e, first_step, nsteps,
+      [&] {
+        if (!ms) return fail(MCX_ERR_INVALID, "ms is NULL");
+        mean.resize((size_t)e->nparam + 1);
+        cov.resize(mean.size() * mean.size());
+        return covariance_args(nsteps, e->nchain, mean.data(), cov.data());
+      },
+      [&](hipStream_t st, Bufs B, const StoreView &v) { return covariance_device(st, B.d, v, mean.data(), cov.data(), nullptr, ms); });
 }
 
 extern "C" int mcx_rows_covariance(const float *rows, int nsteps, int nc, int np, double *mean, double *cov, int *flags)
 {
   if (nc < 1) return fail(MCX_ERR_INVALID, "bad arguments");
   MCXCHK(covariance_args(nsteps, nc, mean, cov));
-  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
-    return covariance_device(st, B.d, x, ly, nc, np, nsteps, mean, cov, flags);
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const StoreView &v) {
+    return covariance_device(st, B.d, v, mean, cov, flags, nullptr);
   });
 }
 

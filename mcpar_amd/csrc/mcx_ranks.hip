@@ -3,7 +3,7 @@
 //
 // The store is x[step][chain][np] plus ly[step][chain]; N = T * nc values per column.  What is new here is the exact pooled
 // rank of every value (ties averaged) and the stores made of it; R-hat and ESS of those stores are mcx_summary.hip's passes,
-// unchanged (summary_device_parts).  Per transform that needs ranks (the values, and their distance from the median):
+// unchanged (summary_thresholds, summary_mixing).  Per transform that needs ranks (the values, and their distance from the median):
 //   1. k_rank_keys       one sweep of the store in mcx_summary.hip's tiles: an order-preserving 32-bit key per value
 //                        (-0 and +0 the same key) into keys[column][N], index = step * nc + chain
 //   2. 4 x { k_rank_hist, k_rank_rowsum, k_rank_scan, k_rank_scatter }
@@ -242,44 +242,6 @@ struct RankDebug {
   float *out_rows;  // host [N][ncol]
 };
 
-struct StageTimer {
-  hipStream_t st;
-  double *ms;
-  struct Ev { int idx; hipEvent_t a, b; };
-  std::vector<Ev> evs;
-  template <class F> int run(int idx, F f)
-  {
-    if (!ms) return f();
-    Ev e{idx, nullptr, nullptr};
-    HIPCHK(hipEventCreate(&e.a));
-    HIPCHK(hipEventCreate(&e.b));
-    evs.push_back(e);
-    HIPCHK(hipEventRecord(e.a, st));
-    MCXCHK(f());
-    HIPCHK(hipEventRecord(e.b, st));
-    return MCX_OK;
-  }
-  int collect()
-  {
-    if (!ms) return MCX_OK;
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < RT_N; ++i) ms[i] = 0.0;
-    for (const Ev &e : evs) {
-      float t = 0.0f;
-      HIPCHK(hipEventElapsedTime(&t, e.a, e.b));
-      ms[e.idx] += (double)t;
-    }
-    return MCX_OK;
-  }
-  ~StageTimer()
-  {
-    for (const Ev &e : evs) {
-      if (e.a) (void)hipEventDestroy(e.a);
-      if (e.b) (void)hipEventDestroy(e.b);
-    }
-  }
-};
-
 // the scratch of one call, released when it is over: the transformed store, the keys (two arrays the sort passes alternate
 // between), the sort's counts, the thresholds
 struct RankScratch {
@@ -292,197 +254,239 @@ struct RankScratch {
   }
 };
 
+// one rank-normalised summary of a view: what its stages share
+struct RankPass {
+  hipStream_t st;
+  Bufs B;
+  const StoreView &v;
+  StageTimer tm;
+  RankScratch S;
+  bool want_ranks;  // mcx_debug_rows_rank_transform: k_rank_transform also writes the average ranks
+  int G = 0;        // columns sorted at a time (rank_scratch)
+  int64_t rchunk;   // steps per workgroup of the key and transform sweeps
+  unsigned chunks;  // their grid.y
+  uint32_t nblk;    // sort tiles per column
+  std::vector<mcx_col_summary> c0s;  // thresholds: the flags
+  std::vector<double> thr;           // thresholds: [3][ncol] q05, median, q95 (S.thr on the device)
+
+  RankPass(hipStream_t st_, Bufs B_, const StoreView &v_, double *ms, bool want_ranks_)
+      : st(st_), B(B_), v(v_), tm{st_, ms, RT_N, {}}, want_ranks(want_ranks_), rchunk(std::max(RCHUNK, (v_.T + 32767) / 32768)),
+        chunks((unsigned)((v_.T + rchunk - 1) / rchunk)), nblk((uint32_t)((v_.N + RTILE - 1) / RTILE)), c0s(v_.ncol),
+        thr(3 * (size_t)v_.ncol)
+  {
+  }
+};
+
+// the thresholds: the order-statistics pass of the summary, once -> c0s, thr, S.thr
+int thresholds(RankPass &p)
+{
+  const int ncol = p.v.ncol;
+  const double probs[3] = {0.05, 0.5, 0.95};
+  std::vector<double> q(3 * (size_t)ncol);
+  MCXCHK(p.tm.run(RT_THRESHOLDS, [&]() -> int { return summary_thresholds(p.st, p.B, p.v, probs, 3, p.c0s.data(), q.data()); }));
+  for (int c = 0; c < ncol; ++c)
+    for (int k = 0; k < 3; ++k) p.thr[(size_t)k * ncol + c] = q[(size_t)c * 3 + k];
+  MCXCHK(p.S.thr.alloc(p.thr.size()));
+  HIPCHK(hipMemcpyAsync(p.S.thr.p, p.thr.data(), p.thr.size() * sizeof(double), hipMemcpyHostToDevice, p.st));
+  return MCX_OK;
+}
+
+// the scratch: the transformed store, and keys for as many columns at a time as fit -> G
+int rank_scratch(RankPass &p)
+{
+  const int ncol = p.v.ncol;
+  const size_t N = (size_t)p.v.N;
+  RankScratch &S = p.S;
+  MCXCHK(S.xs.alloc(N * p.v.np));
+  MCXCHK(S.lys.alloc(N));
+  if (p.want_ranks) MCXCHK(S.ranks.alloc(N * ncol));
+  int G = ncol;
+  if (const char *cap = std::getenv("MCX_RANK_GROUP_COLS")) G = std::max(1, std::min(ncol, std::atoi(cap)));
+  for (;; G = (G + 1) / 2) {
+    const bool ok = S.ka.alloc((size_t)G * N) == MCX_OK && S.kb.alloc((size_t)G * N) == MCX_OK &&
+                    S.hist.alloc((size_t)G * 256 * p.nblk) == MCX_OK && S.rowsum.alloc((size_t)G * 256) == MCX_OK;
+    if (ok) break;
+    if (G == 1)
+      return fail(MCX_ERR_ALLOC, "rank summary: %zu bytes of scratch are needed for one column at a time (DESIGN.md section 11)",
+                  N * ncol * 4 + N * 8 + ((size_t)p.nblk + 1) * 1024 + (size_t)ncol * 24);
+    S.ka.release(); S.kb.release(); S.hist.release(); S.rowsum.release();
+  }
+  p.G = G;
+  return MCX_OK;
+}
+
+// the keys of columns [c0, c1) -> S.ka, then their LSD radix sort: four passes, after which the sorted keys are back in S.ka
+int sort_group(RankPass &p, int what, int c0, int c1)
+{
+  const StoreView &v = p.v;
+  RankScratch &S = p.S;
+  const int t0 = what * RT_PER;
+  const unsigned g = (unsigned)(c1 - c0);
+  const uint32_t nblk = p.nblk;
+  MCXCHK(p.tm.run(t0 + RT_KEYS, [&]() -> int {
+    for (const TileSet *t : {&v.tx, &v.tl}) {
+      if (t->col0 + t->ncs <= c0 || t->col0 >= c1) continue;
+      hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)(t->nbc * t->ntiles), p.chunks), dim3(SB), 0, p.st, *t, v.nc, v.T, what,
+                         (const double *)S.thr.p, v.ncol, c0, c1, S.ka.p, v.N, p.rchunk);
+      HIPCHK(hipGetLastError());
+    }
+    return MCX_OK;
+  }));
+  uint32_t *src = S.ka.p, *dst = S.kb.p;
+  for (int pass = 0; pass < 4; ++pass) {
+    MCXCHK(p.tm.run(t0 + RT_PASS0 + pass, [&]() -> int {
+      const int shift = 8 * pass;
+      hipLaunchKernelGGL(k_rank_hist, dim3(nblk, g), dim3(SB), 0, p.st, (const uint32_t *)src, v.N, shift, nblk, S.hist.p);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(k_rank_rowsum, dim3(256, g), dim3(SB), 0, p.st, (const uint32_t *)S.hist.p, nblk, S.rowsum.p);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(k_rank_scan, dim3(256, g), dim3(SB), 0, p.st, S.hist.p, nblk, (const uint32_t *)S.rowsum.p);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(k_rank_scatter, dim3(nblk, g), dim3(SB), 0, p.st, (const uint32_t *)src, dst, v.N, shift, nblk,
+                         (const uint32_t *)S.hist.p);
+      HIPCHK(hipGetLastError());
+      return MCX_OK;
+    }));
+    std::swap(src, dst);
+  }
+  return MCX_OK;
+}
+
+// k_rank_transform of columns [c0, c1) -> S.xs, S.lys, timed in slot
+int transform(RankPass &p, int what, int c0, int c1, int slot)
+{
+  const StoreView &v = p.v;
+  RankScratch &S = p.S;
+  return p.tm.run(slot, [&]() -> int {
+    for (const TileSet *t : {&v.tx, &v.tl}) {
+      if (t->col0 + t->ncs <= c0 || t->col0 >= c1) continue;
+      hipLaunchKernelGGL(k_rank_transform, dim3((unsigned)(t->nbc * t->ntiles), p.chunks), dim3(SB), 0, p.st, *t, v.nc, v.T, what,
+                         (const double *)S.thr.p, v.ncol, c0, c1, (const uint32_t *)S.ka.p, v.N, t == &v.tx ? S.xs.p : S.lys.p,
+                         p.want_ranks ? S.ranks.p : (double *)nullptr, p.rchunk);
+      HIPCHK(hipGetLastError());
+    }
+    return MCX_OK;
+  });
+}
+
+// z of the ranks of the values (RANK_BULK) or of their distances from the median (RANK_FOLD) -> S.xs, S.lys, G columns at a time
+int normal_scores(RankPass &p, int what)
+{
+  for (int c0 = 0; c0 < p.v.ncol; c0 += p.G) {
+    const int c1 = std::min(p.v.ncol, c0 + p.G);
+    MCXCHK(sort_group(p, what, c0, c1));
+    MCXCHK(transform(p, what, c0, c1, what * RT_PER + RT_TRANSFORM));
+  }
+  return MCX_OK;
+}
+
+// mcx_debug_rows_rank_transform: stop behind transform dbg.what and copy it out as rows
+int rank_debug_copy_out(RankPass &p, const RankDebug &dbg)
+{
+  const int ncol = p.v.ncol, np = p.v.np;
+  const size_t N = (size_t)p.v.N;
+  if (dbg.what <= RANK_FOLD) MCXCHK(normal_scores(p, dbg.what));
+  else MCXCHK(transform(p, dbg.what, 0, ncol, RT_I05));
+  std::vector<float> hx(N * np), hl(N);
+  HIPCHK(hipMemcpyAsync(hx.data(), p.S.xs.p, hx.size() * sizeof(float), hipMemcpyDeviceToHost, p.st));
+  HIPCHK(hipMemcpyAsync(hl.data(), p.S.lys.p, hl.size() * sizeof(float), hipMemcpyDeviceToHost, p.st));
+  if (dbg.ranks) HIPCHK(hipMemcpyAsync(dbg.ranks, p.S.ranks.p, N * ncol * sizeof(double), hipMemcpyDeviceToHost, p.st));
+  HIPCHK(hipStreamSynchronize(p.st));
+  for (size_t r = 0; r < N; ++r) {
+    std::memcpy(dbg.out_rows + r * ncol, hx.data() + r * np, (size_t)np * sizeof(float));
+    dbg.out_rows[r * ncol + np] = hl[r];
+  }
+  return MCX_OK;
+}
+
+// R-hat and ESS of the transformed store S.xs, S.lys -> cs (rhat, ess, ess_lag), timed in slot
+int mixing(RankPass &p, int slot, std::vector<mcx_col_summary> &cs)
+{
+  return p.tm.run(slot, [&]() -> int {
+    return summary_mixing(p.st, p.B, StoreSpan{p.S.xs.p, p.S.lys.p, p.v.nc, p.v.np, p.v.T}, cs.data());
+  });
+}
+
 inline double nan_max(double a, double b) { return a != a || b != b ? std::numeric_limits<double>::quiet_NaN() : std::max(a, b); }
 inline double nan_min(double a, double b) { return a != a || b != b ? std::numeric_limits<double>::quiet_NaN() : std::min(a, b); }
 
-// the rank-normalised summary of x[T][nc][np], ly[T][nc] (device) on stream st.  dbg: stop behind that transform and copy
-// it out; ms (RT_N doubles): the stages' times
-int rank_device(hipStream_t st, Bufs B, const float *x, const float *ly, int nc, int np, int64_t T, mcx_col_rank_summary *out,
-                const RankDebug *dbg, double *ms)
+// rhat and ess_tail of every column from its parts; a column that is not finite is NaN throughout
+void assemble(mcx_col_rank_summary *out, int ncol)
 {
-  const int ncol = np + 1;
-  const int64_t N = T * (int64_t)nc;
-  if (N >= ((int64_t)1 << 31)) return fail(MCX_ERR_UNSUPPORTED, "rank summary: %lld values per column, fewer than 2^31 are supported", (long long)N);
   const double qnan = std::numeric_limits<double>::quiet_NaN();
-  const TileSet tx = tiles_x(x, nc, np), tl = tiles_l(ly, nc, np);
-  const int64_t rchunk = std::max(RCHUNK, (T + 32767) / 32768);
-  const unsigned chunks = (unsigned)((T + rchunk - 1) / rchunk);
-  const uint32_t nblk = (uint32_t)((N + RTILE - 1) / RTILE);
-  StageTimer tm{st, ms, {}};
-  RankScratch S;
-  std::vector<mcx_col_summary> c0s(ncol), cs(ncol);
-  std::vector<double> thr(3 * (size_t)ncol), q(3 * (size_t)ncol);
-
-  MCXCHK(tm.run(RT_TOTAL, [&]() -> int {
-    // ---- thresholds: the existing order-statistics pass, once
-    const double probs[3] = {0.05, 0.5, 0.95};
-    MCXCHK(tm.run(RT_THRESHOLDS, [&]() -> int {
-      return summary_device_parts(st, B.d, B.h, B.u, x, ly, nc, np, T, probs, 3, c0s.data(), q.data(), SUMM_OSTAT);
-    }));
-    for (int c = 0; c < ncol; ++c)
-      for (int k = 0; k < 3; ++k) thr[(size_t)k * ncol + c] = q[(size_t)c * 3 + k];
-    MCXCHK(S.thr.alloc(thr.size()));
-    HIPCHK(hipMemcpyAsync(S.thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, st));
-
-    // ---- scratch: the transformed store, and keys for as many columns at a time as fit
-    MCXCHK(S.xs.alloc((size_t)N * np));
-    MCXCHK(S.lys.alloc((size_t)N));
-    if (dbg && dbg->ranks) MCXCHK(S.ranks.alloc((size_t)N * ncol));
-    int G = ncol;
-    if (const char *cap = std::getenv("MCX_RANK_GROUP_COLS")) G = std::max(1, std::min(ncol, std::atoi(cap)));
-    for (;;) {
-      const bool ok = S.ka.alloc((size_t)G * N) == MCX_OK && S.kb.alloc((size_t)G * N) == MCX_OK &&
-                      S.hist.alloc((size_t)G * 256 * nblk) == MCX_OK && S.rowsum.alloc((size_t)G * 256) == MCX_OK;
-      if (ok) break;
-      if (G == 1)
-        return fail(MCX_ERR_ALLOC, "rank summary: %zu bytes of scratch are needed for one column at a time (DESIGN.md section 11)",
-                    (size_t)N * ncol * 4 + (size_t)N * 8 + ((size_t)nblk + 1) * 1024 + (size_t)ncol * 24);
-      S.ka.release(); S.kb.release(); S.hist.release(); S.rowsum.release();
-      G = (G + 1) / 2;
+  for (int c = 0; c < ncol; ++c) {
+    mcx_col_rank_summary &o = out[c];
+    if (o.flags & MCX_SUMMARY_NONFINITE) {
+      o.rhat = o.rhat_bulk = o.rhat_folded = o.ess_bulk = o.ess_tail = o.ess_q05 = o.ess_q95 = o.q05 = o.median = o.q95 = qnan;
+      o.ess_bulk_lag = 0;
+      continue;
     }
+    o.rhat = nan_max(o.rhat_bulk, o.rhat_folded);
+    o.ess_tail = nan_min(o.ess_q05, o.ess_q95);
+  }
+}
 
-    auto transform = [&](int what, int c0, int c1, int slot) -> int {
-      return tm.run(slot, [&]() -> int {
-        for (const TileSet *t : {&tx, &tl}) {
-          if (t->col0 + t->ncs <= c0 || t->col0 >= c1) continue;
-          hipLaunchKernelGGL(k_rank_transform, dim3((unsigned)(t->nbc * t->ntiles), chunks), dim3(SB), 0, st, *t, nc, T, what,
-                             (const double *)S.thr.p, ncol, c0, c1, (const uint32_t *)S.ka.p, N, t == &tx ? S.xs.p : S.lys.p,
-                             dbg && dbg->ranks ? S.ranks.p : (double *)nullptr, rchunk);
-          HIPCHK(hipGetLastError());
-        }
-        return MCX_OK;
-      });
-    };
-    // z of the ranks of the values (RANK_BULK) or of their distances from the median (RANK_FOLD) -> xs, lys
-    auto normal_scores = [&](int what) -> int {
-      const int t0 = what * RT_PER;
-      for (int c0 = 0; c0 < ncol; c0 += G) {
-        const int c1 = std::min(ncol, c0 + G), g = c1 - c0;
-        MCXCHK(tm.run(t0 + RT_KEYS, [&]() -> int {
-          for (const TileSet *t : {&tx, &tl}) {
-            if (t->col0 + t->ncs <= c0 || t->col0 >= c1) continue;
-            hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)(t->nbc * t->ntiles), chunks), dim3(SB), 0, st, *t, nc, T, what,
-                               (const double *)S.thr.p, ncol, c0, c1, S.ka.p, N, rchunk);
-            HIPCHK(hipGetLastError());
-          }
-          return MCX_OK;
-        }));
-        uint32_t *src = S.ka.p, *dst = S.kb.p;
-        for (int pass = 0; pass < 4; ++pass) {
-          MCXCHK(tm.run(t0 + RT_PASS0 + pass, [&]() -> int {
-            const int shift = 8 * pass;
-            hipLaunchKernelGGL(k_rank_hist, dim3(nblk, (unsigned)g), dim3(SB), 0, st, (const uint32_t *)src, N, shift, nblk, S.hist.p);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_rank_rowsum, dim3(256, (unsigned)g), dim3(SB), 0, st, (const uint32_t *)S.hist.p, nblk, S.rowsum.p);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_rank_scan, dim3(256, (unsigned)g), dim3(SB), 0, st, S.hist.p, nblk, (const uint32_t *)S.rowsum.p);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_rank_scatter, dim3(nblk, (unsigned)g), dim3(SB), 0, st, (const uint32_t *)src, dst, N, shift, nblk,
-                               (const uint32_t *)S.hist.p);
-            HIPCHK(hipGetLastError());
-            return MCX_OK;
-          }));
-          std::swap(src, dst);
-        }
-        // four passes: the sorted keys are back in ka
-        MCXCHK(transform(what, c0, c1, t0 + RT_TRANSFORM));
-      }
-      return MCX_OK;
-    };
-
-    if (dbg) {
-      if (dbg->what <= RANK_FOLD) MCXCHK(normal_scores(dbg->what));
-      else MCXCHK(transform(dbg->what, 0, ncol, RT_I05));
-      std::vector<float> hx((size_t)N * np), hl((size_t)N);
-      HIPCHK(hipMemcpyAsync(hx.data(), S.xs.p, hx.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(hl.data(), S.lys.p, hl.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-      if (dbg->ranks) HIPCHK(hipMemcpyAsync(dbg->ranks, S.ranks.p, (size_t)N * ncol * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      for (int64_t r = 0; r < N; ++r) {
-        std::memcpy(dbg->out_rows + (size_t)r * ncol, hx.data() + (size_t)r * np, (size_t)np * sizeof(float));
-        dbg->out_rows[(size_t)r * ncol + np] = hl[(size_t)r];
-      }
-      return MCX_OK;
-    }
-
-    auto summarise = [&](int slot) -> int {
-      return tm.run(slot, [&]() -> int {
-        return summary_device_parts(st, B.d, B.h, B.u, S.xs.p, S.lys.p, nc, np, T, nullptr, 0, cs.data(), nullptr, SUMM_ACOV);
-      });
-    };
+// the rank-normalised summary of a view on stream st, the stages of DESIGN.md section 11 in their order.  dbg: stop behind
+// that transform and copy it out; ms (RT_N doubles): the stages' times
+int rank_device(hipStream_t st, Bufs B, const StoreView &v, mcx_col_rank_summary *out, const RankDebug *dbg, double *ms)
+{
+  if (v.N >= ((int64_t)1 << 31))
+    return fail(MCX_ERR_UNSUPPORTED, "rank summary: %lld values per column, fewer than 2^31 are supported", (long long)v.N);
+  const int ncol = v.ncol;
+  RankPass p(st, B, v, ms, dbg && dbg->ranks);
+  std::vector<mcx_col_summary> cs(ncol);
+  MCXCHK(p.tm.run(RT_TOTAL, [&]() -> int {
+    MCXCHK(thresholds(p));
+    MCXCHK(rank_scratch(p));
+    if (dbg) return rank_debug_copy_out(p, *dbg);
     for (int c = 0; c < ncol; ++c) {
-      mcx_col_rank_summary &o = out[c];
-      o.flags = c0s[c].flags;
-      o.q05 = thr[c];
-      o.median = thr[(size_t)ncol + c];
-      o.q95 = thr[2 * (size_t)ncol + c];
+      out[c].flags = p.c0s[c].flags;
+      out[c].q05 = p.thr[c];
+      out[c].median = p.thr[(size_t)ncol + c];
+      out[c].q95 = p.thr[2 * (size_t)ncol + c];
     }
-    MCXCHK(normal_scores(RANK_BULK));
-    MCXCHK(summarise(RANK_BULK * RT_PER + RT_SUMMARY));
+    MCXCHK(normal_scores(p, RANK_BULK));
+    MCXCHK(mixing(p, RANK_BULK * RT_PER + RT_SUMMARY, cs));
     for (int c = 0; c < ncol; ++c) {
       out[c].rhat_bulk = cs[c].rhat;
       out[c].ess_bulk = cs[c].ess;
       out[c].ess_bulk_lag = cs[c].ess_lag;
     }
-    MCXCHK(normal_scores(RANK_FOLD));
-    MCXCHK(summarise(RANK_FOLD * RT_PER + RT_SUMMARY));
+    MCXCHK(normal_scores(p, RANK_FOLD));
+    MCXCHK(mixing(p, RANK_FOLD * RT_PER + RT_SUMMARY, cs));
     for (int c = 0; c < ncol; ++c) out[c].rhat_folded = cs[c].rhat;
-    MCXCHK(transform(RANK_I05, 0, ncol, RT_I05));
-    MCXCHK(summarise(RT_I05_SUMMARY));
+    MCXCHK(transform(p, RANK_I05, 0, ncol, RT_I05));
+    MCXCHK(mixing(p, RT_I05_SUMMARY, cs));
     for (int c = 0; c < ncol; ++c) out[c].ess_q05 = cs[c].ess;
-    MCXCHK(transform(RANK_I95, 0, ncol, RT_I95));
-    MCXCHK(summarise(RT_I95_SUMMARY));
+    MCXCHK(transform(p, RANK_I95, 0, ncol, RT_I95));
+    MCXCHK(mixing(p, RT_I95_SUMMARY, cs));
     for (int c = 0; c < ncol; ++c) out[c].ess_q95 = cs[c].ess;
-    for (int c = 0; c < ncol; ++c) {
-      mcx_col_rank_summary &o = out[c];
-      if (o.flags & MCX_SUMMARY_NONFINITE) {
-        o.rhat = o.rhat_bulk = o.rhat_folded = o.ess_bulk = o.ess_tail = o.ess_q05 = o.ess_q95 = o.q05 = o.median = o.q95 = qnan;
-        o.ess_bulk_lag = 0;
-        continue;
-      }
-      o.rhat = nan_max(o.rhat_bulk, o.rhat_folded);
-      o.ess_tail = nan_min(o.ess_q05, o.ess_q95);
-    }
+    assemble(out, ncol);
     return MCX_OK;
   }));
-  return tm.collect();
+  return p.tm.collect();
 }
 
 int rank_args(int nsteps, const void *cols)
 {
   if (!cols) return fail(MCX_ERR_INVALID, "cols is NULL");
-  if (nsteps < 4) return fail(MCX_ERR_INVALID, "a summary needs nsteps >= 4 (two half-chains of >= 2 steps), got %d", nsteps);
-  return MCX_OK;
-}
-
-int rank_engine(mcx_engine *e, int first_step, int nsteps, mcx_col_rank_summary *cols, double *ms)
-{
-  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
-  MCXCHK(rank_args(nsteps, cols));
-  MCXCHK(enter(e));
-  if (e->samp_steps == 0)
-    return fail(MCX_ERR_INVALID, "the sample store is empty (no run yet, MCX_OPT_SAMPLES = 0, or a run into a sink)");
-  if (first_step < 0 || (int64_t)first_step + nsteps > e->samp_steps)
-    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
-                (long long)first_step + nsteps, e->samp_steps);
-  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
-  return rank_device(e->stream, Bufs{&e->summ_d, &e->summ_h, &e->summ_u}, e->samp_x.p + (size_t)first_step * nc * np,
-                     e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np, nsteps, cols, nullptr, ms);
+  return half_chain_args(nsteps);
 }
 
 }  // namespace
 
 extern "C" int mcx_samples_rank_summary(mcx_engine *e, int first_step, int nsteps, mcx_col_rank_summary *cols)
 {
-  return rank_engine(e, first_step, nsteps, cols, nullptr);
+  return on_store(
+      e, first_step, nsteps, [&] { return rank_args(nsteps, cols); },
+      [&](hipStream_t st, Bufs B, const StoreView &v) { return rank_device(st, B, v, cols, nullptr, nullptr); });
 }
 
 extern "C" int mcx_rows_rank_summary(const float *rows, int nsteps, int nc, int np, mcx_col_rank_summary *cols)
 {
   MCXCHK(rank_args(nsteps, cols));
-  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
-    return rank_device(st, B, x, ly, nc, np, nsteps, cols, nullptr, nullptr);
-  });
+  return on_rows(rows, nsteps, nc, np,
+                 [&](hipStream_t st, Bufs B, const StoreView &v) { return rank_device(st, B, v, cols, nullptr, nullptr); });
 }
 
 extern "C" int mcx_debug_rows_rank_transform(const float *rows, int nsteps, int nc, int np, int what, double *ranks,
@@ -492,17 +496,22 @@ extern "C" int mcx_debug_rows_rank_transform(const float *rows, int nsteps, int 
   if (what < RANK_BULK || what > RANK_I95) return fail(MCX_ERR_INVALID, "what = %d: 0 z(x), 1 z(f), 2 I05, 3 I95", what);
   if (ranks && what > RANK_FOLD) return fail(MCX_ERR_INVALID, "ranks only exist for what = 0 and 1");
   const RankDebug dbg{what, ranks, out_rows};
-  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
-    return rank_device(st, B, x, ly, nc, np, nsteps, nullptr, &dbg, nullptr);
-  });
+  return on_rows(rows, nsteps, nc, np,
+                 [&](hipStream_t st, Bufs B, const StoreView &v) { return rank_device(st, B, v, nullptr, &dbg, nullptr); });
 }
 
 extern "C" int mcx_debug_rank_summary_times(mcx_engine *e, int first_step, int nsteps, double *ms)
 {
-  if (!ms) return fail(MCX_ERR_INVALID, "ms is NULL");
-  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
-  std::vector<mcx_col_rank_summary> cols((size_t)e->nparam + 1);
-  return rank_engine(e, first_step, nsteps, cols.data(), ms);
+  return on_store(
+      e, first_step, nsteps,
+      [&] {
+        if (!ms) return fail(MCX_ERR_INVALID, "ms is NULL");
+        return half_chain_args(nsteps);
+      },
+      [&](hipStream_t st, Bufs B, const StoreView &v) {
+        std::vector<mcx_col_rank_summary> cols(v.ncol);
+        return rank_device(st, B, v, cols.data(), nullptr, ms);
+      });
 }
 
 extern "C" int mcx_debug_normal_quantile(const double *p, int n, double *z)

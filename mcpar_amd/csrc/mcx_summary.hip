@@ -151,51 +151,13 @@ inline float key_float(uint32_t k)
   return f;
 }
 
-}  // namespace
-
-// the summary of x[T][nc][np], ly[T][nc] (device) on stream st.  force_lags > 0 (mcx_debug_rows_acov): every finite
-// column takes windows until it holds force_lags lags instead of stopping where its Geyer loop does; the raw lag sums go to
-// acov_out[ncol][force_lags] and the centred sums of squares to sumsq_out[ncol] (NaN for a column that is not finite),
-// and cols / quantiles are not computed.  parts (SUMM_*) leaves out what a pass of mcx_samples_rank_summary does not need:
-// without SUMM_OSTAT no order statistics (min, max and quantiles are not valid), without SUMM_ACOV no autocovariance
-// windows (rhat, ess, ess_lag and mcse_mean are not valid); flags, mean and sd always are.
-static int summary_device(hipStream_t st, Bufs B, const float *x, const float *ly, int nc, int np, int64_t T,
-                          const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles, int *nwin_out,
-                          int force_lags = 0, double *acov_out = nullptr, double *sumsq_out = nullptr,
-                          int parts = SUMM_OSTAT | SUMM_ACOV)
+// ---------------------------------------------------------------------------------------------------------------------
+// the host pieces of the radix select (no HIP in them)
+// ---------------------------------------------------------------------------------------------------------------------
+// the target ranks of a column of N values: 0, N - 1, then lo, lo + 1 of every probability
+std::vector<int64_t> target_ranks(int64_t N, const double *probs, int nprobs)
 {
-  const int ncol = np + 1;
-  const int64_t n = T / 2, M = 2 * (int64_t)nc, N = T * (int64_t)nc;
-  const TileSet tx = tiles_x(x, nc, np), tl = tiles_l(ly, nc, np);
-  const size_t pstride = (size_t)std::max(tx.nbc, tl.nbc);
-  const int KWMAX = 8;
-  // device double scratch: hm[ncol][2][nc] | tot[ncol][nc] | colsum[3][ncol] | part[KWMAX][ncol][NQ][pstride] | win[KWMAX][ncol][NQ]
-  const size_t o_hm = 0, o_tot = o_hm + (size_t)ncol * 2 * nc, o_cs = o_tot + (size_t)ncol * nc, o_part = o_cs + 3 * (size_t)ncol,
-               o_win = o_part + (size_t)KWMAX * ncol * NQ * pstride, nd = o_win + (size_t)KWMAX * ncol * NQ;
-  MCXCHK(B.d->alloc(nd));
-  double *D = B.d->p;
-  auto rows = [&](const double *in, size_t stride, int qper, size_t nrows, size_t lenx, size_t lenl, const double *center,
-                  double cscale, double *out) -> int {
-    hipLaunchKernelGGL(k_sum_rows, dim3((unsigned)nrows), dim3(SB), 0, st, in, stride, qper, ncol, np, lenx, lenl, center, cscale, out);
-    HIPCHK(hipGetLastError());
-    return MCX_OK;
-  };
-
-  // ---- 1. moments
-  for (const TileSet *t : {&tx, &tl}) {
-    hipLaunchKernelGGL(k_sum_moments, dim3((unsigned)(t->nbc * t->ntiles)), dim3(SB), 0, st, *t, nc, T, n, D + o_hm, D + o_tot);
-    HIPCHK(hipGetLastError());
-  }
-  MCXCHK(rows(D + o_tot, nc, 1, ncol, nc, nc, nullptr, 0.0, D + o_cs));
-  MCXCHK(rows(D + o_hm, 2 * (size_t)nc, 1, ncol, 2 * (size_t)nc, 2 * (size_t)nc, nullptr, 0.0, D + o_cs + ncol));
-  MCXCHK(rows(D + o_hm, 2 * (size_t)nc, 1, ncol, 2 * (size_t)nc, 2 * (size_t)nc, D + o_cs + ncol, 1.0 / (double)M, D + o_cs + 2 * ncol));
-  std::vector<double> cs(3 * (size_t)ncol);
-  HIPCHK(hipMemcpyAsync(cs.data(), D + o_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-
-  // ---- 2. order statistics: ranks 0, N-1, then lo, lo+1 of every probability
-  const int nt = 2 + 2 * nprobs;
-  std::vector<int64_t> rank(nt);
+  std::vector<int64_t> rank(2 + 2 * (size_t)nprobs);
   rank[0] = 0;
   rank[1] = N - 1;
   for (int k = 0; k < nprobs; ++k) {
@@ -203,159 +165,239 @@ static int summary_device(hipStream_t st, Bufs B, const float *x, const float *l
     rank[2 + 2 * k] = std::min(lo, N - 1);
     rank[3 + 2 * k] = std::min(lo + 1, N - 1);
   }
-  std::vector<int64_t> rem((size_t)ncol * nt);      // rank within the current prefix
-  std::vector<uint32_t> pre((size_t)ncol * nt, 0);  // key bits found so far
-  for (int c = 0; c < ncol; ++c)
-    for (int k = 0; k < nt; ++k) rem[(size_t)c * nt + k] = rank[k];
+  return rank;
+}
+
+// the distinct prefixes of each column's nt targets, sorted; returns the longest list's length (1 at least)
+int prefix_lists(const std::vector<uint32_t> &pre, int ncol, int nt, std::vector<std::vector<uint32_t>> &lists)
+{
+  int G = 1;
+  lists.assign(ncol, {});
+  for (int c = 0; c < ncol; ++c) {
+    auto &L = lists[c];
+    L.assign(pre.begin() + (size_t)c * nt, pre.begin() + (size_t)(c + 1) * nt);
+    std::sort(L.begin(), L.end());
+    L.erase(std::unique(L.begin(), L.end()), L.end());
+    G = std::max(G, (int)L.size());
+  }
+  return G;
+}
+
+// one digit of one target: the digit b whose bucket of hist[256] holds rank rem of the values under the prefix, and the
+// rank within that bucket.  The walk stops at 255 whatever the counts say: a rank past the end lands in the last bucket
+int select_step(const unsigned long long *hist, int64_t rem, int64_t *rem_out)
+{
+  int b = 0;
+  while (b < 255 && rem >= (int64_t)hist[b]) rem -= (int64_t)hist[b++];
+  *rem_out = rem;
+  return b;
+}
+
+// a tile set for a histogram launch of gn prefixes per column: the LDS counts stay within 32 KiB, by narrower parameter
+// tiles when a column has many target prefixes
+TileSet hist_tiles(TileSet t, int gn, int nc)
+{
+  while (t.ct > 1 && (size_t)t.ct * gn * 256 * 4 > 32768) t.ct /= 2;
+  t.cg = SB / t.ct; t.ntiles = (t.ncs + t.ct - 1) / t.ct; t.nbc = (nc + t.cg - 1) / t.cg;
+  return t;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// one summary of a view: the context its phases share
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int KWMAX = 8;  // lag windows per k_sum_acov launch
+
+struct SummaryPass {
+  hipStream_t st;
+  Bufs B;
+  const StoreView &v;
+  const double *probs;
+  int nprobs, nt;  // nt = 2 + 2 nprobs order statistics per column: min, max, the two neighbours of every quantile
+  // device double scratch: hm[ncol][2][nc] | tot[ncol][nc] | colsum[3][ncol] | part[KWMAX][ncol][NQ][pstride] | win[KWMAX][ncol][NQ]
+  size_t pstride, o_hm, o_tot, o_cs, o_part, o_win, nd;
+  double *D = nullptr;
+  // host copies that later phases read
+  std::vector<double> cs;                  // moments_pass: [3][ncol] sums of the values, of the half-chain means, of their centred squares
+  std::vector<uint32_t> pre;               // order_stats_pass: [ncol][nt] keys of the order statistics (0 until it has run)
+  std::vector<std::vector<double>> acov;   // acov_windows: per column, sums over half-chains and steps of c_i c_{i+t}
+  std::vector<double> ss;                  // acov_windows: per column, the centred sum of squares
+  int nwin = 0;                            // acov_windows: lag windows computed
+
+  SummaryPass(hipStream_t st_, Bufs B_, const StoreView &v_, const double *probs_, int nprobs_)
+      : st(st_), B(B_), v(v_), probs(probs_), nprobs(nprobs_), nt(2 + 2 * nprobs_), pstride((size_t)std::max(v_.tx.nbc, v_.tl.nbc)),
+        pre((size_t)v_.ncol * nt, 0u), acov(v_.ncol), ss(v_.ncol, 0.0)
+  {
+    const size_t ncol = v.ncol, nc = v.nc;
+    o_hm = 0; o_tot = o_hm + ncol * 2 * nc; o_cs = o_tot + ncol * nc; o_part = o_cs + 3 * ncol;
+    o_win = o_part + (size_t)KWMAX * ncol * NQ * pstride; nd = o_win + (size_t)KWMAX * ncol * NQ;
+  }
+  int rows(const double *in, size_t stride, int qper, size_t nrows, size_t lenx, size_t lenl, const double *center, double cscale,
+           double *out) const
+  {
+    hipLaunchKernelGGL(k_sum_rows, dim3((unsigned)nrows), dim3(SB), 0, st, in, stride, qper, v.ncol, v.np, lenx, lenl, center, cscale, out);
+    HIPCHK(hipGetLastError());
+    return MCX_OK;
+  }
+};
+
+// ---- 1. moments -> cs
+int moments_pass(SummaryPass &p)
+{
+  const StoreView &v = p.v;
+  const int ncol = v.ncol;
+  const size_t nc2 = 2 * (size_t)v.nc;
+  MCXCHK(p.B.d->alloc(p.nd));
+  double *D = p.D = p.B.d->p;
+  MCXCHK(launch_moments(p.st, v, D + p.o_hm, D + p.o_tot, D + p.o_cs));
+  MCXCHK(p.rows(D + p.o_hm, nc2, 1, ncol, nc2, nc2, nullptr, 0.0, D + p.o_cs + ncol));
+  MCXCHK(p.rows(D + p.o_hm, nc2, 1, ncol, nc2, nc2, D + p.o_cs + ncol, 1.0 / (double)v.M, D + p.o_cs + 2 * ncol));
+  p.cs.resize(3 * (size_t)ncol);
+  HIPCHK(hipMemcpyAsync(p.cs.data(), D + p.o_cs, p.cs.size() * sizeof(double), hipMemcpyDeviceToHost, p.st));
+  HIPCHK(hipStreamSynchronize(p.st));
+  return MCX_OK;
+}
+
+// ---- 2. order statistics -> pre: a radix select of every column's target ranks, 8 bits per pass from the top
+int order_stats_pass(SummaryPass &p)
+{
+  const StoreView &v = p.v;
+  const int ncol = v.ncol, nt = p.nt;
+  const std::vector<int64_t> rank = target_ranks(v.N, p.probs, p.nprobs);
+  std::vector<int64_t> rem((size_t)ncol * nt);  // rank within the current prefix
+  for (int c = 0; c < ncol; ++c) std::copy(rank.begin(), rank.end(), rem.begin() + (size_t)c * nt);
+  std::vector<std::vector<uint32_t>> lists;
   std::vector<uint32_t> gp;
   std::vector<int> gc(ncol);
   std::vector<unsigned long long> hh;
-  for (int pass = 0; pass < ((parts & SUMM_OSTAT) ? 4 : 0); ++pass) {
+  const unsigned chunks = (unsigned)((v.T + HIST_CHUNK - 1) / HIST_CHUNK);
+  for (int pass = 0; pass < 4; ++pass) {
     const int shift = 32 - 8 * pass;
-    // the distinct prefixes of each column's targets, sorted
-    int G = 1;
-    std::vector<std::vector<uint32_t>> lists(ncol);
-    for (int c = 0; c < ncol; ++c) {
-      auto &L = lists[c];
-      for (int k = 0; k < nt; ++k) L.push_back(pass == 0 ? 0u : pre[(size_t)c * nt + k]);
-      std::sort(L.begin(), L.end());
-      L.erase(std::unique(L.begin(), L.end()), L.end());
-      G = std::max(G, (int)L.size());
-    }
+    const int G = prefix_lists(p.pre, ncol, nt, lists);
     gp.assign((size_t)ncol * G, 0u);
     for (int c = 0; c < ncol; ++c) {
       std::copy(lists[c].begin(), lists[c].end(), gp.begin() + (size_t)c * G);
       gc[c] = (int)lists[c].size();
     }
     const size_t nh = (size_t)ncol * G * 256;
-    MCXCHK(B.u->alloc(gp.size() + ncol));
-    MCXCHK(B.h->alloc(nh));
-    HIPCHK(hipMemcpyAsync(B.u->p, gp.data(), gp.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(B.u->p + gp.size(), gc.data(), (size_t)ncol * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(B.h->p, 0, nh * sizeof(unsigned long long), st));
-    const unsigned chunks = (unsigned)((T + HIST_CHUNK - 1) / HIST_CHUNK);
+    MCXCHK(p.B.u->alloc(gp.size() + ncol));
+    MCXCHK(p.B.h->alloc(nh));
+    HIPCHK(hipMemcpyAsync(p.B.u->p, gp.data(), gp.size() * 4, hipMemcpyHostToDevice, p.st));
+    HIPCHK(hipMemcpyAsync(p.B.u->p + gp.size(), gc.data(), (size_t)ncol * 4, hipMemcpyHostToDevice, p.st));
+    HIPCHK(hipMemsetAsync(p.B.h->p, 0, nh * sizeof(unsigned long long), p.st));
     for (int g0 = 0; g0 < G; g0 += GMAX) {
       const int gn = std::min(GMAX, G - g0);
-      for (const TileSet *t0 : {&tx, &tl}) {
-        TileSet t = *t0;
-        // keep the LDS counts within 32 KiB: narrower parameter tiles when a column has many target prefixes
-        while (t.ct > 1 && (size_t)t.ct * gn * 256 * 4 > 32768) t.ct /= 2;
-        t.cg = SB / t.ct; t.ntiles = (t.ncs + t.ct - 1) / t.ct; t.nbc = (nc + t.cg - 1) / t.cg;
+      for (const TileSet *t0 : {&v.tx, &v.tl}) {
+        const TileSet t = hist_tiles(*t0, gn, v.nc);
         const size_t lds = (size_t)t.ct * gn * 257 * 4 + (size_t)t.ct * 4;
-        hipLaunchKernelGGL(k_sum_hist, dim3((unsigned)(t.nbc * t.ntiles), chunks), dim3(SB), lds, st, t, nc, T, shift,
-                           B.u->p, (const int *)(B.u->p + gp.size()), G, g0, gn, B.h->p);
+        hipLaunchKernelGGL(k_sum_hist, dim3((unsigned)(t.nbc * t.ntiles), chunks), dim3(SB), lds, p.st, t, v.nc, v.T, shift,
+                           p.B.u->p, (const int *)(p.B.u->p + gp.size()), G, g0, gn, p.B.h->p);
         HIPCHK(hipGetLastError());
       }
     }
     hh.resize(nh);
-    HIPCHK(hipMemcpyAsync(hh.data(), B.h->p, nh * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(hh.data(), p.B.h->p, nh * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
+    HIPCHK(hipStreamSynchronize(p.st));
     for (int c = 0; c < ncol; ++c)
       for (int k = 0; k < nt; ++k) {
-        const uint32_t pf = pass == 0 ? 0u : pre[(size_t)c * nt + k];
-        const int g = (int)(std::lower_bound(lists[c].begin(), lists[c].end(), pf) - lists[c].begin());
-        const unsigned long long *h = hh.data() + ((size_t)c * G + g) * 256;
-        int64_t r = rem[(size_t)c * nt + k];
-        int b = 0;
-        while (b < 255 && r >= (int64_t)h[b]) r -= (int64_t)h[b++];
-        rem[(size_t)c * nt + k] = r;
-        pre[(size_t)c * nt + k] = (pf << 8) | (uint32_t)b;
+        const size_t i = (size_t)c * nt + k;
+        const int g = (int)(std::lower_bound(lists[c].begin(), lists[c].end(), p.pre[i]) - lists[c].begin());
+        const int b = select_step(hh.data() + ((size_t)c * G + g) * 256, rem[i], &rem[i]);
+        p.pre[i] = (p.pre[i] << 8) | (uint32_t)b;
       }
-  }
-
-  // ---- 3. autocovariance windows, while some column's Geyer loop wants more lags
-  std::vector<int> active(ncol), need(ncol, 0);
-  std::vector<std::vector<double>> acov(ncol);  // sums over half-chains and steps of c_i c_{i+t}
-  std::vector<double> ss(ncol, 0.0);
-  for (int c = 0; c < ncol; ++c) active[c] = (parts & SUMM_ACOV) && std::isfinite(cs[c]) ? 1 : 0;
-  const int nwin_max = (int)((n + WLAG - 1) / WLAG);
-  int k0 = 0, KW = 2, nwin = 0;
-  std::vector<float> os(nt);
-  std::vector<double> win;
-  for (;;) {
-    bool any = false;
-    for (int c = 0; c < ncol; ++c) any = any || active[c];
-    if (!any || k0 >= nwin_max) break;
-    KW = std::min({KW, KWMAX, nwin_max - k0});
-    MCXCHK(B.u->alloc(ncol));
-    HIPCHK(hipMemcpyAsync(B.u->p, active.data(), (size_t)ncol * 4, hipMemcpyHostToDevice, st));
-    for (const TileSet *t : {&tx, &tl}) {
-      hipLaunchKernelGGL(k_sum_acov, dim3((unsigned)(KW * t->ntiles * t->nbc)), dim3(SB), 0, st, *t, nc, T, n, k0, KW, ncol,
-                         D + o_hm, D + o_cs, (double)N, (const int *)B.u->p, D + o_part, pstride);
-      HIPCHK(hipGetLastError());
-    }
-    MCXCHK(rows(D + o_part, pstride, NQ, (size_t)KW * ncol * NQ, tx.nbc, tl.nbc, nullptr, 0.0, D + o_win));
-    win.resize((size_t)KW * ncol * NQ);
-    HIPCHK(hipMemcpyAsync(win.data(), D + o_win, win.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    nwin += KW;
-    for (int c = 0; c < ncol; ++c) {
-      if (!active[c]) continue;
-      for (int y = 0; y < KW; ++y) {
-        const double *w = win.data() + ((size_t)y * ncol + c) * NQ;
-        for (int q = 0; q < WLAG && (int64_t)acov[c].size() < n; ++q) acov[c].push_back(w[q]);
-        if (k0 + y == 0) ss[c] = w[WLAG];
-      }
-    }
-    k0 += KW;
-    KW *= 2;
-    // which columns want more lags than they have
-    for (int c = 0; c < ncol; ++c) {
-      if (!active[c]) continue;
-      if (force_lags > 0) {
-        active[c] = (int64_t)acov[c].size() < force_lags ? 1 : 0;
-        continue;
-      }
-      std::vector<double> a(acov[c].size());
-      for (size_t t = 0; t < a.size(); ++t) a[t] = acov[c][t] / ((double)n * (double)M);
-      mcx_col_summary tmp;
-      std::fill(os.begin(), os.end(), 0.0f);
-      const double mean = cs[c] / (double)N, vm = cs[2 * ncol + c] / (double)(M - 1), va = ss[c] / (double)(N - 1);
-      MCXCHK(mcx_debug_summary_finish((int)n, (int)M, mean, va, vm, a.data(), (int)a.size(), os.data(), N, nullptr, 0, 0,
-                                      &tmp, nullptr, &need[c]));
-      active[c] = need[c] > 0 ? 1 : 0;
-    }
-  }
-  if (nwin_out) *nwin_out = nwin;
-  if (force_lags > 0) {
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-    for (int c = 0; c < ncol; ++c) {
-      const bool fin = std::isfinite(cs[c]);
-      if (fin && (int64_t)acov[c].size() < force_lags)
-        return fail(MCX_ERR_INVALID, "internal: column %d holds %d of %d lags", c, (int)acov[c].size(), force_lags);
-      for (int t = 0; t < force_lags; ++t) acov_out[(size_t)c * force_lags + t] = fin ? acov[c][t] : qnan;
-      sumsq_out[c] = fin ? ss[c] : qnan;
-    }
-    return MCX_OK;
-  }
-
-  // ---- 4. the host finish
-  for (int c = 0; c < ncol; ++c) {
-    for (int k = 0; k < nt; ++k) os[k] = key_float(pre[(size_t)c * nt + k]);
-    const bool fin = std::isfinite(cs[c]);
-    std::vector<double> a(acov[c].size());
-    for (size_t t = 0; t < a.size(); ++t) a[t] = acov[c][t] / ((double)n * (double)M);
-    const double mean = cs[c] / (double)N, vm = cs[2 * ncol + c] / (double)(M - 1), va = ss[c] / (double)(N - 1);
-    int more = 0;
-    MCXCHK(mcx_debug_summary_finish((int)n, (int)M, mean, va, vm, a.data(), (int)a.size(), os.data(), N, probs, nprobs,
-                                    fin ? 0 : MCX_SUMMARY_NONFINITE, &cols[c], quantiles ? quantiles + (size_t)c * nprobs : nullptr,
-                                    &more));
-    if (more && (parts & SUMM_ACOV)) return fail(MCX_ERR_INVALID, "internal: column %d still wants %d lags", c, more);
   }
   return MCX_OK;
 }
 
-int summary_device_parts(hipStream_t st, DevBuf<double> *d, DevBuf<unsigned long long> *h, DevBuf<uint32_t> *u, const float *x,
-                         const float *ly, int nc, int np, int64_t T, const double *probs, int nprobs, mcx_col_summary *cols,
-                         double *quantiles, int parts)
+// The one place that turns column c's sums into mcx_debug_summary_finish's arguments.  os: the column's order statistics;
+// need: how many lags its Geyer loop wants where it has too few (0: it is done)
+int finish_column(const SummaryPass &p, int c, const float *os, int nprobs, mcx_col_summary *col, double *quantiles, int *need)
 {
-  return summary_device(st, Bufs{d, h, u}, x, ly, nc, np, T, probs, nprobs, cols, quantiles, nullptr, 0, nullptr, nullptr, parts);
+  const StoreView &v = p.v;
+  std::vector<double> a(p.acov[c].size());
+  for (size_t t = 0; t < a.size(); ++t) a[t] = p.acov[c][t] / ((double)v.n * (double)v.M);
+  const double mean = p.cs[c] / (double)v.N, vm = p.cs[2 * v.ncol + c] / (double)(v.M - 1), va = p.ss[c] / (double)(v.N - 1);
+  return mcx_debug_summary_finish((int)v.n, (int)v.M, mean, va, vm, a.data(), (int)a.size(), os, v.N, p.probs, nprobs,
+                                  std::isfinite(p.cs[c]) ? 0 : MCX_SUMMARY_NONFINITE, col, quantiles, need);
 }
 
-static int summary_args(int nsteps, const double *probs, int nprobs, const mcx_col_summary *cols, const double *quantiles)
+// the normal rule of acov_windows: a column wants the lags its Geyer loop asks for
+int geyer_wants(const SummaryPass &p, int c, int *more)
+{
+  const float os[2] = {0.0f, 0.0f};
+  mcx_col_summary tmp;
+  return finish_column(p, c, os, 0, &tmp, nullptr, more);
+}
+
+// ---- 3. autocovariance windows -> acov, ss, nwin: 2, 4, 8, ... windows a launch (KWMAX and the half-chain's length cap
+// them) for the finite columns, while wants(p, c, &more) says that some column wants more lags than it holds
+template <class W> int acov_windows(SummaryPass &p, W wants)
+{
+  const StoreView &v = p.v;
+  const int ncol = v.ncol;
+  double *D = p.D;
+  std::vector<int> active(ncol);
+  for (int c = 0; c < ncol; ++c) active[c] = std::isfinite(p.cs[c]) ? 1 : 0;
+  const int nwin_max = (int)((v.n + WLAG - 1) / WLAG);
+  int k0 = 0, KW = 2;
+  std::vector<double> win;
+  while (k0 < nwin_max && std::count(active.begin(), active.end(), 1) > 0) {
+    KW = std::min({KW, KWMAX, nwin_max - k0});
+    MCXCHK(p.B.u->alloc(ncol));
+    HIPCHK(hipMemcpyAsync(p.B.u->p, active.data(), (size_t)ncol * 4, hipMemcpyHostToDevice, p.st));
+    for (const TileSet *t : {&v.tx, &v.tl}) {
+      hipLaunchKernelGGL(k_sum_acov, dim3((unsigned)(KW * t->ntiles * t->nbc)), dim3(SB), 0, p.st, *t, v.nc, v.T, v.n, k0, KW, ncol,
+                         D + p.o_hm, D + p.o_cs, (double)v.N, (const int *)p.B.u->p, D + p.o_part, p.pstride);
+      HIPCHK(hipGetLastError());
+    }
+    MCXCHK(p.rows(D + p.o_part, p.pstride, NQ, (size_t)KW * ncol * NQ, v.tx.nbc, v.tl.nbc, nullptr, 0.0, D + p.o_win));
+    win.resize((size_t)KW * ncol * NQ);
+    HIPCHK(hipMemcpyAsync(win.data(), D + p.o_win, win.size() * sizeof(double), hipMemcpyDeviceToHost, p.st));
+    HIPCHK(hipStreamSynchronize(p.st));
+    p.nwin += KW;
+    for (int c = 0; c < ncol; ++c) {
+      if (!active[c]) continue;
+      for (int y = 0; y < KW; ++y) {
+        const double *w = win.data() + ((size_t)y * ncol + c) * NQ;
+        for (int q = 0; q < WLAG && (int64_t)p.acov[c].size() < v.n; ++q) p.acov[c].push_back(w[q]);
+        if (k0 + y == 0) p.ss[c] = w[WLAG];
+      }
+      int more = 0;
+      MCXCHK(wants(p, c, &more));
+      active[c] = more > 0 ? 1 : 0;
+    }
+    k0 += KW;
+    KW *= 2;
+  }
+  for (int c = 0; c < ncol; ++c)
+    if (active[c]) return fail(MCX_ERR_INVALID, "internal: column %d holds %d lags and still wants more", c, (int)p.acov[c].size());
+  return MCX_OK;
+}
+
+// ---- 4. the host finish -> cols[ncol], quantiles[ncol][nprobs] (NULL when nprobs = 0)
+int finish_columns(const SummaryPass &p, mcx_col_summary *cols, double *quantiles)
+{
+  std::vector<float> os(p.nt);
+  for (int c = 0; c < p.v.ncol; ++c) {
+    for (int k = 0; k < p.nt; ++k) os[k] = key_float(p.pre[(size_t)c * p.nt + k]);
+    int more = 0;  // (acov_windows has seen to it where it ran; a pass without it reads no rhat or ess)
+    MCXCHK(finish_column(p, c, os.data(), p.nprobs, &cols[c], quantiles ? quantiles + (size_t)c * p.nprobs : nullptr, &more));
+  }
+  return MCX_OK;
+}
+
+// mcx_samples_summary / mcx_rows_summary: every phase
+int summary_full(SummaryPass &p, mcx_col_summary *cols, double *quantiles)
+{
+  MCXCHK(moments_pass(p));
+  MCXCHK(order_stats_pass(p));
+  MCXCHK(acov_windows(p, geyer_wants));
+  return finish_columns(p, cols, quantiles);
+}
+
+int summary_args(int nsteps, const double *probs, int nprobs, const mcx_col_summary *cols, const double *quantiles)
 {
   if (!cols) return fail(MCX_ERR_INVALID, "cols is NULL");
-  if (nsteps < 4) return fail(MCX_ERR_INVALID, "a summary needs nsteps >= 4 (two half-chains of >= 2 steps), got %d", nsteps);
+  MCXCHK(half_chain_args(nsteps));
   if (nprobs < 0 || nprobs > 32) return fail(MCX_ERR_INVALID, "nprobs = %d: 0 to 32 probabilities", nprobs);
   if (nprobs > 0 && (!probs || !quantiles)) return fail(MCX_ERR_INVALID, "probs and quantiles are needed when nprobs > 0");
   for (int k = 0; k < nprobs; ++k)
@@ -363,54 +405,95 @@ static int summary_args(int nsteps, const double *probs, int nprobs, const mcx_c
   return MCX_OK;
 }
 
+}  // namespace
+
+int summary_thresholds(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
+                       double *quantiles)
+{
+  const StoreView v(s);
+  SummaryPass p(st, B, v, probs, nprobs);
+  MCXCHK(moments_pass(p));
+  MCXCHK(order_stats_pass(p));
+  return finish_columns(p, cols, quantiles);
+}
+
+int summary_mixing(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_summary *cols)
+{
+  const StoreView v(s);
+  SummaryPass p(st, B, v, nullptr, 0);
+  MCXCHK(moments_pass(p));
+  MCXCHK(acov_windows(p, geyer_wants));
+  return finish_columns(p, cols, nullptr);
+}
+
 extern "C" int mcx_samples_summary(mcx_engine *e, int first_step, int nsteps, const double *probs, int nprobs,
                                    mcx_col_summary *cols, double *quantiles)
 {
-  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
-  MCXCHK(enter(e));
-  MCXCHK(summary_args(nsteps, probs, nprobs, cols, quantiles));
-  if (e->samp_steps == 0)
-    return fail(MCX_ERR_INVALID, "the sample store is empty (no run yet, MCX_OPT_SAMPLES = 0, or a run into a sink)");
-  if (first_step < 0 || (int64_t)first_step + nsteps > e->samp_steps)
-    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
-                (long long)first_step + nsteps, e->samp_steps);
-  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
-  return summary_device(e->stream, Bufs{&e->summ_d, &e->summ_h, &e->summ_u}, e->samp_x.p + (size_t)first_step * nc * np,
-                        e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np, nsteps, probs, nprobs, cols, quantiles,
-                        nullptr);
+  return on_store(
+      e, first_step, nsteps, [&] { return summary_args(nsteps, probs, nprobs, cols, quantiles); },
+      [&](hipStream_t st, Bufs B, const StoreView &v) {
+        SummaryPass p(st, B, v, probs, nprobs);
+        return summary_full(p, cols, quantiles);
+      });
 }
 
 extern "C" int mcx_rows_summary(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs,
                                 mcx_col_summary *cols, double *quantiles)
 {
   MCXCHK(summary_args(nsteps, probs, nprobs, cols, quantiles));
-  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
-    return summary_device(st, B, x, ly, nc, np, nsteps, probs, nprobs, cols, quantiles, nullptr);
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const StoreView &v) {
+    SummaryPass p(st, B, v, probs, nprobs);
+    return summary_full(p, cols, quantiles);
   });
 }
 
+// the raw sums of acov_windows, every finite column taking windows until it holds nlags lags (NaN for a column that is not)
 extern "C" int mcx_debug_rows_acov(const float *rows, int nsteps, int nc, int np, int nlags, double *acov, double *sumsq)
 {
-  if (nsteps < 4) return fail(MCX_ERR_INVALID, "a summary needs nsteps >= 4 (two half-chains of >= 2 steps), got %d", nsteps);
+  MCXCHK(half_chain_args(nsteps));
   if (nlags < 1 || nlags > nsteps / 2 || !acov || !sumsq)
     return fail(MCX_ERR_INVALID, "nlags = %d: 1 to n = %d lags, acov and sumsq not NULL", nlags, nsteps / 2);
-  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const float *x, const float *ly) {
-    return summary_device(st, B, x, ly, nc, np, nsteps, nullptr, 0, nullptr, nullptr, nullptr, nlags, acov, sumsq);
+  return on_rows(rows, nsteps, nc, np, [&](hipStream_t st, Bufs B, const StoreView &v) -> int {
+    SummaryPass p(st, B, v, nullptr, 0);
+    MCXCHK(moments_pass(p));
+    MCXCHK(acov_windows(p, [&](const SummaryPass &q, int c, int *more) {
+      *more = (int64_t)q.acov[c].size() < nlags ? 1 : 0;
+      return MCX_OK;
+    }));
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    for (int c = 0; c < v.ncol; ++c) {
+      const bool fin = std::isfinite(p.cs[c]);
+      for (int t = 0; t < nlags; ++t) acov[(size_t)c * nlags + t] = fin ? p.acov[c][t] : qnan;
+      sumsq[c] = fin ? p.ss[c] : qnan;
+    }
+    return MCX_OK;
   });
 }
 
 extern "C" int mcx_debug_summary_windows(mcx_engine *e, int first_step, int nsteps, int *nwin)
 {
-  if (!e || !nwin) return fail(MCX_ERR_INVALID, "bad arguments");
-  MCXCHK(enter(e));
-  if (e->samp_steps == 0 || first_step < 0 || nsteps < 4 || (int64_t)first_step + nsteps > e->samp_steps)
-    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
-                (long long)first_step + nsteps, e->samp_steps);
-  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
-  std::vector<mcx_col_summary> cols(np + 1);
-  return summary_device(e->stream, Bufs{&e->summ_d, &e->summ_h, &e->summ_u}, e->samp_x.p + (size_t)first_step * nc * np,
-                        e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np, nsteps, nullptr, 0, cols.data(), nullptr,
-                        nwin);
+  return on_store(
+      e, first_step, nsteps,
+      [&] {
+        if (!nwin) return fail(MCX_ERR_INVALID, "nwin is NULL");
+        return half_chain_args(nsteps);
+      },
+      [&](hipStream_t st, Bufs B, const StoreView &v) -> int {
+        std::vector<mcx_col_summary> cols(v.ncol);
+        SummaryPass p(st, B, v, nullptr, 0);
+        MCXCHK(summary_full(p, cols.data(), nullptr));
+        *nwin = p.nwin;
+        return MCX_OK;
+      });
+}
+
+extern "C" int mcx_debug_select_step(const unsigned long long hist[256], long long rem, int *digit, long long *rem_out)
+{
+  if (!hist || !digit || !rem_out || rem < 0) return fail(MCX_ERR_INVALID, "bad arguments");
+  int64_t r = 0;
+  *digit = select_step(hist, rem, &r);
+  *rem_out = r;
+  return MCX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1,15 +1,31 @@
-// mcx_summary_kernels.hpp -- what mcx_summary.hip, mcx_covariance.hip and mcx_ranks.hip need: the column tiles of the sample store,
-// pass 1 of every summary (k_sum_moments: per-series fp64 sums), the fixed-order reducer k_sum_rows that every cross-chain
-// or cross-workgroup sum goes through, and the upload of host rows to a scratch store (on_rows).  Internal to those three
-// translation units (each gets its own copy of the kernels); nothing here is part of the library's interface.
+// mcx_summary_kernels.hpp -- what mcx_summary.hip, mcx_covariance.hip and mcx_ranks.hip share: the column tiles of the sample
+// store and the one view of a store made of them (StoreView), the two ways to a view (on_store: a step range of an engine's
+// store; on_rows: host rows uploaded to a scratch store), pass 1 of every analysis (k_sum_moments: per-series fp64 sums), the
+// fixed-order reducer k_sum_rows that every cross-chain or cross-workgroup sum goes through, and the stage timer of the
+// mcx_debug_*_times entry points.  Internal to those three translation units (each gets its own copy of the kernels);
+// nothing here is part of the library's interface.
 #pragma once
 #include "mcx_engine_internal.hpp"
 
-// mcx_summary.hip's device passes for mcx_ranks.hip: summary_device with the parts (SUMM_*) a pass needs
-enum { SUMM_OSTAT = 1, SUMM_ACOV = 2 };
-MCXI int summary_device_parts(hipStream_t st, DevBuf<double> *d, DevBuf<unsigned long long> *h, DevBuf<uint32_t> *u,
-                              const float *x, const float *ly, int nc, int np, int64_t T, const double *probs, int nprobs,
-                              mcx_col_summary *cols, double *quantiles, int parts);
+// What crosses between the three units is plain: the scratch buffers of a call and a step range of a store on the device.
+// (TileSet is a type of each unit's own -- its kernels take it by value -- and so is the StoreView that holds two of them.)
+struct Bufs {
+  DevBuf<double> *d;
+  DevBuf<unsigned long long> *h;
+  DevBuf<uint32_t> *u;
+};
+struct StoreSpan {
+  const float *x, *ly;  // x[T][nc][np], ly[T][nc]
+  int nc, np;
+  int64_t T;
+};
+
+// mcx_summary.hip's passes for mcx_ranks.hip, each a subset of mcx_samples_summary's:
+// summary_thresholds: moments, order statistics, finish -- rhat, ess, ess_lag and mcse_mean of cols are not valid;
+// summary_mixing: moments, autocovariance windows, finish -- min and max of cols are not valid
+MCXI int summary_thresholds(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
+                            double *quantiles);
+MCXI int summary_mixing(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_summary *cols);
 
 namespace {
 
@@ -111,14 +127,47 @@ inline TileSet tiles_l(const float *ly, int nc, int np)
   return t;
 }
 
-struct Bufs {
-  DevBuf<double> *d;
-  DevBuf<unsigned long long> *h;
-  DevBuf<uint32_t> *u;
+// a step range of a store with everything the passes derive from it, formed once
+struct StoreView : StoreSpan {
+  int ncol;         // np + 1 columns: the parameters, then log L
+  int64_t N, n, M;  // values per column T * nc; steps per half-chain T / 2; half-chains 2 * nc
+  TileSet tx, tl;
+  explicit StoreView(const StoreSpan &s)
+      : StoreSpan(s), ncol(s.np + 1), N(s.T * (int64_t)s.nc), n(s.T / 2), M(2 * (int64_t)s.nc), tx(tiles_x(s.x, s.nc, s.np)),
+        tl(tiles_l(s.ly, s.nc, s.np))
+  {
+  }
 };
 
+// the text every analysis of half-chains refuses a short range with
+inline int half_chain_args(int nsteps)
+{
+  if (nsteps < 4) return fail(MCX_ERR_INVALID, "a summary needs nsteps >= 4 (two half-chains of >= 2 steps), got %d", nsteps);
+  return MCX_OK;
+}
+
+// Steps [first_step, first_step + nsteps) of an engine's store on the engine's stream, with its summ_* buffers:
+// f(st, bufs, view) runs the device passes there.  Every engine entry point of the three units comes through here, so
+// their checks have one order: 1. engine NULL, 2. the call's own arguments (args(), which may read *e), 3. enter,
+// 4. store empty, 5. range
+template <class A, class F> int on_store(mcx_engine *e, int first_step, int nsteps, A args, F f)
+{
+  if (!e) return fail(MCX_ERR_INVALID, "engine is NULL");
+  MCXCHK(args());
+  MCXCHK(enter(e));
+  if (e->samp_steps == 0)
+    return fail(MCX_ERR_INVALID, "the sample store is empty (no run yet, MCX_OPT_SAMPLES = 0, or a run into a sink)");
+  if (first_step < 0 || (int64_t)first_step + nsteps > e->samp_steps)
+    return fail(MCX_ERR_INVALID, "steps [%d,%lld) not in the sample store (%d steps)", first_step,
+                (long long)first_step + nsteps, e->samp_steps);
+  const size_t nc = (size_t)e->nchain, np = (size_t)e->nparam;
+  return f(e->stream, Bufs{&e->summ_d, &e->summ_h, &e->summ_u},
+           StoreView(StoreSpan{e->samp_x.p + (size_t)first_step * nc * np, e->samp_ly.p + (size_t)first_step * nc, (int)nc, (int)np,
+                               nsteps}));
+}
+
 // rows [nsteps * nc][np + 1] on the host (MCout layout) uploaded to a scratch store x, ly on a stream of its own:
-// f(st, bufs, x, ly) runs the device passes there
+// f(st, bufs, view) runs the device passes there
 template <class F> int on_rows(const float *rows, int nsteps, int nc, int np, F f)
 {
   if (!rows || nc < 1 || np < 1 || np > 256) return fail(MCX_ERR_INVALID, "bad arguments");
@@ -137,7 +186,7 @@ template <class F> int on_rows(const float *rows, int nsteps, int nc, int np, F 
     HIPCHK(hipMemcpyAsync(rd.p, rows, nr * (np + 1) * sizeof(float), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_sum_deinterleave, dim3(nblocks(nr * (np + 1))), dim3(BLOCK), 0, st, rd.p, nr, np, x.p, ly.p);
     HIPCHK(hipGetLastError());
-    return f(st, Bufs{&d, &h, &u}, x.p, ly.p);
+    return f(st, Bufs{&d, &h, &u}, StoreView(StoreSpan{x.p, ly.p, nc, np, nsteps}));
   };
   const int rc = run();
   if (st) {
@@ -147,5 +196,70 @@ template <class F> int on_rows(const float *rows, int nsteps, int nc, int np, F 
   rd.release(); x.release(); ly.release(); d.release(); h.release(); u.release();
   return rc;
 }
+
+// pass 1 of every analysis, in two launches' worth: sweep_moments is k_sum_moments over both tile sets -> hm[ncol][2][nc],
+// tot[ncol][nc]; column_sums adds tot over the chains -> colsum[ncol].  (Two names because mcx_debug_covariance_times
+// times the first alone.)
+inline int sweep_moments(hipStream_t st, const StoreView &v, double *hm, double *tot)
+{
+  for (const TileSet *t : {&v.tx, &v.tl}) {
+    hipLaunchKernelGGL(k_sum_moments, dim3((unsigned)(t->nbc * t->ntiles)), dim3(SB), 0, st, *t, v.nc, v.T, v.n, hm, tot);
+    HIPCHK(hipGetLastError());
+  }
+  return MCX_OK;
+}
+inline int column_sums(hipStream_t st, const StoreView &v, const double *tot, double *colsum)
+{
+  hipLaunchKernelGGL(k_sum_rows, dim3((unsigned)v.ncol), dim3(SB), 0, st, tot, (size_t)v.nc, 1, v.ncol, v.np, (size_t)v.nc,
+                     (size_t)v.nc, (const double *)nullptr, 0.0, colsum);
+  HIPCHK(hipGetLastError());
+  return MCX_OK;
+}
+inline int launch_moments(hipStream_t st, const StoreView &v, double *hm, double *tot, double *colsum)
+{
+  MCXCHK(sweep_moments(st, v, hm, tot));
+  return column_sums(st, v, tot, colsum);
+}
+
+// HIP events around the stages of a call: ms[slot] += the time of every run(slot, f).  With ms == NULL no event is
+// created or recorded and run() is f()
+struct StageTimer {
+  hipStream_t st;
+  double *ms;
+  int nslots;
+  struct Ev { int idx; hipEvent_t a, b; };
+  std::vector<Ev> evs;
+  template <class F> int run(int idx, F f)
+  {
+    if (!ms) return f();
+    Ev e{idx, nullptr, nullptr};
+    HIPCHK(hipEventCreate(&e.a));
+    HIPCHK(hipEventCreate(&e.b));
+    evs.push_back(e);
+    HIPCHK(hipEventRecord(e.a, st));
+    MCXCHK(f());
+    HIPCHK(hipEventRecord(e.b, st));
+    return MCX_OK;
+  }
+  int collect()
+  {
+    if (!ms) return MCX_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < nslots; ++i) ms[i] = 0.0;
+    for (const Ev &e : evs) {
+      float t = 0.0f;
+      HIPCHK(hipEventElapsedTime(&t, e.a, e.b));
+      ms[e.idx] += (double)t;
+    }
+    return MCX_OK;
+  }
+  ~StageTimer()
+  {
+    for (const Ev &e : evs) {
+      if (e.a) (void)hipEventDestroy(e.a);
+      if (e.b) (void)hipEventDestroy(e.b);
+    }
+  }
+};
 
 }  // namespace

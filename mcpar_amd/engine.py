@@ -308,6 +308,17 @@ def debug_summary_finish(n, M, mean, var_all, var_means, acov, ostat, N, probs=(
     return col[0], q[:len(p)], need.value
 
 
+def debug_select_step(hist, rem):
+    """mcx_debug_select_step (host only): one digit of the summary's radix select -- (digit, rank within its bucket) of the
+    target of rank rem among the keys that hist [256] counts by their next 8 bits"""
+    h = np.ascontiguousarray(hist, np.uint64)
+    if h.shape != (256,):
+        raise ValueError("hist must hold 256 counts")
+    digit, out = C.c_int(0), C.c_longlong(0)
+    check(load().mcx_debug_select_step(h.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(rem), C.byref(digit), C.byref(out)))
+    return digit.value, out.value
+
+
 def device_count():
     n = C.c_int(0)
     check(load().mcx_device_count(C.byref(n)))
@@ -641,63 +652,52 @@ class Engine:
             check(load().mcx_samples_text(self.h, first_step, nsteps, buf.ctypes.data_as(C.c_char_p), buf.size, C.byref(nb)))
         return nb.value
 
-    def summary(self, probs=(0.01, 0.5, 0.99), first_step=0, nsteps=None):
-        """mcx_samples_summary: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps)
-        -- a dict of arrays [np + 1]: mean, sd, min, max, rhat, ess, mcse_mean, ess_lag, flags; quantiles [np + 1, nprobs]"""
+    def _on_store(self, fn, first_step, nsteps, *args):
+        """fn(engine, first_step, nsteps, *args) of kept steps [first_step, first_step + nsteps) -- nsteps None: to the
+        end of the store --; McxError with mcx_last_error's text on a status other than 0"""
         if nsteps is None:
             ns = C.c_int(0)
             check(load().mcx_samples_steps(self.h, C.byref(ns)))
             nsteps = ns.value - first_step
+        check(fn(self.h, first_step, nsteps, *args))
+
+    def summary(self, probs=(0.01, 0.5, 0.99), first_step=0, nsteps=None):
+        """mcx_samples_summary: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps)
+        -- a dict of arrays [np + 1]: mean, sd, min, max, rhat, ess, mcse_mean, ess_lag, flags; quantiles [np + 1, nprobs]"""
         p, pp = _probs(probs)
         cols = np.zeros(self.np + 1, SUMMARY_DTYPE)
         q = np.zeros((self.np + 1, len(p)), np.float64)
-        check(load().mcx_samples_summary(self.h, first_step, nsteps, pp, len(p), cols.ctypes.data_as(C.c_void_p),
-                                         q.ctypes.data_as(C.POINTER(C.c_double))))
+        self._on_store(load().mcx_samples_summary, first_step, nsteps, pp, len(p), cols.ctypes.data_as(C.c_void_p),
+                       q.ctypes.data_as(C.POINTER(C.c_double)))
         return _summary_dict(cols, q)
 
     def rank_summary(self, first_step=0, nsteps=None):
         """mcx_samples_rank_summary: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps)
         -- a dict of arrays [np + 1]: rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, q05, median, q95,
         ess_bulk_lag, flags"""
-        if nsteps is None:
-            ns = C.c_int(0)
-            check(load().mcx_samples_steps(self.h, C.byref(ns)))
-            nsteps = ns.value - first_step
         cols = np.zeros(self.np + 1, RANK_SUMMARY_DTYPE)
-        check(load().mcx_samples_rank_summary(self.h, first_step, nsteps, cols.ctypes.data_as(C.c_void_p)))
+        self._on_store(load().mcx_samples_rank_summary, first_step, nsteps, cols.ctypes.data_as(C.c_void_p))
         return _rank_summary_dict(cols)
 
     def rank_summary_times(self, first_step=0, nsteps=None):
         """mcx_debug_rank_summary_times: the 20 stage times of one rank_summary() call in ms (include/mcx.h lists them)"""
-        if nsteps is None:
-            ns = C.c_int(0)
-            check(load().mcx_samples_steps(self.h, C.byref(ns)))
-            nsteps = ns.value - first_step
         ms = np.zeros(20)
-        check(load().mcx_debug_rank_summary_times(self.h, first_step, nsteps, _dp(ms)))
+        self._on_store(load().mcx_debug_rank_summary_times, first_step, nsteps, _dp(ms))
         return ms
 
     def covariance(self, first_step=0, nsteps=None):
         """mcx_samples_covariance of kept steps [first_step, first_step + nsteps): a dict of mean [np + 1] (summary()'s,
         bit for bit), cov and corr [np + 1, np + 1] (the parameters, then log L) and flags [np + 1]"""
-        if nsteps is None:
-            ns = C.c_int(0)
-            check(load().mcx_samples_steps(self.h, C.byref(ns)))
-            nsteps = ns.value - first_step
         ncol = self.np + 1
         mean, cov, flags = np.zeros(ncol), np.zeros((ncol, ncol)), np.zeros(ncol, np.int32)
-        check(load().mcx_samples_covariance(self.h, first_step, nsteps, _dp(mean), _dp(cov),
-                                            flags.ctypes.data_as(C.POINTER(C.c_int))))
+        self._on_store(load().mcx_samples_covariance, first_step, nsteps, _dp(mean), _dp(cov),
+                       flags.ctypes.data_as(C.POINTER(C.c_int)))
         return _covariance_dict(mean, cov, flags)
 
     def covariance_times(self, first_step=0, nsteps=None):
         """mcx_debug_covariance_times: ms of (the column-sum sweep, the covariance sweep, the partials' reducer) of one call"""
-        if nsteps is None:
-            ns = C.c_int(0)
-            check(load().mcx_samples_steps(self.h, C.byref(ns)))
-            nsteps = ns.value - first_step
         ms = np.zeros(3)
-        check(load().mcx_debug_covariance_times(self.h, first_step, nsteps, _dp(ms)))
+        self._on_store(load().mcx_debug_covariance_times, first_step, nsteps, _dp(ms))
         return ms
 
     def proposal_cov(self, scale=None, first_step=0, nsteps=None):
@@ -706,12 +706,8 @@ class Engine:
 
     def summary_windows(self, first_step=0, nsteps=None):
         """how many 32-lag autocovariance windows the summary of that range computes (mcx_debug_summary_windows)"""
-        if nsteps is None:
-            ns = C.c_int(0)
-            check(load().mcx_samples_steps(self.h, C.byref(ns)))
-            nsteps = ns.value - first_step
         nw = C.c_int(0)
-        check(load().mcx_debug_summary_windows(self.h, first_step, nsteps, C.byref(nw)))
+        self._on_store(load().mcx_debug_summary_windows, first_step, nsteps, C.byref(nw))
         return nw.value
 
     def maxlike(self):

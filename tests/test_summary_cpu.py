@@ -269,3 +269,57 @@ def test_debug_rows_acov_bad_arguments():
     for nsteps, nlags in ((8, 0), (8, 5), (3, 1)):
         with pytest.raises(McxError):
             E.debug_rows_acov(rows, nsteps, 2, nlags)
+
+
+# ---- mcx_debug_select_step: the digit walk of the radix select, driven from numpy -----------------------------------------
+def radix_select(keys, k):
+    """the k-th smallest of uint32 keys: four passes, most significant byte first; numpy histograms the keys that match the
+    prefix found so far, the library walks the histogram"""
+    keys = np.asarray(keys, np.uint32)
+    prefix, rem = 0, k
+    for p in range(4):
+        shift = 24 - 8 * p
+        under = keys[(keys.astype(np.uint64) >> (shift + 8)) == prefix]
+        hist = np.bincount((under >> np.uint32(shift)) & np.uint32(255), minlength=256)
+        digit, rem = E.debug_select_step(hist, rem)
+        assert 0 <= digit <= 255 and 0 <= rem < max(hist[digit], 1), (p, digit, rem)
+        prefix = (prefix << 8) | digit
+    return prefix
+
+
+SELECT_CASES = {
+    # name: (keys, target ranks)
+    "one key": ([0x12345678], [0]),
+    "all equal": ([0x80000001] * 7, [0, 3, 6]),
+    "first and last": ([5, 0xfffffffe, 0x01020304, 0x01020305, 0], [0, 4]),
+    # 0xff in every position: each pass ends at the b < 255 stop, before and behind smaller keys in the same buckets
+    "all bytes 0xff": ([0xffffffff, 0xffffff00, 0xff00ffff, 0x00ffffff, 0xffffffff, 0xfffffffe], [0, 3, 4, 5]),
+    # a run of duplicates (ranks 2 .. 6): inside it, on both of its ends, and its two neighbours
+    "duplicates": ([0x40000000, 0x40000001] + [0x40000100] * 5 + [0x40000101, 0x41000000], [1, 2, 3, 4, 6, 7]),
+    # two targets that share three bytes and differ in the last
+    "last byte": ([0xabcdef01, 0xabcdef02, 0xabcdee02, 0xabcdef00, 0xabcdf000], [1, 2, 3]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SELECT_CASES))
+def test_select_step_radix_select(name):
+    keys, ranks = SELECT_CASES[name]
+    keys = np.array(keys, np.uint32)
+    want = np.sort(keys)
+    rng = np.random.default_rng(len(name))
+    for order in (keys, keys[::-1], rng.permutation(keys)):  # the counts, not the order, decide
+        for k in ranks:
+            assert radix_select(order, k) == int(want[k]), (name, k)
+
+
+def test_select_step_stops_at_255():
+    """a rank past every count lands in bucket 255 (a histogram the device never makes: the walk must still end)"""
+    hist = np.zeros(256, np.uint64)
+    hist[3] = 2
+    assert E.debug_select_step(hist, 1) == (3, 1)
+    assert E.debug_select_step(hist, 2) == (255, 0)
+    assert E.debug_select_step(hist, 9) == (255, 7)
+    hist[255] = 4
+    assert E.debug_select_step(hist, 5) == (255, 3)
+    with pytest.raises(McxError):
+        E.debug_select_step(hist, -1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compile the translation units of libmcx with -save-temps and summarise one kernel: registers and the instruction
 mix of its biggest loop.  usage: tools/kernel_asm.py <mangled-name-substring> [--dump]
-       tools/kernel_asm.py --compare DIR_A DIR_B: two sets of <unit>.s files (hipcc <Makefile's flags> --cuda-device-only -S),
+       tools/kernel_asm.py --compare DIR_A DIR_B [UNIT ...]: two sets of <unit>.s files (the step kernels' units, or UNIT ...) (hipcc <Makefile's flags> --cuda-device-only -S),
        kernel by kernel: how many instruction streams are the same, and size / registers / LDS / scratch / occupancy of the rest
 
 The biggest loop is the biggest INNERMOST one (a backward branch whose span holds no other): the hot kernels' step
@@ -90,10 +90,10 @@ def instruction_stream(body):
     return out
 
 
-def compare(dir_a, dir_b):
+def compare(dir_a, dir_b, units=STEP_UNITS):
     """one markdown table per translation unit; returns the number of kernels with new scratch or lower occupancy"""
     bad = 0
-    for tu in STEP_UNITS:
+    for tu in units:
         a, b = (open(os.path.join(d, tu + ".s")).read() for d in (dir_a, dir_b))
         names = re.findall(r"\.amdhsa_kernel (\w+)", a)
         assert names == re.findall(r"\.amdhsa_kernel (\w+)", b), tu + ": the two sets hold different kernels"
@@ -118,7 +118,7 @@ def compare(dir_a, dir_b):
 
 def main():
     if sys.argv[1] == "--compare":
-        return 1 if compare(sys.argv[2], sys.argv[3]) else 0
+        return 1 if compare(sys.argv[2], sys.argv[3], tuple(sys.argv[4:]) or STEP_UNITS) else 0
     pat = sys.argv[1]
     s = ""
     for tu in ("mcx_k_fast", "mcx_k_fast_full", "mcx_k_fastb", "mcx_k_fastb_full", "mcx_k_pregen", "mcx_k_generic_main", "mcx_k_generic_burn", "mcx_engine"):
