@@ -428,6 +428,66 @@ int mcx_rows_covariance(const float *rows, int nsteps, int nc, int np, double *m
  * pivot named in mcx_last_error, when an entry is not finite or the float Cholesky mcx_covar_setup uses rejects it. */
 int mcx_proposal_from_cov(int np, const double *cov, int ld, double scale, float *incov);
 
+/* ---- derived columns and bootstrap draws of the sample store, on the device ----
+ * The reference's mcparam.sample(mc.data, nsamp, func) (src/anly/mcpar-analysis.R:30-47).  A function f maps one row
+ * (x[0..np-1], ly) to nout floats, 1 <= nout <= 256.  One sweep over a step range applies it to every row and writes a store
+ * of the same shape: nout derived columns, then log L, copied, as the last column.  The same store and arguments give the
+ * same bytes.
+ *   MCX_DERIVE_LINEAR  par = A[nout][np] row-major, then b[nout]: npar = nout * (np + 1).  out[j]: acc = b[j], then for
+ *                      k = 0 .. np-1 in that order acc = acc + A[j][k] * x[k], the product and the sum each rounded to
+ *                      float32 (not an fma chain).  Compiled into the library: needs no hiprtc.
+ *   MCX_DERIVE_SOURCE  source = NUL-terminated HIP text that defines, in the global namespace,
+ *
+ *     __device__ void mcx_user_derive(const float *x, int d, float ly, const float *par, float *out, int nout);
+ *
+ *                      par = the npar floats of the spec (may be 0 / NULL).  x and out point to on-chip memory: x[0..d-1]
+ *                      is one row, out[0..nout-1] is written by the function (what it leaves unwritten is unspecified).
+ *                      The function is called for rows of the range only, never for a lane without a row: it never sees
+ *                      values that no run produced.  "mcx_numerics.hpp" is already included; MCX_DERIVE_NP (= np) and
+ *                      MCX_DERIVE_NOUT (= nout) are defined.  Compiled like an MCX_VL_SOURCE text (-O3 -ffp-contract=off),
+ *                      once per (text, np, nout) per process; a text that does not compile gives MCX_ERR_VLFUNC with the
+ *                      compiler's messages under the text's own line numbers ("mcx_user_derive:LINE") in
+ *                      mcx_last_error(); without libhiprtc MCX_ERR_UNSUPPORTED. */
+enum { MCX_DERIVE_LINEAR = 1, MCX_DERIVE_SOURCE = 2 };
+typedef struct mcx_derive {
+  int kind;           /* MCX_DERIVE_* */
+  int nout;           /* outputs per row, 1 to 256 */
+  int npar;           /* floats in par */
+  const float *par;   /* copied by the call */
+  const char *source; /* SOURCE: the text */
+} mcx_derive;
+/* A derived store: it owns its device memory, a stream and the scratch of its analyses, and does not depend on the engine
+ * it was derived from -- a later mcx_run or mcx_destroy of that engine leaves it intact.  One thread at a time per store. */
+typedef struct mcx_store mcx_store;
+/* Steps [first_step, first_step + nsteps) of the engine's store, nsteps >= 1: refused as mcx_samples_summary refuses a
+ * range the store does not hold; a queued MCX_OPT_ASYNC_RUN run is finished first. */
+int mcx_samples_derive(mcx_engine *e, int first_step, int nsteps, const mcx_derive *f, mcx_store **out);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows), np <= 256 */
+int mcx_rows_derive(const float *rows, int nsteps, int nc, int np, const mcx_derive *f, mcx_store **out);
+int mcx_store_destroy(mcx_store *s);
+int mcx_store_shape(const mcx_store *s, int *nsteps, int *nc, int *ncol);      /* ncol = nout + 1 */
+int mcx_store_copy(mcx_store *s, int first_step, int nsteps, float *rows);     /* MCout layout: rows[nsteps * nc][ncol] */
+/* mcx_samples_summary, mcx_samples_rank_summary and mcx_samples_covariance of the whole derived store: the same device
+ * passes under the same rules (nsteps >= 4 for the first two, nsteps * nc >= 2 for the third, MCX_SUMMARY_NONFINITE for
+ * a column in which f produced an inf or NaN); cols[ncol], quantiles[ncol * nprobs], mean[ncol], cov[ncol * ncol] */
+int mcx_store_summary(mcx_store *s, const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles);
+int mcx_store_rank_summary(mcx_store *s, mcx_col_rank_summary *cols);
+int mcx_store_covariance(mcx_store *s, double *mean, double *cov, int *flags);
+/* the compile step of an MCX_DERIVE_SOURCE text alone (needs no GPU): MCX_OK and the code object's size, or MCX_ERR_VLFUNC */
+int mcx_debug_derive_compile(const char *source, int np, int nout, size_t *code_bytes);
+
+/* Bootstrap draws: ndraw rows of the range (of the derived store), with replacement, as the reference's
+ * sample.int(..., replace = TRUE).  The row of draw i among the N = nsteps * nc rows depends on (seed, i, N) only:
+ *   w = Philox4x32-10(counter = (i & 0xffffffff, i >> 32, 0, 0), key = (seed, 5)), r = (w.x << 32) | w.y,
+ *   index = (r * N) >> 64 (the high half of the 128-bit product); row index is step index / nc, chain index % nc.
+ * (Stream 5: a run uses streams 0 to 4 of its seed.)  So mcx_samples_draw on a range and mcx_store_draw on the store derived
+ * from that range pick the same rows: the derived draws are f of the draws.  rows[ndraw][ncol] in MCout layout, gathered on
+ * the device; index[ndraw] may be NULL; ndraw = 0 is allowed. */
+int mcx_samples_draw(mcx_engine *e, int first_step, int nsteps, uint32_t seed, int64_t ndraw, float *rows, int64_t *index);
+int mcx_store_draw(mcx_store *s, uint32_t seed, int64_t ndraw, float *rows, int64_t *index);
+/* host only: index[k] = the row of draw first + k among N rows, k < n */
+int mcx_debug_draw_indices(uint32_t seed, uint64_t N, uint64_t first, int n, int64_t *index);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote
@@ -556,6 +616,9 @@ int mcx_debug_select_step(const unsigned long long hist[256], long long rem, int
  * on its mean (n M times the acov of mcx_debug_summary_finish); sumsq[np + 1]: sum over all N values of (x - mean)^2.
  * A column that is not finite gets NaN in both. */
 int mcx_debug_rows_acov(const float *rows, int nsteps, int nc, int np, int nlags, double *acov, double *sumsq);
+/* mcx_samples_derive with HIP events around the sweep, for tools/derive_bench.py: the sweep runs twice into the same derived
+ * store, ms[0] = the time of the second in ms; the store is let go */
+int mcx_debug_derive_times(mcx_engine *e, int first_step, int nsteps, const mcx_derive *f, double *ms);
 /* mcx_samples_covariance with HIP events around its device passes, for tools/covariance_bench.py: ms[0] the column-sum
  * sweep (k_sum_moments, the pass mcx_samples_summary shares), ms[1] the covariance sweep, ms[2] the reducer of its partials */
 int mcx_debug_covariance_times(mcx_engine *e, int first_step, int nsteps, double *ms);

@@ -9,6 +9,9 @@ from ._lib import McxError, load, lib_path  # noqa: F401
 from .engine import (Engine, VL_DEVICE, VL_SOURCE, VL_DUALGAUSS, VL_GAUSSIAN, VL_GAUSSMIX, VL_HOST,  # noqa: F401
                      VL_ROSENBROCK1, VL_ROSENBROCK2, debug_normals, debug_numerics, device_info,
                      make_vlfunc, vlfunc_eval)
+from .engine import (DerivedStore, debug_derive_compile, debug_draw_indices, derive_linear, derive_rows,  # noqa: F401
+                     derive_source, user_source_available)
 
 __all__ = ["Engine", "McxError", "load", "lib_path", "make_vlfunc", "vlfunc_eval", "device_info",
-           "debug_numerics", "debug_normals"]
+           "debug_numerics", "debug_normals", "DerivedStore", "derive_linear", "derive_source", "derive_rows",
+           "debug_draw_indices", "debug_derive_compile", "user_source_available"]

@@ -23,6 +23,12 @@ class VLFunc(C.Structure):
                 ("params", C.POINTER(C.c_float)), ("fn", HOSTFN), ("ctx", C.c_void_p)]
 
 
+class Derive(C.Structure):
+    """include/mcx.h mcx_derive"""
+    _fields_ = [("kind", C.c_int), ("nout", C.c_int), ("npar", C.c_int), ("par", C.POINTER(C.c_float)),
+                ("source", C.c_char_p)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -109,6 +115,19 @@ def load():
         "mcx_debug_rows_rank_transform": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, fp],
         "mcx_debug_normal_quantile": [dp, C.c_int, dp],
         "mcx_debug_rank_summary_times": [vp, C.c_int, C.c_int, dp],
+        "mcx_samples_derive": [vp, C.c_int, C.c_int, C.POINTER(Derive), C.POINTER(vp)],
+        "mcx_rows_derive": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(Derive), C.POINTER(vp)],
+        "mcx_store_destroy": [vp],
+        "mcx_store_shape": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+        "mcx_store_copy": [vp, C.c_int, C.c_int, fp],
+        "mcx_store_summary": [vp, dp, C.c_int, vp, dp],
+        "mcx_store_rank_summary": [vp, vp],
+        "mcx_store_covariance": [vp, dp, dp, C.POINTER(C.c_int)],
+        "mcx_debug_derive_compile": [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)],
+        "mcx_debug_derive_times": [vp, C.c_int, C.c_int, C.POINTER(Derive), dp],
+        "mcx_samples_draw": [vp, C.c_int, C.c_int, C.c_uint32, C.c_int64, fp, C.POINTER(C.c_int64)],
+        "mcx_store_draw": [vp, C.c_uint32, C.c_int64, fp, C.POINTER(C.c_int64)],
+        "mcx_debug_draw_indices": [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int64)],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

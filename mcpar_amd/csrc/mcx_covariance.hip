@@ -201,6 +201,12 @@ static int covariance_args(int nsteps, int nc, const double *mean, const double 
   return MCX_OK;
 }
 
+int covariance_span(hipStream_t st, Bufs B, const StoreSpan &s, double *mean, double *cov, int *flags)
+{
+  MCXCHK(covariance_args((int)s.T, s.nc, mean, cov));
+  return covariance_device(st, B.d, StoreView(s), mean, cov, flags, nullptr);
+}
+
 extern "C" int mcx_samples_covariance(mcx_engine *e, int first_step, int nsteps, double *mean, double *cov, int *flags)
 {
   return on_store(

@@ -39,6 +39,7 @@ typedef enum { ncclFloat = 7 } ncclDataType_t;
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -156,6 +157,12 @@ int user_lik_variant(int lpc, const SegArgs &a);  // 0 hot-path kernel, 1 its fu
 double user_lik_compile_ms(const UserLik &u);
 bool user_lik_small_ok(const UserLik &u);  // block form, <= 8 lanes per chain: the one-launch small-n kernel can be built for it
 hipError_t user_lik_launch_small(UserLik &u, int bpl, const RunArgs &a, hipStream_t st, StepLedger *led);  // (mcxk_launch_persist's role)
+// mcx_user.hip's way to hiprtc, for mcx_derive.hip: HIP text -> code object for gfx950 with the library's own flags and the
+// embedded kernel headers; MCX_ERR_UNSUPPORTED without libhiprtc, MCX_ERR_VLFUNC + the compiler's log ("the <what> source does
+// not compile") for a text that does not build.  One compilation at a time: call it holding rtc_lock()
+MCXI std::mutex &rtc_lock();
+MCXI int rtc_compile(const std::string &src, const char *name, const std::vector<std::string> &defs, std::vector<char> &code,
+                     std::string &log, const char *what = "likelihood");
 
 struct LikDev {
   int kind = 0;  // LikKind, or MCX_VL_HOST / MCX_VL_DEVICE

@@ -475,6 +475,12 @@ int rank_args(int nsteps, const void *cols)
 
 }  // namespace
 
+int rank_span(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_rank_summary *cols)
+{
+  MCXCHK(rank_args((int)s.T, cols));
+  return rank_device(st, B, StoreView(s), cols, nullptr, nullptr);
+}
+
 extern "C" int mcx_samples_rank_summary(mcx_engine *e, int first_step, int nsteps, mcx_col_rank_summary *cols)
 {
   return on_store(

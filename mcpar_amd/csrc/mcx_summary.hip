@@ -426,6 +426,14 @@ int summary_mixing(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_summary *
   return finish_columns(p, cols, nullptr);
 }
 
+int summary_span(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles)
+{
+  MCXCHK(summary_args((int)s.T, probs, nprobs, cols, quantiles));
+  const StoreView v(s);
+  SummaryPass p(st, B, v, probs, nprobs);
+  return summary_full(p, cols, quantiles);
+}
+
 extern "C" int mcx_samples_summary(mcx_engine *e, int first_step, int nsteps, const double *probs, int nprobs,
                                    mcx_col_summary *cols, double *quantiles)
 {

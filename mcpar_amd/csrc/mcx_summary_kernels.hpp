@@ -1,8 +1,11 @@
 // mcx_summary_kernels.hpp -- what mcx_summary.hip, mcx_covariance.hip and mcx_ranks.hip share: the column tiles of the sample
 // store and the one view of a store made of them (StoreView), the two ways to a view (on_store: a step range of an engine's
-// store; on_rows: host rows uploaded to a scratch store), pass 1 of every analysis (k_sum_moments: per-series fp64 sums), the
+// store; on_rows: host rows uploaded to a scratch store; mcx_derive.hip comes through both to read a span, and its derived
+// store is a third way: a span handed to summary_span / rank_span / covariance_span below), pass 1 of every analysis (k_sum_moments: per-series fp64 sums), the
 // fixed-order reducer k_sum_rows that every cross-chain or cross-workgroup sum goes through, and the stage timer of the
-// mcx_debug_*_times entry points.  Internal to those three translation units (each gets its own copy of the kernels);
+// mcx_debug_*_times entry points.  Internal to the three analysis units (each gets its own copy of the kernels).
+// mcx_derive.hip includes it for the view plumbing alone (on_store, on_rows with its k_sum_deinterleave, StageTimer); the
+// other kernels' copies in that unit are never launched;
 // nothing here is part of the library's interface.
 #pragma once
 #include "mcx_engine_internal.hpp"
@@ -26,6 +29,13 @@ struct StoreSpan {
 MCXI int summary_thresholds(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
                             double *quantiles);
 MCXI int summary_mixing(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_summary *cols);
+
+// The three analyses on any span, for the third way to a view (mcx_derive.hip: a derived store): each checks its own
+// arguments as its mcx_samples_* entry point does, then runs the passes of that entry point on a StoreView of the span
+MCXI int summary_span(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
+                      double *quantiles);                                                          // mcx_summary.hip
+MCXI int rank_span(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_rank_summary *cols);        // mcx_ranks.hip
+MCXI int covariance_span(hipStream_t st, Bufs B, const StoreSpan &s, double *mean, double *cov, int *flags);  // mcx_covariance.hip
 
 namespace {
 

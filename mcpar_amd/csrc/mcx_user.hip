@@ -67,17 +67,23 @@ bool rtc_load()
 const char *const RTC_FLAGS[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
                                  "-fno-gpu-flush-denormals-to-zero", "-Wno-unused-function"};
 
-// source -> code object; log = the compiler's words on failure
-int rtc_compile(const std::string &src, const char *name, const std::vector<std::string> &defs, std::vector<char> &code, std::string &log)
+}  // namespace
+
+std::mutex &rtc_lock() { return g_user_m; }
+
+// source -> code object; log = the compiler's words on failure.  Under rtc_lock().  what: whose text it is, for the refusal
+int rtc_compile(const std::string &src, const char *name, const std::vector<std::string> &defs, std::vector<char> &code, std::string &log,
+                const char *what)
 {
   if (!rtc_load()) return fail(MCX_ERR_UNSUPPORTED, "run-time compilation unavailable: %s", g_rtc.why.c_str());
   // (a user's text may well start with #include <hip/hip_runtime.h>: hiprtc has the runtime's declarations built in and no
   // such file, so an empty one stands in)
-  const char *hn[] = {"mcx_numerics.hpp", "mcx_block.hpp", "mcx_device.hpp", "mcx_fastb.hpp", "mcx_persist.hpp", "hip/hip_runtime.h"};
-  const char *hs[] = {k_hdr_mcx_numerics, k_hdr_mcx_block, k_hdr_mcx_device, k_hdr_mcx_fastb, k_hdr_mcx_persist,
+  const char *hn[] = {"mcx_numerics.hpp", "mcx_block.hpp", "mcx_device.hpp", "mcx_fastb.hpp", "mcx_persist.hpp", "mcx_derive.hpp",
+                      "hip/hip_runtime.h"};
+  const char *hs[] = {k_hdr_mcx_numerics, k_hdr_mcx_block, k_hdr_mcx_device, k_hdr_mcx_fastb, k_hdr_mcx_persist, k_hdr_mcx_derive,
                       "// the HIP runtime declarations are built into hiprtc\n"};
   rtcProgram prog = nullptr;
-  int r = g_rtc.CreateProgram(&prog, src.c_str(), name, 6, hs, hn);
+  int r = g_rtc.CreateProgram(&prog, src.c_str(), name, 7, hs, hn);
   if (r != 0) return fail(MCX_ERR_HIP, "hiprtcCreateProgram: %s", g_rtc.GetErrorString(r));
   std::vector<const char *> opts(std::begin(RTC_FLAGS), std::end(RTC_FLAGS));
   for (const std::string &d : defs) opts.push_back(d.c_str());
@@ -92,7 +98,7 @@ int rtc_compile(const std::string &src, const char *name, const std::vector<std:
     (void)g_rtc.DestroyProgram(&prog);
     // the tail is where clang puts the error count; the head is where the first error is: keep both ends
     std::string shown = log.size() > 3000 ? log.substr(0, 2200) + "\n[...]\n" + log.substr(log.size() - 600) : log;
-    return fail(MCX_ERR_VLFUNC, "the likelihood source does not compile (%s):\n%s", g_rtc.GetErrorString(r), shown.c_str());
+    return fail(MCX_ERR_VLFUNC, "the %s source does not compile (%s):\n%s", what, g_rtc.GetErrorString(r), shown.c_str());
   }
   size_t nb = 0;
   r = g_rtc.GetCodeSize(prog, &nb);
@@ -104,6 +110,8 @@ int rtc_compile(const std::string &src, const char *name, const std::vector<std:
   if (r != 0) return fail(MCX_ERR_HIP, "hiprtcGetCode: %s", g_rtc.GetErrorString(r));
   return MCX_OK;
 }
+
+namespace {
 
 // What the run-time translation unit looks like around the user's text.  The user's functions live in the global
 // namespace and may use mcx_numerics.hpp (mcx::logf_v1, mcx::expf_v2, ... -- the functions the built-ins and the CPU

@@ -4,6 +4,9 @@
 //             [--nc CHAINS] [--nsamp N] [--nburn B] [--pl P] [--sync S] [--ncomp K] [--quiet] [--iter] [--binary]
 //             [--stream-text] [--out FILE] [--summary FILE] [--rank-summary FILE] [--covariance FILE] [--proposal FILE]
 //             [--incov FILE]
+//             [--derive-source FILE.hip --derive-nout K [--derive-par a,b,...] | --derive-linear FILE]
+//             [--derived-summary FILE] [--derived-rank-summary FILE] [--derived-covariance FILE]
+//             [--draws FILE --ndraw N [--draw-seed S]]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -19,6 +22,13 @@
 // parameter block as the proposal covariance of a next run (mcx_proposal_from_cov, scale 2.38^2 / np).  Both under the
 // conditions of --summary.  --incov FILE: np * np whitespace-separated numbers, the proposal covariance of this run
 // (MCPar::run's incov) -- `--proposal P.txt` of a pilot run, then `--incov P.txt`, is the adaptive two-stage job.
+// --derive-source / --derive-linear: a function of one kept row (its np parameters and log L) to K derived columns
+// (mcx_rows_derive; mcpar_amd/examples/derive_*.hip): a user's HIP text defining mcx_user_derive with --derive-nout outputs
+// and --derive-par as its `par`, or FILE holding K rows of np + 1 numbers, a row of A and then b, for out = b + A x.
+// --derived-summary, --derived-rank-summary, --derived-covariance FILE: the files of --summary, --rank-summary and
+// --covariance for the derived columns d0 .. d{K-1}, then LL (mcx_store_summary, ...).  Under the conditions of --summary.
+// --draws FILE --ndraw N [--draw-seed S]: N of the kept rows drawn with replacement, as the text of the sample output; the
+// row of draw i is mcx_samples_draw's (mcx_debug_draw_indices of seed S, default 8675309).  Under the conditions of --summary.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -35,20 +45,14 @@
 
 #include "../csrc/fmt_g6.hpp"
 
-// --summary: the per-column statistics of MCout's rows, one row per column
-static int write_summary(const char *path, MCout &rows, int nsamp, int nc, int np)
+static const double SUMMARY_PROBS[3] = {0.01, 0.5, 0.99};
+
+// column c of np columns and log L: p0 .. (the parameters) or d0 .. (derived columns), then LL
+static std::string colname(char prefix, int c, int np) { return c < np ? prefix + std::to_string(c) : "LL"; }
+
+// the files' writers: np named columns, then LL
+static int print_summary(const char *path, const std::vector<mcx_col_summary> &cols, const std::vector<double> &q, int np, char prefix)
 {
-  const double probs[3] = {0.01, 0.5, 0.99};
-  std::vector<mcx_col_summary> cols((size_t)np + 1);
-  std::vector<double> q(((size_t)np + 1) * 3);
-  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 4) {
-    std::cerr << "--summary: " << rows.size() << " rows stored, a summary needs nsamp * nc of them and nsamp >= 4\n";
-    return 1;
-  }
-  if (mcx_rows_summary(rows.getpset(0), nsamp, nc, np, probs, 3, cols.data(), q.data()) != MCX_OK) {
-    std::cerr << "--summary: " << mcx_last_error() << "\n";
-    return 1;
-  }
   FILE *f = fopen(path, "w");
   if (!f) {
     std::cerr << "cannot open " << path << "\n";
@@ -58,9 +62,40 @@ static int write_summary(const char *path, MCout &rows, int nsamp, int nc, int n
   for (int c = 0; c <= np; ++c) {
     const mcx_col_summary &s = cols[c];
     const double *qc = q.data() + (size_t)c * 3;
-    std::string name = c < np ? "p" + std::to_string(c) : "LL";
-    fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", name.c_str(), s.mean, s.sd, qc[0], qc[1], qc[2],
+    fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", colname(prefix, c, np).c_str(), s.mean, s.sd, qc[0], qc[1], qc[2],
             s.rhat, s.ess, s.mcse_mean);
+  }
+  return fclose(f) == 0 ? 0 : 1;
+}
+
+// --summary: the per-column statistics of MCout's rows, one row per column
+static int write_summary(const char *path, MCout &rows, int nsamp, int nc, int np)
+{
+  std::vector<mcx_col_summary> cols((size_t)np + 1);
+  std::vector<double> q(((size_t)np + 1) * 3);
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 4) {
+    std::cerr << "--summary: " << rows.size() << " rows stored, a summary needs nsamp * nc of them and nsamp >= 4\n";
+    return 1;
+  }
+  if (mcx_rows_summary(rows.getpset(0), nsamp, nc, np, SUMMARY_PROBS, 3, cols.data(), q.data()) != MCX_OK) {
+    std::cerr << "--summary: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  return print_summary(path, cols, q, np, 'p');
+}
+
+static int print_rank_summary(const char *path, const std::vector<mcx_col_rank_summary> &cols, int np, char prefix)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "name rhat rhat_bulk rhat_folded ess_bulk ess_tail ess_q05 ess_q95 q05 q50 q95 ess_bulk_lag flags\n");
+  for (int c = 0; c <= np; ++c) {
+    const mcx_col_rank_summary &s = cols[c];
+    fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %d\n", colname(prefix, c, np).c_str(), s.rhat, s.rhat_bulk,
+            s.rhat_folded, s.ess_bulk, s.ess_tail, s.ess_q05, s.ess_q95, s.q05, s.median, s.q95, s.ess_bulk_lag, s.flags);
   }
   return fclose(f) == 0 ? 0 : 1;
 }
@@ -77,17 +112,24 @@ static int write_rank_summary(const char *path, MCout &rows, int nsamp, int nc, 
     std::cerr << "--rank-summary: " << mcx_last_error() << "\n";
     return 1;
   }
+  return print_rank_summary(path, cols, np, 'p');
+}
+
+static int print_covariance(const char *path, const std::vector<double> &mean, const std::vector<double> &cov, int np, char prefix)
+{
+  const size_t ncol = (size_t)np + 1;
   FILE *f = fopen(path, "w");
   if (!f) {
     std::cerr << "cannot open " << path << "\n";
     return 1;
   }
-  fprintf(f, "name rhat rhat_bulk rhat_folded ess_bulk ess_tail ess_q05 ess_q95 q05 q50 q95 ess_bulk_lag flags\n");
+  fprintf(f, "name mean");
+  for (int c = 0; c <= np; ++c) fprintf(f, " %s", colname(prefix, c, np).c_str());
+  fprintf(f, "\n");
   for (int c = 0; c <= np; ++c) {
-    const mcx_col_rank_summary &s = cols[c];
-    std::string name = c < np ? "p" + std::to_string(c) : "LL";
-    fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %d\n", name.c_str(), s.rhat, s.rhat_bulk,
-            s.rhat_folded, s.ess_bulk, s.ess_tail, s.ess_q05, s.ess_q95, s.q05, s.median, s.q95, s.ess_bulk_lag, s.flags);
+    fprintf(f, "%s %.17g", colname(prefix, c, np).c_str(), mean[c]);
+    for (int k = 0; k <= np; ++k) fprintf(f, " %.17g", cov[c * ncol + k]);
+    fprintf(f, "\n");
   }
   return fclose(f) == 0 ? 0 : 1;
 }
@@ -105,22 +147,7 @@ static int write_covariance(const char *cov_path, const char *prop_path, MCout &
     std::cerr << "--covariance / --proposal: " << mcx_last_error() << "\n";
     return 1;
   }
-  if (cov_path) {
-    FILE *f = fopen(cov_path, "w");
-    if (!f) {
-      std::cerr << "cannot open " << cov_path << "\n";
-      return 1;
-    }
-    fprintf(f, "name mean");
-    for (int c = 0; c <= np; ++c) fprintf(f, " %s", c < np ? ("p" + std::to_string(c)).c_str() : "LL");
-    fprintf(f, "\n");
-    for (int c = 0; c <= np; ++c) {
-      fprintf(f, "%s %.17g", c < np ? ("p" + std::to_string(c)).c_str() : "LL", mean[c]);
-      for (int k = 0; k <= np; ++k) fprintf(f, " %.17g", cov[c * ncol + k]);
-      fprintf(f, "\n");
-    }
-    if (fclose(f) != 0) return 1;
-  }
+  if (cov_path && print_covariance(cov_path, mean, cov, np, 'p') != 0) return 1;
   if (prop_path) {
     std::vector<float> prop((size_t)np * np);
     if (mcx_proposal_from_cov(np, cov.data(), np + 1, 0.0, prop.data()) != MCX_OK) {
@@ -137,6 +164,115 @@ static int write_covariance(const char *cov_path, const char *prop_path, MCout &
     if (fclose(f) != 0) return 1;
   }
   return 0;
+}
+
+// --derived-*: the three files for the K derived columns of MCout's rows, through one derived store on the device
+static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, MCout &rows, int nsamp,
+                         int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--derived-*: " << rows.size() << " rows stored, a derive needs nsamp * nc of them\n";
+    return 1;
+  }
+  mcx_store *st = 0;
+  if (mcx_rows_derive(rows.getpset(0), nsamp, nc, np, &spec, &st) != MCX_OK) {
+    std::cerr << "--derive-*: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  const int K = spec.nout;
+  int rc = 0;
+  if (sum_path) {
+    std::vector<mcx_col_summary> cols((size_t)K + 1);
+    std::vector<double> q(((size_t)K + 1) * 3);
+    if (mcx_store_summary(st, SUMMARY_PROBS, 3, cols.data(), q.data()) != MCX_OK) {
+      std::cerr << "--derived-summary: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_summary(sum_path, cols, q, K, 'd');
+  }
+  if (rc == 0 && rank_path) {
+    std::vector<mcx_col_rank_summary> cols((size_t)K + 1);
+    if (mcx_store_rank_summary(st, cols.data()) != MCX_OK) {
+      std::cerr << "--derived-rank-summary: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_rank_summary(rank_path, cols, K, 'd');
+  }
+  if (rc == 0 && cov_path) {
+    std::vector<double> mean((size_t)K + 1), cov(((size_t)K + 1) * ((size_t)K + 1));
+    if (mcx_store_covariance(st, mean.data(), cov.data(), 0) != MCX_OK) {
+      std::cerr << "--derived-covariance: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_covariance(cov_path, mean, cov, K, 'd');
+  }
+  mcx_store_destroy(st);
+  return rc;
+}
+
+// --derive-linear: K rows of np + 1 numbers (a row of A, then b) -> par = A[K][np], then b[K]
+static int read_linear(const char *path, int np, std::vector<float> &par, int *nout)
+{
+  FILE *f = fopen(path, "r");
+  if (!f) {
+    std::cerr << "--derive-linear: cannot read " << path << "\n";
+    return 1;
+  }
+  std::vector<double> v;
+  double t;
+  while (fscanf(f, "%lf", &t) == 1) v.push_back(t);
+  const bool clean = feof(f) != 0;
+  fclose(f);
+  const size_t w = (size_t)np + 1, K = v.size() / w;
+  if (!clean || K < 1 || K > 256 || K * w != v.size()) {
+    std::cerr << "--derive-linear: " << path << " holds " << v.size() << " numbers" << (clean ? "" : " before something that is not one")
+              << ", 1 to 256 rows of np + 1 = " << w << " are needed\n";
+    return 1;
+  }
+  par.resize(v.size());
+  for (size_t j = 0; j < K; ++j) {
+    for (int k = 0; k < np; ++k) par[j * np + k] = (float)v[j * w + k];
+    par[K * np + j] = (float)v[j * w + np];
+  }
+  *nout = (int)K;
+  return 0;
+}
+
+// --draws: ndraw of MCout's rows with replacement, the rows mcx_samples_draw picks, as the text of the sample output
+static int write_draws(const char *path, MCout &rows, int np, long long ndraw, unsigned seed)
+{
+  const size_t ncol = (size_t)np + 1;
+  if (rows.size() < 1 || ndraw < 0 || ndraw > 2000000000LL) {
+    std::cerr << "--draws: " << rows.size() << " rows stored, --ndraw " << ndraw << ": at least one row and 0 to 2e9 draws\n";
+    return 1;
+  }
+  std::vector<int64_t> index((size_t)ndraw);
+  if (mcx_debug_draw_indices(seed, (uint64_t)rows.size(), 0, (int)ndraw, index.data()) != MCX_OK) {
+    std::cerr << "--draws: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  std::vector<float> drawn((size_t)ndraw * ncol);
+  for (size_t i = 0; i < index.size(); ++i) std::memcpy(&drawn[i * ncol], rows.getpset((int)index[i]), ncol * sizeof(float));
+  size_t nb = 0;
+  std::vector<char> text;
+  if (ndraw > 0) {
+    if (mcx_format_rows(drawn.data(), (size_t)ndraw, (int)ncol, 0, 0, &nb) != MCX_OK) {
+      std::cerr << "--draws: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    text.resize(nb);
+    if (mcx_format_rows(drawn.data(), (size_t)ndraw, (int)ncol, text.data(), nb, &nb) != MCX_OK) {
+      std::cerr << "--draws: " << mcx_last_error() << "\n";
+      return 1;
+    }
+  }
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  if (nb && fwrite(text.data(), 1, nb, f) != nb) {
+    fclose(f);
+    return 1;
+  }
+  return fclose(f) == 0 ? 0 : 1;
 }
 
 // --incov: np * np numbers -> incov, checked by the factorisation MCPar::covar_setup will use
@@ -174,7 +310,11 @@ int main(int argc, char *argv[])
   float pl = 1.0f;
   bool quiet = false, iter = false, binary = false, stream_text = false;
   std::string out_file, func_source, summary_file, rank_summary_file, covariance_file, proposal_file, incov_file;
-  std::vector<float> user_par;
+  std::string derive_source_file, derive_linear_file, derived_summary_file, derived_rank_summary_file, derived_covariance_file, draws_file;
+  std::vector<float> user_par, derive_par;
+  int derive_nout = 0;
+  long long ndraw = 0;
+  unsigned draw_seed = 8675309u;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : "0"; };
@@ -201,6 +341,19 @@ int main(int argc, char *argv[])
     else if (a == "--covariance") covariance_file = val();
     else if (a == "--proposal") proposal_file = val();
     else if (a == "--incov") incov_file = val();
+    else if (a == "--derive-source") derive_source_file = val();
+    else if (a == "--derive-nout") derive_nout = atoi(val());
+    else if (a == "--derive-par") {
+      std::stringstream ss(val());
+      for (std::string tok; std::getline(ss, tok, ',');) derive_par.push_back((float)atof(tok.c_str()));
+    }
+    else if (a == "--derive-linear") derive_linear_file = val();
+    else if (a == "--derived-summary") derived_summary_file = val();
+    else if (a == "--derived-rank-summary") derived_rank_summary_file = val();
+    else if (a == "--derived-covariance") derived_covariance_file = val();
+    else if (a == "--draws") draws_file = val();
+    else if (a == "--ndraw") ndraw = atoll(val());
+    else if (a == "--draw-seed") draw_seed = (unsigned)strtoul(val(), 0, 10);
     else { std::cerr << "unknown option " << a << "\n"; return 2; }
   }
   MPI_Init(&argc, &argv);
@@ -225,6 +378,20 @@ int main(int argc, char *argv[])
     if (rank == 0)
       std::cerr << "--covariance / --proposal need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  const bool want_derived = !derived_summary_file.empty() || !derived_rank_summary_file.empty() || !derived_covariance_file.empty();
+  const bool have_derive = !derive_source_file.empty() || !derive_linear_file.empty();
+  if ((want_derived || !draws_file.empty()) && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--derived-* and --draws need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_derived != have_derive || (!derive_source_file.empty() && !derive_linear_file.empty())) {
+    if (rank == 0) std::cerr << "--derived-* files need one of --derive-source and --derive-linear, and the other way round\n";
     MPI_Finalize();
     return 2;
   }
@@ -318,6 +485,40 @@ int main(int argc, char *argv[])
   if ((!covariance_file.empty() || !proposal_file.empty()) &&
       write_covariance(covariance_file.empty() ? 0 : covariance_file.c_str(), proposal_file.empty() ? 0 : proposal_file.c_str(),
                        rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_derived) {
+    mcx_derive spec = {MCX_DERIVE_LINEAR, derive_nout, 0, 0, 0};
+    std::string text;
+    if (!derive_linear_file.empty()) {
+      if (read_linear(derive_linear_file.c_str(), np, derive_par, &spec.nout) != 0) {
+        MPI_Finalize();
+        return 2;
+      }
+    } else {
+      FILE *f = fopen(derive_source_file.c_str(), "rb");
+      if (!f) {
+        std::cerr << "cannot read " << derive_source_file << "\n";
+        MPI_Finalize();
+        return 2;
+      }
+      char buf[4096];
+      for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, k);
+      fclose(f);
+      spec.kind = MCX_DERIVE_SOURCE;
+      spec.source = text.c_str();
+    }
+    spec.npar = (int)derive_par.size();
+    spec.par = derive_par.empty() ? 0 : derive_par.data();
+    if (write_derived(spec, derived_summary_file.empty() ? 0 : derived_summary_file.c_str(),
+                      derived_rank_summary_file.empty() ? 0 : derived_rank_summary_file.c_str(),
+                      derived_covariance_file.empty() ? 0 : derived_covariance_file.c_str(), rslts, nsamp, nc, np) != 0) {
+      MPI_Finalize();
+      return 2;
+    }
+  }
+  if (!draws_file.empty() && write_draws(draws_file.c_str(), rslts, np, ndraw, draw_seed) != 0) {
     MPI_Finalize();
     return 2;
   }

@@ -4,7 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, Counters, PlanItem, Profile, VLFunc, check, load)
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, Counters, Derive, PlanItem, Profile, VLFunc, check,
+                   load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -41,6 +42,7 @@ RANK_SUMMARY_DTYPE = np.dtype([("rhat", np.float64), ("rhat_bulk", np.float64), 
                                ("ess_bulk_lag", np.int32), ("flags", np.int32)], align=True)
 assert RANK_SUMMARY_DTYPE.itemsize == 88
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
+DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
 
 
 def _fp(a):
@@ -280,6 +282,117 @@ def rows_covariance(rows, nsteps, nc):
     check(load().mcx_rows_covariance(_fp(rows), nsteps, nc, ncol - 1, _dp(mean), _dp(cov),
                                      flags.ctypes.data_as(C.POINTER(C.c_int))))
     return _covariance_dict(mean, cov, flags)
+
+
+# ---- derived columns and bootstrap draws (include/mcx.h) ----
+class DeriveSpec:
+    """an mcx_derive and the arrays it points to"""
+
+    def __init__(self, kind, nout, par=None, source=None):
+        self.par = None if par is None else np.ascontiguousarray(par, np.float32).reshape(-1)
+        self.text = None if source is None else (source.encode() if isinstance(source, str) else bytes(source))
+        self.c = Derive(kind, nout, 0 if self.par is None else self.par.size, None if self.par is None else _fp(self.par),
+                        self.text)
+
+
+def derive_linear(A, b):
+    """MCX_DERIVE_LINEAR: out = b + A x, A [nout, np], b [nout]; acc = b[j], then acc = acc + A[j][k] * x[k] for k in
+    order, every product and sum rounded to float32"""
+    A = np.ascontiguousarray(A, np.float32)
+    b = np.ascontiguousarray(b, np.float32).reshape(-1)
+    if A.ndim != 2 or A.shape[0] != b.size:
+        raise ValueError("A must be [nout, np] and b [nout]")
+    return DeriveSpec(DERIVE_LINEAR, A.shape[0], np.concatenate([A.reshape(-1), b]))
+
+
+def derive_source(text, nout, par=None):
+    """MCX_DERIVE_SOURCE: HIP text that defines mcx_user_derive(x, d, ly, par, out, nout) (mcpar_amd/examples/derive_*.hip)"""
+    return DeriveSpec(DERIVE_SOURCE, nout, par, text)
+
+
+class DerivedStore:
+    """an mcx_store: nout derived columns, then log L, of every row of a step range.  It owns its device memory."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    def close(self):
+        if self.h:
+            load().mcx_store_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def shape(self):
+        """(nsteps, nc, ncol), ncol = nout + 1"""
+        t, nc, ncol = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(load().mcx_store_shape(self.h, C.byref(t), C.byref(nc), C.byref(ncol)))
+        return t.value, nc.value, ncol.value
+
+    def rows(self, first_step=0, nsteps=None):
+        """MCout rows [nsteps * nc, ncol] of steps [first_step, first_step + nsteps) -- nsteps None: to the end"""
+        t, nc, ncol = self.shape
+        if nsteps is None:
+            nsteps = t - first_step
+        out = np.empty((max(nsteps, 0) * nc, ncol), np.float32)
+        check(load().mcx_store_copy(self.h, first_step, nsteps, _fp(out)))
+        return out
+
+    def summary(self, probs=(0.01, 0.5, 0.99)):
+        """Engine.summary's dict for the derived columns, then log L"""
+        ncol = self.shape[2]
+        p, pp = _probs(probs)
+        cols = np.zeros(ncol, SUMMARY_DTYPE)
+        q = np.zeros((ncol, len(p)), np.float64)
+        check(load().mcx_store_summary(self.h, pp, len(p), cols.ctypes.data_as(C.c_void_p), _dp(q)))
+        return _summary_dict(cols, q)
+
+    def rank_summary(self):
+        """Engine.rank_summary's dict"""
+        cols = np.zeros(self.shape[2], RANK_SUMMARY_DTYPE)
+        check(load().mcx_store_rank_summary(self.h, cols.ctypes.data_as(C.c_void_p)))
+        return _rank_summary_dict(cols)
+
+    def covariance(self):
+        """Engine.covariance's dict"""
+        ncol = self.shape[2]
+        mean, cov, flags = np.zeros(ncol), np.zeros((ncol, ncol)), np.zeros(ncol, np.int32)
+        check(load().mcx_store_covariance(self.h, _dp(mean), _dp(cov), flags.ctypes.data_as(C.POINTER(C.c_int))))
+        return _covariance_dict(mean, cov, flags)
+
+    def draw(self, ndraw, seed):
+        """ndraw rows with replacement: (rows [ndraw, ncol], index [ndraw] int64), the index Engine.draw gives for the
+        same seed and number of rows"""
+        rows, index = np.empty((max(ndraw, 0), self.shape[2]), np.float32), np.empty(max(ndraw, 0), np.int64)
+        check(load().mcx_store_draw(self.h, seed, ndraw, _fp(rows), index.ctypes.data_as(C.POINTER(C.c_int64))))
+        return rows, index
+
+
+def derive_rows(rows, nsteps, nc, spec):
+    """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    h = C.c_void_p()
+    check(load().mcx_rows_derive(_fp(rows), nsteps, nc, rows.shape[1] - 1, None if spec is None else C.byref(spec.c), C.byref(h)))
+    return DerivedStore(h)
+
+
+def debug_draw_indices(seed, N, first, n):
+    """mcx_debug_draw_indices (host only): the rows of draws first .. first + n - 1 among N rows, int64"""
+    out = np.empty(max(n, 0), np.int64)
+    check(load().mcx_debug_draw_indices(seed, N, first, n, out.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out
+
+
+def debug_derive_compile(text, np_, nout):
+    """mcx_debug_derive_compile (needs no GPU): bytes of the code object of a derive text for rows of np_ parameters"""
+    nb = C.c_size_t(0)
+    check(load().mcx_debug_derive_compile(text.encode() if isinstance(text, str) else text, np_, nout, C.byref(nb)))
+    return nb.value
 
 
 def proposal_from_cov(cov, np_, scale=None):
@@ -699,6 +812,27 @@ class Engine:
         ms = np.zeros(3)
         self._on_store(load().mcx_debug_covariance_times, first_step, nsteps, _dp(ms))
         return ms
+
+    def derive(self, spec, first_step=0, nsteps=None):
+        """mcx_samples_derive: the DerivedStore of spec (derive_linear / derive_source) applied to every row of kept steps
+        [first_step, first_step + nsteps)"""
+        h = C.c_void_p()
+        self._on_store(load().mcx_samples_derive, first_step, nsteps, None if spec is None else C.byref(spec.c), C.byref(h))
+        return DerivedStore(h)
+
+    def derive_times(self, spec, first_step=0, nsteps=None):
+        """mcx_debug_derive_times: ms of one derive sweep of spec over the range (the second of two into one store)"""
+        ms = np.zeros(1)
+        self._on_store(load().mcx_debug_derive_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
+        return float(ms[0])
+
+    def draw(self, ndraw, seed, first_step=0, nsteps=None):
+        """mcx_samples_draw: ndraw rows of kept steps [first_step, first_step + nsteps) with replacement -- (rows [ndraw,
+        np + 1], index [ndraw] int64 into the rows of the range)"""
+        rows, index = np.empty((max(ndraw, 0), self.np + 1), np.float32), np.empty(max(ndraw, 0), np.int64)
+        self._on_store(load().mcx_samples_draw, first_step, nsteps, seed, ndraw, _fp(rows),
+                       index.ctypes.data_as(C.POINTER(C.c_int64)))
+        return rows, index
 
     def proposal_cov(self, scale=None, first_step=0, nsteps=None):
         """covariance() then proposal_from_cov(): the incov of the next run from this run's store"""
