@@ -549,6 +549,11 @@ int mcx_device_pci_bus_id(char *buf, size_t len);
  * HIP events; *gbps = (bytes read + bytes written) / time in GB/s.  What bench.py reports the HBM figures against
  * next to the nominal 8 TB/s. */
 int mcx_debug_copy_bandwidth(size_t bytes, int reps, double *gbps);
+/* what the library holds at this moment, process-wide (no device; fails only on NULL): out[0] device allocations, out[1]
+ * pinned host allocations, out[2] streams, out[3] events -- every engine, derived store and call in flight together.  All
+ * four are zero once every engine and store is destroyed and no call is running.  An engine's main stream is not counted
+ * (it may be the caller's, MCX_OPT_STREAM), nor are the modules of run-time compiled sources, which stay for the process. */
+int mcx_debug_live_resources(uint64_t out[4]);
 /* host logic of the one-launch small-n kernel, for tests (no device): recorders yes/no and steps per phase for `own` owner
  * wavefronts per workgroup of lpc2 lanes per chain x bpl blocks per lane, and who generates what: tab[3][16][24] item
  * codes (0xffffffff ends a wavefront's list; kind << 14 | step pair << 4 | (owner, block)) */

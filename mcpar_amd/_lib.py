@@ -156,6 +156,7 @@ def load():
         "mcx_debug_small_stretch": [C.POINTER(PlanItem), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int)],
         "mcx_debug_copy_bandwidth": [C.c_size_t, C.c_int, C.POINTER(C.c_double)],
+        "mcx_debug_live_resources": [C.POINTER(C.c_uint64)],
         "mcx_debug_numerics": [C.c_int, C.c_int, u32p, u32p],
         "mcx_debug_murray_screen": [C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.POINTER(C.c_uint64)],
         "mcx_debug_murray_decode": [C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -139,17 +139,13 @@ struct mcx_store {
   DevBuf<double> d;     // the analyses' scratch, as on_rows has it
   DevBuf<unsigned long long> h;
   DevBuf<uint32_t> u;
-  hipStream_t st = nullptr;
+  DevStream st;
   StoreSpan span() const { return StoreSpan{x.p, ly.p, nc, nout, (int64_t)T}; }
   Bufs bufs() { return Bufs{&d, &h, &u}; }
   size_t rows() const { return (size_t)T * nc; }
   ~mcx_store()
   {
-    if (st) {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-    x.release(); ly.release(); d.release(); h.release(); u.release();
+    if (st) (void)hipStreamSynchronize(st);  // (before the members go)
   }
 };
 
@@ -169,7 +165,7 @@ int derive_span(hipStream_t st, const StoreSpan &s, const mcx_derive *f, mcx_sto
   if (nwg > 0x7fffffffull) return fail(MCX_ERR_UNSUPPORTED, "derive: %llu rows in tiles of %d are more workgroups than a grid holds", (unsigned long long)N, a.R);
   hipFunction_t ufn = nullptr;
   if (f->kind == MCX_DERIVE_SOURCE) MCXCHK(derive_user_kernel(f->source, s.np, f->nout, &ufn));
-  HIPCHK(hipStreamCreateWithFlags(&o->st, hipStreamNonBlocking));
+  MCXCHK(o->st.ensure(hipStreamNonBlocking));
   MCXCHK(o->x.alloc((size_t)N * f->nout));
   MCXCHK(o->ly.alloc((size_t)N));
   DevBuf<float> par;
@@ -198,10 +194,9 @@ int derive_span(hipStream_t st, const StoreSpan &s, const mcx_derive *f, mcx_sto
     return MCX_OK;
   };
   const int rc = run();
-  if (rc != MCX_OK) (void)hipStreamSynchronize(st);
-  par.release();
+  if (rc != MCX_OK) (void)hipStreamSynchronize(st);  // (before par and the new store go)
   MCXCHK(rc);
-  *out = o.release();
+  *out = o.release();  // (the unique_ptr's: the store is the caller's now)
   return MCX_OK;
 }
 
@@ -232,8 +227,7 @@ int gather_to_host(hipStream_t st, const StoreSpan &s, uint32_t seed, uint64_t i
     return MCX_OK;
   };
   const int rc = run();
-  if (rc != MCX_OK) (void)hipStreamSynchronize(st);
-  dr.release(); di.release();
+  if (rc != MCX_OK) (void)hipStreamSynchronize(st);  // (before the chunk buffers go)
   return rc;
 }
 

@@ -211,8 +211,6 @@ void prof_collect(mcx_engine *e)
       e->prof.launches[p.kind] += 1;
       e->prof.chain_steps[p.kind] += p.chain_steps;
     }
-    (void)hipEventDestroy(p.a);
-    (void)hipEventDestroy(p.b);
   }
   e->evs.clear();
 }
@@ -280,6 +278,8 @@ extern "C" int mcx_create(mcx_engine **out, int np, int nc, int nshards, int sha
   return MCX_OK;
 }
 
+// Every buffer, stream and event of the engine is a member that releases itself: `delete e` gives them back.  What is
+// left here is order alone: nothing may still be running on, or waiting for, what is about to go.
 extern "C" int mcx_destroy(mcx_engine *e)
 {
   if (!e) return MCX_OK;
@@ -288,43 +288,10 @@ extern "C" int mcx_destroy(mcx_engine *e)
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   e->pend.active = false;  // (a run nobody waited for: over now; its results go with the engine)
   if (e->meet_held) { (void)flock(e->meet_fd, LOCK_UN); e->meet_held = false; }
-  if (e->astream) { (void)hipStreamSynchronize(e->astream); (void)hipStreamDestroy(e->astream); e->astream = nullptr; }
-  for (hipEvent_t &ev : e->run_ev) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
-  for (hipEvent_t &ev : e->copy_ev) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
+  if (e->astream) (void)hipStreamSynchronize(e->astream);
   prof_collect(e);
-  (void)mcx_exchange_rccl_destroy(e);
-  e->pvals.release(); e->ptrial.release(); e->mu.release(); e->sig.release(); e->psum2.release();
-  e->mutrial.release(); e->sigtrial.release(); e->musigall.release(); e->winvall.release();
-  e->lylast.release(); e->lytrial.release(); e->cfac.release(); e->cmax.release(); e->cov.release(); e->cov0.release();
-  e->trace.release(); e->acc_cnt.release(); e->acc_slots.release(); e->ctr.release(); e->active0.release();
-  e->active1.release(); e->nact.release(); e->ntrace.release(); e->samp_x.release();
-  e->cull_keys.release(); e->cull_hist.release(); e->cull_sorted.release(); e->cull_stats.release(); e->cull_box.release();
-  e->cull_lim.release(); e->cull_excl.release(); e->scr_a.release(); e->scr_b.release(); e->scr_centre.release(); e->cand.release(); e->proj_acc.release(); e->proj_p.release(); e->proj_lohi.release(); e->tun_cells.release(); e->text_wg.release(); e->text_dev.release();
-  e->summ_d.release(); e->summ_h.release(); e->summ_u.release();
-  e->samp_ly.release(); e->mask.release(); e->lik.params.release(); e->winv_tab.release(); e->psum.release(); e->pmax.release(); e->racpt.release(); e->pinit_dev.release();
-  e->h_ptrial.release(); e->h_lytrial.release(); e->h_ctr.release(); e->h_nact.release(); e->zpre.release(); e->upre.release(); e->trash.release(); e->deal_tab.release(); e->trace_clk.release();
-  for (int b = 0; b < 2; ++b) {
-    e->sink_stage[b].release();
-    e->sink_pin[b].release();
-    e->sink_text_wg[b].release();
-    e->sink_text_total[b].release();
-    if (e->ev_steps[b]) (void)hipEventDestroy(e->ev_steps[b]);
-    if (e->ev_copy[b]) (void)hipEventDestroy(e->ev_copy[b]);
-    if (e->ev_write[b]) (void)hipEventDestroy(e->ev_write[b]);
-    e->sink_text_dev[b].release();
-  }
-  e->best_row.release(); e->best_key.release(); e->cov0.release();
-  for (auto &pr : e->xw_pool) {
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
+  (void)mcx_exchange_rccl_destroy(e);  // (finish_tail needs a live stream)
   if (e->meet_fd >= 0) (void)close(e->meet_fd);
-  if (e->cstream) (void)hipStreamDestroy(e->cstream);
-  if (e->mstream) (void)hipStreamDestroy(e->mstream);
-  for (hipEvent_t ev : e->mev) (void)hipEventDestroy(ev);
-  if (e->tstream) (void)hipStreamDestroy(e->tstream);
-  if (e->ev_text) (void)hipEventDestroy(e->ev_text);
-  e->sink_text_pin.release();
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
   return MCX_OK;
@@ -575,47 +542,28 @@ extern "C" int mcx_vlfunc_eval(const mcx_vlfunc *f, int npset, const float *x, f
   }
   MCXCHK(need_device());
   LikDev L;
-  hipStream_t st = nullptr;
-  int rc = lik_setup(L, f, f->d, st);
-  if (rc == MCX_OK && L.kind == MCX_VL_DEVICE) {
-    DevBuf<float> ux, uy;
-    rc = ux.alloc((size_t)std::max(npset, 1) * f->d);
-    if (rc == MCX_OK) rc = uy.alloc((size_t)std::max(npset, 1));
-    if (rc == MCX_OK && npset > 0) {
-      auto run = [&]() -> int {
-        HIPCHK(hipMemcpy(ux.p, x, (size_t)npset * f->d * sizeof(float), hipMemcpyHostToDevice));
-        const float *xa = ux.p;
-        float *ya = uy.p;
-        void *args[] = {&npset, &xa, &ya};
-        HIPCHK(hipModuleLaunchKernel((hipFunction_t)L.ctx, nblocks((size_t)npset), 1, 1, BLOCK, 1, 1, 0, st, args, nullptr));
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(y, uy.p, (size_t)npset * sizeof(float), hipMemcpyDeviceToHost));
-        return MCX_OK;
-      };
-      rc = run();
-    }
-    ux.release(); uy.release();
-    return rc;
-  }
-  if (rc != MCX_OK || npset == 0) {
-    (void)hipDeviceSynchronize();  // the parameter upload reads L.host
-    L.params.release();
-    return rc;
-  }
   DevBuf<float> dx, dy;
-  rc = dx.alloc((size_t)npset * f->d);
-  if (rc == MCX_OK) rc = dy.alloc((size_t)npset);
-  if (rc == MCX_OK) {
-    auto run = [&]() -> int {
-      HIPCHK(hipMemcpy(dx.p, x, (size_t)npset * f->d * sizeof(float), hipMemcpyHostToDevice));
+  hipStream_t st = nullptr;
+  auto run = [&]() -> int {
+    MCXCHK(lik_setup(L, f, f->d, st));
+    if (npset == 0) return MCX_OK;
+    MCXCHK(dx.alloc((size_t)npset * f->d));
+    MCXCHK(dy.alloc((size_t)npset));
+    HIPCHK(hipMemcpy(dx.p, x, (size_t)npset * f->d * sizeof(float), hipMemcpyHostToDevice));
+    if (L.kind == MCX_VL_DEVICE) {
+      const float *xa = dx.p;
+      float *ya = dy.p;
+      void *args[] = {&npset, &xa, &ya};
+      HIPCHK(hipModuleLaunchKernel((hipFunction_t)L.ctx, nblocks((size_t)npset), 1, 1, BLOCK, 1, 1, 0, st, args, nullptr));
+    } else {
       MCXCHK(eval_device(L, dx.p, dy.p, npset, f->d, st));
-      HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemcpy(y, dy.p, (size_t)npset * sizeof(float), hipMemcpyDeviceToHost));
-      return MCX_OK;
-    };
-    rc = run();
-  }
-  dx.release(); dy.release(); L.params.release();
+    }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, dy.p, (size_t)npset * sizeof(float), hipMemcpyDeviceToHost));
+    return MCX_OK;
+  };
+  const int rc = run();
+  (void)hipDeviceSynchronize();  // the parameter upload reads L.host, which goes with L
   return rc;
 }
 
@@ -626,21 +574,16 @@ extern "C" int mcx_gen_local(mcx_engine *e, uint32_t t, const float *pvals, floa
   hipStream_t st = e->stream;
   DevBuf<float> x;
   MCXCHK(x.alloc((size_t)e->ntot));
-  auto run = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(x.p, pvals, (size_t)e->ntot * sizeof(float), hipMemcpyHostToDevice, st));
-    StepArgs a;
-    fill_step(e, a, t, 0, false, 0, 0, 0);
-    a.x = x.p;
-    a.mask = nullptr;
-    MCXCHK(launch_propose(e, a));
-    HIPCHK(hipMemcpyAsync(ptrial, e->ptrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(cfac, e->cfac.p, (size_t)e->nchain * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return MCX_OK;
-  };
-  const int rc = run();
-  x.release();
-  return rc;
+  HIPCHK(hipMemcpyAsync(x.p, pvals, (size_t)e->ntot * sizeof(float), hipMemcpyHostToDevice, st));
+  StepArgs a;
+  fill_step(e, a, t, 0, false, 0, 0, 0);
+  a.x = x.p;
+  a.mask = nullptr;
+  MCXCHK(launch_propose(e, a));
+  HIPCHK(hipMemcpyAsync(ptrial, e->ptrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(cfac, e->cfac.p, (size_t)e->nchain * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return MCX_OK;
 }
 
 extern "C" int mcx_gen_remote(mcx_engine *e, uint32_t t, const float *pvals, const float *musigall,
@@ -651,23 +594,17 @@ extern "C" int mcx_gen_remote(mcx_engine *e, uint32_t t, const float *pvals, con
   hipStream_t st = e->stream;
   DevBuf<float> x, ms;
   MCXCHK(x.alloc((size_t)e->ntot));
-  int rc = ms.alloc(2 * (size_t)e->tchains * e->nparam);
-  if (rc != MCX_OK) { x.release(); return rc; }
-  auto run = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(x.p, pvals, (size_t)e->ntot * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ms.p, musigall, 2 * (size_t)e->tchains * e->nparam * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(e->cfac.p, 0, (size_t)e->nchain * sizeof(float), st));
-    MCXCHK(remote_device(e, t, x.p, ms.p, e->ptrial.p, e->cfac.p, e->mutrial.p, e->sigtrial.p, npass));
-    HIPCHK(hipMemcpyAsync(ptrial, e->ptrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(cfac, e->cfac.p, (size_t)e->nchain * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (mutrial) HIPCHK(hipMemcpyAsync(mutrial, e->mutrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (sigtrial) HIPCHK(hipMemcpyAsync(sigtrial, e->sigtrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return MCX_OK;
-  };
-  rc = run();
-  x.release(); ms.release();
-  return rc;
+  MCXCHK(ms.alloc(2 * (size_t)e->tchains * e->nparam));
+  HIPCHK(hipMemcpyAsync(x.p, pvals, (size_t)e->ntot * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ms.p, musigall, 2 * (size_t)e->tchains * e->nparam * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(e->cfac.p, 0, (size_t)e->nchain * sizeof(float), st));
+  MCXCHK(remote_device(e, t, x.p, ms.p, e->ptrial.p, e->cfac.p, e->mutrial.p, e->sigtrial.p, npass));
+  HIPCHK(hipMemcpyAsync(ptrial, e->ptrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(cfac, e->cfac.p, (size_t)e->nchain * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (mutrial) HIPCHK(hipMemcpyAsync(mutrial, e->mutrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (sigtrial) HIPCHK(hipMemcpyAsync(sigtrial, e->sigtrial.p, (size_t)e->ntot * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return MCX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -751,13 +688,13 @@ extern "C" int mcx_samples_copy(mcx_engine *e, int first_step, int nsteps, float
   if (nr == 0) return MCX_OK;
   const size_t chunk_rows = std::max<size_t>(1, std::min<size_t>(nr, ((size_t)32 << 20) / (ncol * sizeof(float))));
   DevBuf<float> stage[2];
-  float *pin[2] = {nullptr, nullptr};
-  hipEvent_t done[2] = {nullptr, nullptr};
+  PinBuf<float> pin[2];
+  DevEvent done[2];
   auto run = [&]() -> int {
     for (int b = 0; b < 2; ++b) {
       MCXCHK(stage[b].alloc(chunk_rows * ncol));
-      HIPCHK(hipHostMalloc((void **)&pin[b], chunk_rows * ncol * sizeof(float), hipHostMallocDefault));
-      HIPCHK(hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+      MCXCHK(pin[b].alloc(chunk_rows * ncol));
+      MCXCHK(done[b].ensure(hipEventDisableTiming));
     }
     const float *sx = e->samp_x.p + (size_t)first_step * n * d, *sl = e->samp_ly.p + (size_t)first_step * n;
     size_t issued = 0, copied = 0;
@@ -769,26 +706,21 @@ extern "C" int mcx_samples_copy(mcx_engine *e, int first_step, int nsteps, float
         hipLaunchKernelGGL(k_rows_interleave, dim3(nblocks(r * ncol)), dim3(BLOCK), 0, e->stream, sx + issued * d,
                            sl + issued, stage[ib].p, r, (int)d);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(pin[ib], stage[ib].p, r * ncol * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(pin[ib].p, stage[ib].p, r * ncol * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipEventRecord(done[ib], e->stream));
         rows_in[ib] = r;
         issued += r;
         ib ^= 1;
       }
       HIPCHK(hipEventSynchronize(done[cb]));
-      std::memcpy(rows + copied * ncol, pin[cb], rows_in[cb] * ncol * sizeof(float));
+      std::memcpy(rows + copied * ncol, pin[cb].p, rows_in[cb] * ncol * sizeof(float));
       copied += rows_in[cb];
       cb ^= 1;
     }
     return MCX_OK;
   };
   const int rc = run();
-  (void)hipStreamSynchronize(e->stream);
-  for (int b = 0; b < 2; ++b) {
-    stage[b].release();
-    if (pin[b]) (void)hipHostFree(pin[b]);
-    if (done[b]) (void)hipEventDestroy(done[b]);
-  }
+  (void)hipStreamSynchronize(e->stream);  // (the pinned buffers are the target of copies that may still be in flight)
   return rc;
 }
 
@@ -853,20 +785,13 @@ extern "C" int mcx_debug_numerics(int what, int n, const uint32_t *in, uint32_t 
   if (n == 0) return MCX_OK;
   DevBuf<uint32_t> di, dout;
   MCXCHK(di.alloc((size_t)n));
-  int rc = dout.alloc((size_t)n);
-  if (rc == MCX_OK) {
-    auto run = [&]() -> int {
-      HIPCHK(hipMemcpy(di.p, in, (size_t)n * 4, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(k_debug_numerics, dim3(nblocks((size_t)n)), dim3(BLOCK), 0, 0, what, n, di.p, dout.p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemcpy(out_bits, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-      return MCX_OK;
-    };
-    rc = run();
-  }
-  di.release(); dout.release();
-  return rc;
+  MCXCHK(dout.alloc((size_t)n));
+  HIPCHK(hipMemcpy(di.p, in, (size_t)n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_numerics, dim3(nblocks((size_t)n)), dim3(BLOCK), 0, 0, what, n, di.p, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out_bits, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return MCX_OK;
 }
 
 extern "C" int mcx_debug_copy_bandwidth(size_t bytes, int reps, double *gbps)
@@ -875,11 +800,11 @@ extern "C" int mcx_debug_copy_bandwidth(size_t bytes, int reps, double *gbps)
   DevBuf<unsigned char> a, b;
   MCXCHK(a.alloc(bytes));
   MCXCHK(b.alloc(bytes));
-  hipEvent_t t0 = nullptr, t1 = nullptr;
+  DevEvent t0, t1;
   int rc = MCX_OK;
   float ms = 0.0f;
   do {
-    if (hipMemset(a.p, 1, bytes) != hipSuccess || hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess ||
+    if (hipMemset(a.p, 1, bytes) != hipSuccess || t0.ensure(hipEventDefault) != MCX_OK || t1.ensure(hipEventDefault) != MCX_OK ||
         hipMemcpyAsync(b.p, a.p, bytes, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||  // warm
         hipEventRecord(t0, nullptr) != hipSuccess) { rc = MCX_ERR_HIP; break; }
     for (int r = 0; r < reps && rc == MCX_OK; ++r)
@@ -888,10 +813,6 @@ extern "C" int mcx_debug_copy_bandwidth(size_t bytes, int reps, double *gbps)
     if (hipEventRecord(t1, nullptr) != hipSuccess || hipEventSynchronize(t1) != hipSuccess ||
         hipEventElapsedTime(&ms, t0, t1) != hipSuccess || !(ms > 0.0f)) rc = MCX_ERR_HIP;
   } while (0);
-  if (t0) (void)hipEventDestroy(t0);
-  if (t1) (void)hipEventDestroy(t1);
-  a.release();
-  b.release();
   if (rc != MCX_OK) return fail(rc, "copy bandwidth: %s", hipGetErrorString(hipGetLastError()));
   *gbps = 2.0 * (double)bytes * reps / (ms * 1e-3) / 1e9;
   return MCX_OK;
@@ -904,25 +825,18 @@ extern "C" int mcx_debug_sqrt_sweep(uint32_t lo_bits, uint32_t hi_bits, uint64_t
   DevBuf<unsigned long long> dn;
   DevBuf<uint32_t> df;
   MCXCHK(dn.alloc(1));
-  int rc = df.alloc(1);
-  if (rc == MCX_OK) {
-    auto run = [&]() -> int {
-      const uint32_t init = 0xffffffffu;
-      HIPCHK(hipMemset(dn.p, 0, sizeof(unsigned long long)));
-      HIPCHK(hipMemcpy(df.p, &init, 4, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(k_debug_sqrt_sweep, dim3(4096), dim3(BLOCK), 0, 0, lo_bits, hi_bits, dn.p, df.p);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipDeviceSynchronize());
-      unsigned long long n = 0;
-      HIPCHK(hipMemcpy(&n, dn.p, sizeof n, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(first_bad, df.p, 4, hipMemcpyDeviceToHost));
-      *nbad = n;
-      return MCX_OK;
-    };
-    rc = run();
-  }
-  dn.release(); df.release();
-  return rc;
+  MCXCHK(df.alloc(1));
+  const uint32_t init = 0xffffffffu;
+  HIPCHK(hipMemset(dn.p, 0, sizeof(unsigned long long)));
+  HIPCHK(hipMemcpy(df.p, &init, 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_sqrt_sweep, dim3(4096), dim3(BLOCK), 0, 0, lo_bits, hi_bits, dn.p, df.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  unsigned long long n = 0;
+  HIPCHK(hipMemcpy(&n, dn.p, sizeof n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(first_bad, df.p, 4, hipMemcpyDeviceToHost));
+  *nbad = n;
+  return MCX_OK;
 }
 
 extern "C" int mcx_debug_normals(uint32_t seed, uint32_t stream, uint32_t t, uint32_t g0, uint32_t a,
@@ -933,15 +847,17 @@ extern "C" int mcx_debug_normals(uint32_t seed, uint32_t stream, uint32_t t, uin
   if (n == 0) return MCX_OK;
   DevBuf<float> d;
   MCXCHK(d.alloc((size_t)n * 4));
-  auto run = [&]() -> int {
-    hipLaunchKernelGGL(k_debug_normals, dim3(nblocks((size_t)n)), dim3(BLOCK), 0, 0, seed, stream, t, g0, a, q, n, d.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, d.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-    return MCX_OK;
-  };
-  const int rc = run();
-  d.release();
-  return rc;
+  hipLaunchKernelGGL(k_debug_normals, dim3(nblocks((size_t)n)), dim3(BLOCK), 0, 0, seed, stream, t, g0, a, q, n, d.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, d.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+  return MCX_OK;
 }
 
+// what the owners of mcx_engine_internal.hpp hold at this moment, process-wide; needs no device
+extern "C" int mcx_debug_live_resources(uint64_t out[4])
+{
+  if (!out) return fail(MCX_ERR_INVALID, "out is NULL");
+  for (int i = 0; i < 4; ++i) out[i] = g_live[i].load(std::memory_order_relaxed);
+  return MCX_OK;
+}

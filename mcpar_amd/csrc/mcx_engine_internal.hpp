@@ -1,5 +1,7 @@
 // mcx_engine_internal.hpp -- what the translation units of libmcx.so's host side share: the engine's state, the error
-// and check macros, the device buffers, and the handful of functions that cross the seams between
+// and check macros, the owners of device memory, pinned memory, streams and events (DevBuf, PinBuf, DevStream, DevEvent: what
+// is a member or a local is released with it; mcx_debug_live_resources counts them), and the handful of functions that cross
+// the seams between
 //   mcx_engine.hip    the C ABI's create / destroy / options / getters / standalone operators, likelihood and covariance set-up
 //   mcx_run.hip       mcx_run: the plan executor run_once, its launch helpers, the meeting lock, the ends of a run
 //   mcx_plan.hip      the schedule of one run and the small-n stretches of it (pure host logic, exported as mcx_plan)
@@ -31,6 +33,7 @@ typedef enum { ncclFloat = 7 } ncclDataType_t;
 #endif
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cerrno>
 #include <cmath>
@@ -94,10 +97,25 @@ static inline int dmax_for(int d)
 }
 static inline unsigned nblocks(size_t threads) { return (unsigned)((threads + BLOCK - 1) / BLOCK); }
 
+// ---------------------------------------------------------------------------------------------
+// owners: device memory, pinned memory, streams and events are released by being a member or a local
+// ---------------------------------------------------------------------------------------------
+// Not copyable; the stream and the event can be moved (they live in vectors).  None may live at namespace or static
+// scope: its destructor would call HIP after the runtime is gone.  g_live counts what the owners hold at this moment,
+// process-wide (mcx_debug_live_resources); it is touched in their create and free paths and nowhere else.
+enum { LIVE_DEVICE, LIVE_PINNED, LIVE_STREAMS, LIVE_EVENTS };
+inline std::atomic<uint64_t> g_live[4];
+static inline void live_add(int what) { g_live[what].fetch_add(1, std::memory_order_relaxed); }
+static inline void live_sub(int what) { g_live[what].fetch_sub(1, std::memory_order_relaxed); }
+
 template <typename T>
 struct DevBuf {
   T *p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
   int alloc(size_t count)
   {
     if (count <= n && p) return MCX_OK;
@@ -110,12 +128,16 @@ struct DevBuf {
       n = 0;
       return fail(MCX_ERR_ALLOC, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
     }
+    live_add(LIVE_DEVICE);
     n = count;
     return MCX_OK;
   }
-  void release()
+  void release()  // (the destructor's work; by name only where a buffer is freed in mid-life)
   {
-    if (p) (void)hipFree(p);
+    if (p) {
+      (void)hipFree(p);
+      live_sub(LIVE_DEVICE);
+    }
     p = nullptr;
     n = 0;
   }
@@ -126,6 +148,10 @@ template <typename T>
 struct PinBuf {
   T *p = nullptr;
   size_t n = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf &) = delete;
+  PinBuf &operator=(const PinBuf &) = delete;
+  ~PinBuf() { release(); }
   int alloc(size_t count)
   {
     if (count <= n && p) return MCX_OK;
@@ -136,15 +162,70 @@ struct PinBuf {
       p = nullptr;
       return fail(MCX_ERR_ALLOC, "hipHostMalloc(%zu bytes) failed", count * sizeof(T));
     }
+    live_add(LIVE_PINNED);
     n = count;
     return MCX_OK;
   }
   void release()
   {
-    if (p) (void)hipHostFree(p);
+    if (p) {
+      (void)hipHostFree(p);
+      live_sub(LIVE_PINNED);
+    }
     p = nullptr;
     n = 0;
   }
+};
+
+// a stream / an event created on first use: ensure(flags) creates it once and is MCX_OK ever after; the object converts
+// to the raw handle (null until then), so launch, record and wait sites take it as they would the handle
+struct DevStream {
+  hipStream_t h = nullptr;
+  DevStream() = default;
+  DevStream(DevStream &&o) noexcept : h(o.h) { o.h = nullptr; }
+  DevStream(const DevStream &) = delete;
+  DevStream &operator=(const DevStream &) = delete;
+  ~DevStream() { reset(); }
+  int ensure(unsigned flags)
+  {
+    if (h) return MCX_OK;
+    HIPCHK(hipStreamCreateWithFlags(&h, flags));
+    live_add(LIVE_STREAMS);
+    return MCX_OK;
+  }
+  void reset()
+  {
+    if (h) {
+      (void)hipStreamDestroy(h);
+      live_sub(LIVE_STREAMS);
+    }
+    h = nullptr;
+  }
+  operator hipStream_t() const { return h; }
+};
+struct DevEvent {  // (flags hipEventDefault: what hipEventCreate makes)
+  hipEvent_t h = nullptr;
+  DevEvent() = default;
+  DevEvent(DevEvent &&o) noexcept : h(o.h) { o.h = nullptr; }
+  DevEvent(const DevEvent &) = delete;
+  DevEvent &operator=(const DevEvent &) = delete;
+  ~DevEvent() { reset(); }
+  int ensure(unsigned flags)
+  {
+    if (h) return MCX_OK;
+    HIPCHK(hipEventCreateWithFlags(&h, flags));
+    live_add(LIVE_EVENTS);
+    return MCX_OK;
+  }
+  void reset()
+  {
+    if (h) {
+      (void)hipEventDestroy(h);
+      live_sub(LIVE_EVENTS);
+    }
+    h = nullptr;
+  }
+  operator hipEvent_t() const { return h; }
 };
 
 // device-side likelihood descriptor built from an mcx_vlfunc
@@ -215,7 +296,7 @@ constexpr int CTR_WORDS = 8 + PEVENTS * PLEAVES, CTR_RING = 16;
 constexpr int SINK_RING = 4;  // blocks of the device ring in sink mode
 
 struct EvPair {
-  hipEvent_t a, b;
+  DevEvent a, b;
   int kind;
   uint64_t chain_steps;
 };
@@ -276,7 +357,7 @@ struct mcx_engine {
   int opt_meet_timeout_ms = 50, opt_debug_meet = 0;
   int opt_meet_under_gather = -1;  // may a launch with tuner meetings start under this engine's in-flight gather: -1 auto (= no), 0 no, 1 yes
   // run bookkeeping
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;  // a raw handle: mcx_create makes one, MCX_OPT_STREAM adopts the caller's (own_stream says which)
   bool own_stream = false;
   int opt_stride = 1;
   int opt_split = -1;  // small-n mode: -1 auto, 0 off, 1 on (when the hot-path kernel applies)
@@ -307,17 +388,17 @@ struct mcx_engine {
     int slot = 0;                        // its counter slot / events
     unsigned long long serial = 0;       // != 0: its last launch reports to the slot itself (RunArgs::report) and stores this last
   } pend;
-  hipStream_t astream = nullptr;         // an asynchronous run's counters travel on it, beside the next run's kernels
+  DevStream astream;                     // an asynchronous run's counters travel on it, beside the next run's kernels
   // Counter slots in pinned memory, one per run in turn.  FOUR: run k is queued once run k-2's kernels are over (two in flight),
   // run k-2's counters may leave only when run k-1 ends (their copy kernel finds no room beside a grid that fills the device),
   // and run k-3's are what the books look at meanwhile.
   static constexpr int HSLOTS = 4;
-  hipEvent_t copy_ev[HSLOTS] = {nullptr, nullptr, nullptr, nullptr};
+  DevEvent copy_ev[HSLOTS];
   bool copy_pending[HSLOTS] = {false, false, false, false};
   unsigned superseded_mask = 0;  // slots of runs nobody looked at before the next was queued (and that had tuner meetings): for the books only
   DevBuf<float> pinit_async;
   int hctr_slot = 0;
-  hipEvent_t run_ev[HSLOTS] = {nullptr, nullptr, nullptr, nullptr};  // recorded behind each asynchronous run's last command, by counter slot
+  DevEvent run_ev[HSLOTS];  // recorded behind each asynchronous run's last command, by counter slot
   bool run_queued[HSLOTS] = {false, false, false, false};
   // MCX_OPT_SELF_REPORT: a run that ends with a launch of the one-launch kernel has that launch write the counters to the slot
   // and its serial number behind them (RunArgs::report): nothing is queued behind the kernel, the host spins on the word
@@ -326,12 +407,12 @@ struct mcx_engine {
   double report_wait_us = 0.0;  // how long the last self-reporting run kept the host waiting: a run that takes longer than the
                                 // spin allows is not spun for at all the next time (a core's 1.5 ms are somebody else's)
   unsigned long long slot_serial[HSLOTS] = {0, 0, 0, 0};   // the serial the slot's run will store (0: its counters come by copy)
-  hipStream_t mstream = nullptr;   // Murray passes by column chunks: the sweeps' stream (mcx_murray.hip: screen_sweep_chunked)
-  std::vector<hipEvent_t> mev;
+  DevStream mstream;  // Murray passes by column chunks: the sweeps' stream (mcx_murray.hip: screen_sweep_chunked)
+  std::vector<DevEvent> mev;
   int opt_murray_overlap = 0;
   int opt_murray_max_passes = MURRAY_MAX_PASSES_DEFAULT;
-  hipStream_t xstream = nullptr;
-  hipEvent_t xready = nullptr, xdone = nullptr;
+  DevStream xstream;
+  DevEvent xready, xdone;
   mcx_output_fn ofn = nullptr;
   void *octx = nullptr;
   // streaming sample sink (mcx_set_sink): ring of SINK_RING blocks in samp_x / samp_ly, staged out on cstream
@@ -352,10 +433,10 @@ struct mcx_engine {
   bool run_sink = false;           // the current / last run streamed its samples
   int last_sink_total = 0;         // kept steps handed to the copy stream so far
   int run_sblock = 0, run_kb = 0;  // its block length in steps / in kept steps
-  hipStream_t cstream = nullptr;
-  hipEvent_t ev_steps[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
-  hipStream_t tstream = nullptr;   // the text's copies to the host
-  hipEvent_t ev_write[2] = {nullptr, nullptr}, ev_text = nullptr;
+  DevStream cstream;
+  DevEvent ev_steps[2], ev_copy[2];
+  DevStream tstream;  // the text's copies to the host
+  DevEvent ev_write[2], ev_text;
   DevBuf<float> sink_stage[2];
   PinBuf<float> sink_pin[2];
   DevBuf<float> best_row;            // running maximum-likelihood sample: [0] = log-likelihood, [1..np] = parameters
@@ -370,7 +451,7 @@ struct mcx_engine {
   int runs_since_broken = 0;         // runs on the per-segment kernels since then (the one-launch kernel is tried again)
   // time the step stream waits for gathers begun earlier (mcx_counters.exchange_wait_ns): event pairs around each wait
   std::chrono::steady_clock::time_point ht_mark[3];  // MCX_VERBOSE=2: first launch queued / everything queued / stream idle
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> xw_pool;
+  std::vector<std::pair<DevEvent, DevEvent>> xw_pool;
   size_t xw_used = 0;
   std::vector<EvPair> evs;
   mcx_profile prof{};
@@ -403,15 +484,15 @@ struct ProfScope {
     if (!on) return;
     p.kind = kind;
     p.chain_steps = cs;
-    (void)hipEventCreate(&p.a);
-    (void)hipEventCreate(&p.b);
+    (void)p.a.ensure(hipEventDefault);  // (a failure costs the pair its time, not the call: prof_collect skips it)
+    (void)p.b.ensure(hipEventDefault);
     (void)hipEventRecord(p.a, e->stream);
   }
   ~ProfScope()
   {
     if (!on) return;
     (void)hipEventRecord(p.b, e->stream);
-    e->evs.push_back(p);
+    e->evs.push_back(std::move(p));
   }
 };
 

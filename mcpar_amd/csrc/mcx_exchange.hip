@@ -14,10 +14,10 @@ int exchange_wait(mcx_engine *e)
   // the wait as the step stream sees it: an event on either side (collected by xwait_collect once the stream is idle)
   const bool timed = e->xw_used < XW_MAX;
   if (timed && e->xw_used == e->xw_pool.size()) {
-    hipEvent_t a = nullptr, b = nullptr;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
-    e->xw_pool.emplace_back(a, b);
+    DevEvent a, b;
+    MCXCHK(a.ensure(hipEventDefault));
+    MCXCHK(b.ensure(hipEventDefault));
+    e->xw_pool.emplace_back(std::move(a), std::move(b));
   }
   if (timed) HIPCHK(hipEventRecord(e->xw_pool[e->xw_used].first, e->stream));
   if (e->xfn(e->xctx, MCX_XCHG_WAIT, e->musigall.p, 2 * (size_t)e->ntot, e->rank, e->size, e->stream) != 0)
@@ -175,9 +175,9 @@ int rccl_install(mcx_engine *e, ncclComm_t comm, bool owned)
   NCCLCHK(g_rccl.CommUserRank(comm, &rk));
   if (cnt != e->size || rk != e->rank)
     return fail(MCX_ERR_INVALID, "communicator is rank %d of %d but the engine is shard %d of %d", rk, cnt, e->rank, e->size);
-  if (!e->xstream) HIPCHK(hipStreamCreateWithFlags(&e->xstream, hipStreamNonBlocking));
-  if (!e->xready) HIPCHK(hipEventCreateWithFlags(&e->xready, hipEventDisableTiming));
-  if (!e->xdone) HIPCHK(hipEventCreateWithFlags(&e->xdone, hipEventDisableTiming));
+  MCXCHK(e->xstream.ensure(hipStreamNonBlocking));
+  MCXCHK(e->xready.ensure(hipEventDisableTiming));
+  MCXCHK(e->xdone.ensure(hipEventDisableTiming));
   e->xcomm = comm;
   e->xcomm_owned = owned;
   e->xfn = rccl_exchange;
@@ -241,9 +241,9 @@ extern "C" int mcx_exchange_rccl_destroy(mcx_engine *e)
     e->xcomm_owned = false;
     e->xchg_pending = false;
   }
-  if (e->xready) { (void)hipEventDestroy(e->xready); e->xready = nullptr; }
-  if (e->xdone) { (void)hipEventDestroy(e->xdone); e->xdone = nullptr; }
-  if (e->xstream) { (void)hipStreamDestroy(e->xstream); e->xstream = nullptr; }
+  e->xready.reset();
+  e->xdone.reset();
+  e->xstream.reset();
   return MCX_OK;
 }
 

@@ -293,11 +293,11 @@ static int screen_sweep_chunked(mcx_engine *e, const float *xrows, const int *ai
   ScreenLaunch L;
   MCXCHK((screen_prepare<DM>(e, xrows, ain, nact, SUMS, own0, fresh_q, order_out, st, true, &L, chunks)));
   const ScreenView v = screen_view(e, SUMS);
-  if (!e->mstream) HIPCHK(hipStreamCreateWithFlags(&e->mstream, hipStreamNonBlocking));
+  MCXCHK(e->mstream.ensure(hipStreamNonBlocking));
   while ((int)e->mev.size() < chunks + 1) {
-    hipEvent_t ev = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    e->mev.push_back(ev);
+    DevEvent ev;
+    MCXCHK(ev.ensure(hipEventDisableTiming));
+    e->mev.push_back(std::move(ev));
   }
   {
     // (profile: the phase as a whole counts as the sweep -- the screen has no time of its own any more)
@@ -785,11 +785,6 @@ static int debug_screen(int nact, int N, const float *x, const float *musig, int
     DevBuf<unsigned> hist;
     DevBuf<unsigned short> A, B;
     DevBuf<unsigned long long> excl, kept;
-    ~Bufs()
-    {
-      dx.release(); dms.release(); q.release(); centre.release(); stats.release(); hist.release(); A.release(); B.release();
-      excl.release(); kept.release();
-    }
   } b;
   MCXCHK(b.dx.alloc((size_t)nact * d)); MCXCHK(b.dms.alloc((size_t)N * d * 2)); MCXCHK(b.q.alloc((size_t)N * d * 2));
   MCXCHK(b.centre.alloc(64)); MCXCHK(b.stats.alloc(2 * CULL_KD)); MCXCHK(b.hist.alloc(CULL_BINS));

@@ -248,10 +248,6 @@ struct RankScratch {
   DevBuf<float> xs, lys;
   DevBuf<uint32_t> ka, kb, hist, rowsum;
   DevBuf<double> thr, ranks;
-  ~RankScratch()
-  {
-    xs.release(); lys.release(); ka.release(); kb.release(); hist.release(); rowsum.release(); thr.release(); ranks.release();
-  }
 };
 
 // one rank-normalised summary of a view: what its stages share
@@ -309,7 +305,7 @@ int rank_scratch(RankPass &p)
     if (G == 1)
       return fail(MCX_ERR_ALLOC, "rank summary: %zu bytes of scratch are needed for one column at a time (DESIGN.md section 11)",
                   N * ncol * 4 + N * 8 + ((size_t)p.nblk + 1) * 1024 + (size_t)ncol * 24);
-    S.ka.release(); S.kb.release(); S.hist.release(); S.rowsum.release();
+    S.ka.release(); S.kb.release(); S.hist.release(); S.rowsum.release();  // mid-life: room for the next, smaller try
   }
   p.G = G;
   return MCX_OK;

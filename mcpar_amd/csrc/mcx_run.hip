@@ -523,13 +523,13 @@ static int prepare_outputs(Run &r)
         MCXCHK(e->sink_text_total[b].alloc(1));
       }
       if (!e->tfn) MCXCHK(e->sink_pin[b].alloc((size_t)kb * n * (d + 1)));
-      if (!e->ev_steps[b]) HIPCHK(hipEventCreateWithFlags(&e->ev_steps[b], hipEventDisableTiming));
-      if (!e->ev_copy[b]) HIPCHK(hipEventCreateWithFlags(&e->ev_copy[b], hipEventDisableTiming));
-      if (!e->ev_write[b]) HIPCHK(hipEventCreateWithFlags(&e->ev_write[b], hipEventDisableTiming));
+      MCXCHK(e->ev_steps[b].ensure(hipEventDisableTiming));
+      MCXCHK(e->ev_copy[b].ensure(hipEventDisableTiming));
+      MCXCHK(e->ev_write[b].ensure(hipEventDisableTiming));
     }
-    if (!e->cstream) HIPCHK(hipStreamCreateWithFlags(&e->cstream, hipStreamNonBlocking));
-    if (!e->tstream) HIPCHK(hipStreamCreateWithFlags(&e->tstream, hipStreamNonBlocking));
-    if (!e->ev_text) HIPCHK(hipEventCreateWithFlags(&e->ev_text, hipEventDisableTiming));
+    MCXCHK(e->cstream.ensure(hipStreamNonBlocking));
+    MCXCHK(e->tstream.ensure(hipStreamNonBlocking));
+    MCXCHK(e->ev_text.ensure(hipEventDisableTiming));
   }
   MCXCHK(e->best_row.alloc((size_t)d + 1));
   MCXCHK(e->best_key.alloc(1));
@@ -986,9 +986,9 @@ static int finish_async(Run &r)
     e->run_queued[sl] = true;
   } else {
     r.reported = 0;
-    if (!e->astream) HIPCHK(hipStreamCreateWithFlags(&e->astream, hipStreamNonBlocking));
-    if (!e->run_ev[sl]) HIPCHK(hipEventCreateWithFlags(&e->run_ev[sl], hipEventDisableTiming));
-    if (!e->copy_ev[sl]) HIPCHK(hipEventCreateWithFlags(&e->copy_ev[sl], hipEventDisableTiming));
+    MCXCHK(e->astream.ensure(hipStreamNonBlocking));
+    MCXCHK(e->run_ev[sl].ensure(hipEventDisableTiming));
+    MCXCHK(e->copy_ev[sl].ensure(hipEventDisableTiming));
     HIPCHK(hipEventRecord(e->run_ev[sl], st));
     e->run_queued[sl] = true;
     HIPCHK(hipStreamWaitEvent(e->astream, e->run_ev[sl], 0));

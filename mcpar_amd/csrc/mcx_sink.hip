@@ -216,11 +216,8 @@ extern "C" int mcx_format_rows(const float *rows, size_t nrows, int ncol, char *
   DevBuf<unsigned long long> wg;
   DevBuf<char> dev;
   const size_t count = nrows * (size_t)ncol;
-  int rc = dr.alloc(count);
-  if (rc == MCX_OK && count && hipMemcpy(dr.p, rows, count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(MCX_ERR_HIP, "hipMemcpy failed");
-  if (rc == MCX_OK) rc = text_of_rows(dr.p, nullptr, count, ncol - 1, wg, dev, nullptr, text, capacity, nbytes);
-  dr.release(); wg.release(); dev.release();
-  return rc;
+  MCXCHK(dr.alloc(count));
+  if (count) HIPCHK(hipMemcpy(dr.p, rows, count * sizeof(float), hipMemcpyHostToDevice));
+  return text_of_rows(dr.p, nullptr, count, ncol - 1, wg, dev, nullptr, text, capacity, nbytes);
 }
 

@@ -187,9 +187,9 @@ template <class F> int on_rows(const float *rows, int nsteps, int nc, int np, F 
   DevBuf<double> d;
   DevBuf<unsigned long long> h;
   DevBuf<uint32_t> u;
-  hipStream_t st = nullptr;
+  DevStream st;
   auto run = [&]() -> int {
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    MCXCHK(st.ensure(hipStreamNonBlocking));
     MCXCHK(rd.alloc(nr * (np + 1)));
     MCXCHK(x.alloc(nr * np));
     MCXCHK(ly.alloc(nr));
@@ -199,11 +199,7 @@ template <class F> int on_rows(const float *rows, int nsteps, int nc, int np, F 
     return f(st, Bufs{&d, &h, &u}, StoreView(StoreSpan{x.p, ly.p, nc, np, nsteps}));
   };
   const int rc = run();
-  if (st) {
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-  }
-  rd.release(); x.release(); ly.release(); d.release(); h.release(); u.release();
+  if (st) (void)hipStreamSynchronize(st);  // (before the buffers go)
   return rc;
 }
 
@@ -237,18 +233,19 @@ struct StageTimer {
   hipStream_t st;
   double *ms;
   int nslots;
-  struct Ev { int idx; hipEvent_t a, b; };
+  struct Ev { int idx; DevEvent a, b; };
   std::vector<Ev> evs;
   template <class F> int run(int idx, F f)
   {
     if (!ms) return f();
-    Ev e{idx, nullptr, nullptr};
-    HIPCHK(hipEventCreate(&e.a));
-    HIPCHK(hipEventCreate(&e.b));
-    evs.push_back(e);
-    HIPCHK(hipEventRecord(e.a, st));
+    Ev e{idx, {}, {}};
+    MCXCHK(e.a.ensure(hipEventDefault));
+    MCXCHK(e.b.ensure(hipEventDefault));
+    const size_t k = evs.size();  // (f may run stages of its own: evs grows and moves under it)
+    evs.push_back(std::move(e));
+    HIPCHK(hipEventRecord(evs[k].a, st));
     MCXCHK(f());
-    HIPCHK(hipEventRecord(e.b, st));
+    HIPCHK(hipEventRecord(evs[k].b, st));
     return MCX_OK;
   }
   int collect()
@@ -262,13 +259,6 @@ struct StageTimer {
       ms[e.idx] += (double)t;
     }
     return MCX_OK;
-  }
-  ~StageTimer()
-  {
-    for (const Ev &e : evs) {
-      if (e.a) (void)hipEventDestroy(e.a);
-      if (e.b) (void)hipEventDestroy(e.b);
-    }
   }
 };
 

@@ -381,6 +381,13 @@ def derive_rows(rows, nsteps, nc, spec):
     return DerivedStore(h)
 
 
+def debug_live_resources():
+    """mcx_debug_live_resources (needs no GPU): (device allocations, pinned allocations, streams, events) the library holds now"""
+    out = (C.c_uint64 * 4)()
+    check(load().mcx_debug_live_resources(out))
+    return tuple(int(v) for v in out)
+
+
 def debug_draw_indices(seed, N, first, n):
     """mcx_debug_draw_indices (host only): the rows of draws first .. first + n - 1 among N rows, int64"""
     out = np.empty(max(n, 0), np.int64)
