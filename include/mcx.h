@@ -488,6 +488,62 @@ int mcx_store_draw(mcx_store *s, uint32_t seed, int64_t ndraw, float *rows, int6
 /* host only: index[k] = the row of draw first + k among N rows, k < n */
 int mcx_debug_draw_indices(uint32_t seed, uint64_t N, uint64_t first, int n, int64_t *index);
 
+/* ---- densities of the sample store, on the device -------------------
+ * The reference's mcparam.density (src/anly/mcpar-analysis.R:22-28): per column (the parameters, then log L; of a derived
+ * store the nout outputs, then log L) the binned Gaussian kernel density estimate of R's density.default, which is what
+ * geom_density evaluates.  N = nsteps * nc >= 2 values per column, a grid of n_g = 512 points, n output points.
+ *   mean, sd, min, max, q25, q75   mcx_samples_summary's numbers (its type-7 quantiles for probs 0.25 and 0.75), bit for bit
+ *   bw         bw.nrd0: hi = sd, lo_ = min(hi, (q75 - q25) / 1.34), or hi where that is 0, or |min|, or 1;
+ *              bw = adjust * 0.9 * lo_ * N^(-1/5).  A positive finite spec->bw[c] replaces it (adjust is not applied)
+ *   from, to   min and max; with clip other than (0, 1) the type-7 quantiles of clip_lo and clip_hi, except that the last
+ *              column, log L, keeps to = max (the exception of mcparam.clip.tails); finite spec->from[c] / to[c] override
+ *   lo, up     from - 4 bw, to + 4 bw;  delta = (up - lo) / 511,  inv = 511 / (up - lo)
+ *   binning    every value v: xpos = (double(v) - lo) * inv, ix = floor(xpos), w = floor((xpos - ix) * 2^24); for
+ *              -1 <= ix <= 511 slot ix + 1 gets cnt += 1 and frac += w (both u64); every other value is dropped;
+ *              nbinned = the sum of cnt over the slots 1 .. 512
+ *   masses     y[k] = (cnt[k+1] - frac[k+1] / 2^24 + frac[k] / 2^24) / N for k < 512, 0 for 512 <= k < 1024
+ *   kernel     K[m] = exp(-(k_m / bw)^2 / 2) / (bw sqrt(2 pi)), k_m = m delta for m <= 512, -(1024 - m) delta above
+ *   d[j]       = max(0, sum over m of y[m] K[(m - j) mod 1024]), j < 512: a plain fp64 sum on the host
+ *   x[j]       = from + j (to - from) / (n - 1), x[n-1] = to;  y[j] = the linear interpolation of (lo + k delta, d[k]) at x[j]
+ * The sweep adds integers only: the same store and arguments give the same bytes.  A column holding an inf or NaN has
+ * MCX_SUMMARY_NONFINITE, NaN in every double of its record and of its x and y, and nbinned = 0; every other column is what
+ * it would be without that column. */
+typedef struct mcx_density_spec {
+  int n;                    /* output points per column, 2..512 */
+  double adjust;            /* > 0; multiplies the nrd0 bandwidth */
+  double clip_lo, clip_hi;  /* 0, 1 = the data's range; else 0 <= clip_lo < clip_hi <= 1 */
+  const double *bw, *from, *to; /* NULL, or [ncol]; a NaN entry = the default of that column */
+} mcx_density_spec;
+typedef struct mcx_col_density {
+  double bw, from, to, lo, up, mean, sd;
+  long long nvalues, nbinned;
+  int flags;                /* MCX_SUMMARY_* */
+} mcx_col_density;
+/* Steps [first_step, first_step + nsteps) of the store; cols[np + 1], x and y [np + 1][n].  MCX_ERR_INVALID in the cases
+ * mcx_samples_summary refuses (but any nsteps >= 1 with nsteps * nc >= 2 will do), and for n outside 2..512, adjust <= 0 or
+ * not finite, clip probabilities out of order, a given bw <= 0 or from > to: the spec is checked before a device is
+ * touched.  A queued MCX_OPT_ASYNC_RUN run is finished first. */
+int mcx_samples_density(mcx_engine *e, int first_step, int nsteps, const mcx_density_spec *spec, mcx_col_density *cols,
+                        double *x, double *y);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows), and for a derived store */
+int mcx_rows_density(const float *rows, int nsteps, int nc, int np, const mcx_density_spec *spec, mcx_col_density *cols,
+                     double *x, double *y);
+int mcx_store_density(mcx_store *s, const mcx_density_spec *spec, mcx_col_density *cols, double *x, double *y);
+/* The two host steps of a density call for one column (no device): the record of column `col` (the index into the spec's
+ * arrays) from its statistics -- qclip_* are read only with a clip pair --, nbinned left 0; and x[n], y[n] from the record
+ * and the column's slots[513][2] = (cnt, frac).  The product path calls these very functions. */
+int mcx_debug_density_grid(long long N, double mean, double sd, float min, float max, double q25, double q75,
+                           double qclip_lo, double qclip_hi, int is_last_col, int col, const mcx_density_spec *spec,
+                           mcx_col_density *out);
+int mcx_debug_density_finish(const mcx_col_density *col, const unsigned long long *slots, int n, double *x, double *y);
+/* the device sweep alone on given grids lo[np + 1] < up[np + 1]: slots[np + 1][513][2] */
+int mcx_debug_rows_density_bins(const float *rows, int nsteps, int nc, int np, const double *lo, const double *up,
+                                unsigned long long *slots);
+/* one mcx_samples_density call, its results let go: ms[0] the statistics passes (wall clock), ms[1] the binning sweep
+ * (HIP events), ms[2] the host grid and finish (wall clock), ms[3] the whole call (wall clock) */
+int mcx_debug_density_times(mcx_engine *e, int first_step, int nsteps, const mcx_density_spec *spec, double *ms);
+int mcx_debug_store_density_times(mcx_store *s, const mcx_density_spec *spec, double *ms); /* the same of a derived store */
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

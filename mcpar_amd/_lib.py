@@ -29,6 +29,12 @@ class Derive(C.Structure):
                 ("source", C.c_char_p)]
 
 
+class DensitySpecC(C.Structure):
+    """include/mcx.h mcx_density_spec"""
+    _fields_ = [("n", C.c_int), ("adjust", C.c_double), ("clip_lo", C.c_double), ("clip_hi", C.c_double),
+                ("bw", C.POINTER(C.c_double)), ("from_", C.POINTER(C.c_double)), ("to", C.POINTER(C.c_double))]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -128,6 +134,15 @@ def load():
         "mcx_samples_draw": [vp, C.c_int, C.c_int, C.c_uint32, C.c_int64, fp, C.POINTER(C.c_int64)],
         "mcx_store_draw": [vp, C.c_uint32, C.c_int64, fp, C.POINTER(C.c_int64)],
         "mcx_debug_draw_indices": [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int64)],
+        "mcx_samples_density": [vp, C.c_int, C.c_int, C.POINTER(DensitySpecC), vp, dp, dp],
+        "mcx_rows_density": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(DensitySpecC), vp, dp, dp],
+        "mcx_store_density": [vp, C.POINTER(DensitySpecC), vp, dp, dp],
+        "mcx_debug_density_grid": [C.c_longlong, C.c_double, C.c_double, C.c_float, C.c_float, C.c_double, C.c_double,
+                                   C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(DensitySpecC), vp],
+        "mcx_debug_density_finish": [vp, C.POINTER(C.c_ulonglong), C.c_int, dp, dp],
+        "mcx_debug_rows_density_bins": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_ulonglong)],
+        "mcx_debug_density_times": [vp, C.c_int, C.c_int, C.POINTER(DensitySpecC), dp],
+        "mcx_debug_store_density_times": [vp, C.POINTER(DensitySpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

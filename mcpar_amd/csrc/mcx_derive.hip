@@ -331,6 +331,23 @@ extern "C" int mcx_store_covariance(mcx_store *s, double *mean, double *cov, int
   return covariance_span(s->st, s->bufs(), s->span(), mean, cov, flags);
 }
 
+extern "C" int mcx_store_density(mcx_store *s, const mcx_density_spec *spec, mcx_col_density *cols, double *x, double *y)
+{
+  MCXCHK(store_enter(s));
+  return density_span(s->st, s->bufs(), s->span(), spec, cols, x, y);
+}
+
+// mcx_store_density with its stages timed (mcx_debug_density_times' ms[4]), for tools/density_bench.py; the results are let go
+extern "C" int mcx_debug_store_density_times(mcx_store *s, const mcx_density_spec *spec, double *ms)
+{
+  MCXCHK(store_enter(s));
+  if (!ms || !spec) return fail(MCX_ERR_INVALID, "ms or the density spec is NULL");
+  const size_t ncol = (size_t)s->nout + 1, n = (size_t)std::max(spec->n, 1);
+  std::vector<mcx_col_density> cols(ncol);
+  std::vector<double> x(ncol * n), y(ncol * n);
+  return density_span(s->st, s->bufs(), s->span(), spec, cols.data(), x.data(), y.data(), ms);
+}
+
 extern "C" int mcx_samples_draw(mcx_engine *e, int first_step, int nsteps, uint32_t seed, int64_t ndraw, float *rows, int64_t *index)
 {
   return on_store(

@@ -329,16 +329,17 @@ int geyer_wants(const SummaryPass &p, int c, int *more)
 }
 
 // ---- 3. autocovariance windows -> acov, ss, nwin: 2, 4, 8, ... windows a launch (KWMAX and the half-chain's length cap
-// them) for the finite columns, while wants(p, c, &more) says that some column wants more lags than it holds
-template <class W> int acov_windows(SummaryPass &p, W wants)
+// them) for the finite columns, while wants(p, c, &more) says that some column wants more lags than it holds.  kw0: the
+// windows of the first launch (summary_spread wants window 0 alone: the centred sum of squares)
+template <class W> int acov_windows(SummaryPass &p, W wants, int kw0 = 2)
 {
   const StoreView &v = p.v;
   const int ncol = v.ncol;
   double *D = p.D;
   std::vector<int> active(ncol);
   for (int c = 0; c < ncol; ++c) active[c] = std::isfinite(p.cs[c]) ? 1 : 0;
-  const int nwin_max = (int)((v.n + WLAG - 1) / WLAG);
-  int k0 = 0, KW = 2;
+  const int nwin_max = std::max(1, (int)((v.n + WLAG - 1) / WLAG));  // (window 0 also where a range of < 2 steps has no half-chain)
+  int k0 = 0, KW = kw0;
   std::vector<double> win;
   while (k0 < nwin_max && std::count(active.begin(), active.end(), 1) > 0) {
     KW = std::min({KW, KWMAX, nwin_max - k0});
@@ -424,6 +425,31 @@ int summary_mixing(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_summary *
   MCXCHK(moments_pass(p));
   MCXCHK(acov_windows(p, geyer_wants));
   return finish_columns(p, cols, nullptr);
+}
+
+int summary_spread(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles)
+{
+  const StoreView v(s);
+  SummaryPass p(st, B, v, probs, nprobs);
+  MCXCHK(moments_pass(p));
+  MCXCHK(order_stats_pass(p));
+  MCXCHK(acov_windows(
+      p,
+      [](const SummaryPass &, int, int *more) {
+        *more = 0;
+        return MCX_OK;
+      },
+      1));
+  // the finish without lags reads its n and M nowhere: mean, sd, the order statistics and the quantiles, by finish_column's
+  // expressions, for any range of N >= 2 values
+  std::vector<float> os(p.nt);
+  for (int c = 0; c < v.ncol; ++c) {
+    for (int k = 0; k < p.nt; ++k) os[k] = key_float(p.pre[(size_t)c * p.nt + k]);
+    int more = 0;
+    MCXCHK(mcx_debug_summary_finish(2, 2, p.cs[c] / (double)v.N, p.ss[c] / (double)(v.N - 1), 0.0, nullptr, 0, os.data(), v.N, probs, nprobs,
+                                    std::isfinite(p.cs[c]) ? 0 : MCX_SUMMARY_NONFINITE, &cols[c], quantiles + (size_t)c * nprobs, &more));
+  }
+  return MCX_OK;
 }
 
 int summary_span(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols, double *quantiles)

@@ -4,8 +4,9 @@
 // store is a third way: a span handed to summary_span / rank_span / covariance_span below), pass 1 of every analysis (k_sum_moments: per-series fp64 sums), the
 // fixed-order reducer k_sum_rows that every cross-chain or cross-workgroup sum goes through, and the stage timer of the
 // mcx_debug_*_times entry points.  Internal to the three analysis units (each gets its own copy of the kernels).
-// mcx_derive.hip includes it for the view plumbing alone (on_store, on_rows with its k_sum_deinterleave, StageTimer); the
-// other kernels' copies in that unit are never launched;
+// mcx_derive.hip and mcx_density.hip (section 13, which has its own sweep and gets its statistics from summary_spread below)
+// include it for the view plumbing alone (on_store, on_rows with its k_sum_deinterleave, StageTimer); the
+// other kernels' copies in those units are never launched;
 // nothing here is part of the library's interface.
 #pragma once
 #include "mcx_engine_internal.hpp"
@@ -29,6 +30,11 @@ struct StoreSpan {
 MCXI int summary_thresholds(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
                             double *quantiles);
 MCXI int summary_mixing(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_summary *cols);
+// and for mcx_density.hip (section 13): moments, order statistics, window 0 of the autocovariance for the centred sum of
+// squares, the finish without lags -- mean, sd, min, max, flags and the quantiles are mcx_samples_summary's bits; rhat, ess,
+// ess_lag and mcse_mean of cols are not valid.  Any range of N >= 2 values (the summary's nsteps >= 4 is not asked)
+MCXI int summary_spread(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
+                        double *quantiles);
 
 // The three analyses on any span, for the third way to a view (mcx_derive.hip: a derived store): each checks its own
 // arguments as its mcx_samples_* entry point does, then runs the passes of that entry point on a StoreView of the span
@@ -36,6 +42,8 @@ MCXI int summary_span(hipStream_t st, Bufs B, const StoreSpan &s, const double *
                       double *quantiles);                                                          // mcx_summary.hip
 MCXI int rank_span(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_rank_summary *cols);        // mcx_ranks.hip
 MCXI int covariance_span(hipStream_t st, Bufs B, const StoreSpan &s, double *mean, double *cov, int *flags);  // mcx_covariance.hip
+MCXI int density_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_density_spec *spec, mcx_col_density *cols, double *x,
+                      double *y, double *ms = nullptr);  // mcx_density.hip; ms: mcx_debug_density_times' four stages
 
 namespace {
 

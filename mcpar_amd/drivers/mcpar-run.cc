@@ -7,6 +7,7 @@
 //             [--derive-source FILE.hip --derive-nout K [--derive-par a,b,...] | --derive-linear FILE]
 //             [--derived-summary FILE] [--derived-rank-summary FILE] [--derived-covariance FILE]
 //             [--draws FILE --ndraw N [--draw-seed S]]
+//             [--density FILE] [--derived-density FILE] [--density-n N] [--density-clip QLO,QHI]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -29,6 +30,11 @@
 // --covariance for the derived columns d0 .. d{K-1}, then LL (mcx_store_summary, ...).  Under the conditions of --summary.
 // --draws FILE --ndraw N [--draw-seed S]: N of the kept rows drawn with replacement, as the text of the sample output; the
 // row of draw i is mcx_samples_draw's (mcx_debug_draw_indices of seed S, default 8675309).  Under the conditions of --summary.
+// --density FILE: the kernel density estimate of every column of the kept rows on the GPU (mcx_rows_density; R's density() /
+// geom_density, the reference's mcparam.density) in long form: a header `column x density`, then --density-n (default 512)
+// lines `name x y` per column p0 .. LL.  --density-clip QLO,QHI: from the QLO to the QHI quantile of a column instead of min to
+// max (log L keeps its maximum).  --derived-density FILE: the same for the derived columns d0 .. LL.  Both under the
+// conditions of --summary.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -166,9 +172,39 @@ static int write_covariance(const char *cov_path, const char *prop_path, MCout &
   return 0;
 }
 
-// --derived-*: the three files for the K derived columns of MCout's rows, through one derived store on the device
-static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, MCout &rows, int nsamp,
-                         int nc, int np)
+static int print_density(const char *path, const std::vector<double> &x, const std::vector<double> &y, int np, int n, char prefix)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "column x density\n");
+  for (int c = 0; c <= np; ++c)
+    for (int j = 0; j < n; ++j) fprintf(f, "%s %.17g %.17g\n", colname(prefix, c, np).c_str(), x[(size_t)c * n + j], y[(size_t)c * n + j]);
+  return fclose(f) == 0 ? 0 : 1;
+}
+
+// --density: the density estimate of every column of MCout's rows, n lines per column
+static int write_density(const char *path, const mcx_density_spec &spec, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || (long long)nsamp * nc < 2) {
+    std::cerr << "--density: " << rows.size() << " rows stored, a density needs nsamp * nc >= 2 of them\n";
+    return 1;
+  }
+  const size_t ncol = (size_t)np + 1, n = (size_t)(spec.n > 0 ? spec.n : 1);
+  std::vector<mcx_col_density> cols(ncol);
+  std::vector<double> x(ncol * n), y(ncol * n);
+  if (mcx_rows_density(rows.getpset(0), nsamp, nc, np, &spec, cols.data(), x.data(), y.data()) != MCX_OK) {
+    std::cerr << "--density: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  return print_density(path, x, y, np, spec.n, 'p');
+}
+
+// --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
+static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
+                         const mcx_density_spec &dspec, MCout &rows, int nsamp, int nc, int np)
 {
   if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
     std::cerr << "--derived-*: " << rows.size() << " rows stored, a derive needs nsamp * nc of them\n";
@@ -202,6 +238,15 @@ static int write_derived(const mcx_derive &spec, const char *sum_path, const cha
       std::cerr << "--derived-covariance: " << mcx_last_error() << "\n";
       rc = 1;
     } else rc = print_covariance(cov_path, mean, cov, K, 'd');
+  }
+  if (rc == 0 && dens_path) {
+    const size_t n = (size_t)(dspec.n > 0 ? dspec.n : 1);
+    std::vector<mcx_col_density> cols((size_t)K + 1);
+    std::vector<double> x(((size_t)K + 1) * n), y(((size_t)K + 1) * n);
+    if (mcx_store_density(st, &dspec, cols.data(), x.data(), y.data()) != MCX_OK) {
+      std::cerr << "--derived-density: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_density(dens_path, x, y, K, dspec.n, 'd');
   }
   mcx_store_destroy(st);
   return rc;
@@ -311,6 +356,8 @@ int main(int argc, char *argv[])
   bool quiet = false, iter = false, binary = false, stream_text = false;
   std::string out_file, func_source, summary_file, rank_summary_file, covariance_file, proposal_file, incov_file;
   std::string derive_source_file, derive_linear_file, derived_summary_file, derived_rank_summary_file, derived_covariance_file, draws_file;
+  std::string density_file, derived_density_file;
+  mcx_density_spec density_spec = {512, 1.0, 0.0, 1.0, 0, 0, 0};
   std::vector<float> user_par, derive_par;
   int derive_nout = 0;
   long long ndraw = 0;
@@ -351,6 +398,15 @@ int main(int argc, char *argv[])
     else if (a == "--derived-summary") derived_summary_file = val();
     else if (a == "--derived-rank-summary") derived_rank_summary_file = val();
     else if (a == "--derived-covariance") derived_covariance_file = val();
+    else if (a == "--density") density_file = val();
+    else if (a == "--derived-density") derived_density_file = val();
+    else if (a == "--density-n") density_spec.n = atoi(val());
+    else if (a == "--density-clip") {
+      if (sscanf(val(), "%lf,%lf", &density_spec.clip_lo, &density_spec.clip_hi) != 2) {
+        std::cerr << "--density-clip takes QLO,QHI\n";
+        return 2;
+      }
+    }
     else if (a == "--draws") draws_file = val();
     else if (a == "--ndraw") ndraw = atoll(val());
     else if (a == "--draw-seed") draw_seed = (unsigned)strtoul(val(), 0, 10);
@@ -381,7 +437,15 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
-  const bool want_derived = !derived_summary_file.empty() || !derived_rank_summary_file.empty() || !derived_covariance_file.empty();
+  if (!density_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--density needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  const bool want_derived = !derived_summary_file.empty() || !derived_rank_summary_file.empty() || !derived_covariance_file.empty() ||
+                            !derived_density_file.empty();
   const bool have_derive = !derive_source_file.empty() || !derive_linear_file.empty();
   if ((want_derived || !draws_file.empty()) && (stream_text || size > 1)) {
     if (rank == 0)
@@ -488,6 +552,10 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
+  if (!density_file.empty() && write_density(density_file.c_str(), density_spec, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
   if (want_derived) {
     mcx_derive spec = {MCX_DERIVE_LINEAR, derive_nout, 0, 0, 0};
     std::string text;
@@ -513,7 +581,8 @@ int main(int argc, char *argv[])
     spec.par = derive_par.empty() ? 0 : derive_par.data();
     if (write_derived(spec, derived_summary_file.empty() ? 0 : derived_summary_file.c_str(),
                       derived_rank_summary_file.empty() ? 0 : derived_rank_summary_file.c_str(),
-                      derived_covariance_file.empty() ? 0 : derived_covariance_file.c_str(), rslts, nsamp, nc, np) != 0) {
+                      derived_covariance_file.empty() ? 0 : derived_covariance_file.c_str(),
+                      derived_density_file.empty() ? 0 : derived_density_file.c_str(), density_spec, rslts, nsamp, nc, np) != 0) {
       MPI_Finalize();
       return 2;
     }

@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, Counters, Derive, PlanItem, Profile, VLFunc, check,
-                   load)
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, Counters, DensitySpecC, Derive, PlanItem, Profile,
+                   VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -41,6 +41,12 @@ RANK_SUMMARY_DTYPE = np.dtype([("rhat", np.float64), ("rhat_bulk", np.float64), 
                                ("ess_q95", np.float64), ("q05", np.float64), ("median", np.float64), ("q95", np.float64),
                                ("ess_bulk_lag", np.int32), ("flags", np.int32)], align=True)
 assert RANK_SUMMARY_DTYPE.itemsize == 88
+# include/mcx.h mcx_col_density
+DENSITY_DTYPE = np.dtype([("bw", np.float64), ("from", np.float64), ("to", np.float64), ("lo", np.float64), ("up", np.float64),
+                          ("mean", np.float64), ("sd", np.float64), ("nvalues", np.int64), ("nbinned", np.int64),
+                          ("flags", np.int32)], align=True)
+assert DENSITY_DTYPE.itemsize == 80
+DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
 
@@ -284,6 +290,81 @@ def rows_covariance(rows, nsteps, nc):
     return _covariance_dict(mean, cov, flags)
 
 
+# ---- densities (include/mcx.h) ----
+class DensitySpec:
+    """an mcx_density_spec and the arrays it points to: n output points, adjust times the nrd0 bandwidth, clip = (qlo, qhi)
+    quantiles as the range ((0, 1): min to max), bw / from_ / to = None or [ncol] with NaN for a column's default"""
+
+    def __init__(self, n=512, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None):
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1))  # noqa: E731
+        ptr = lambda a: None if a is None else _dp(a)  # noqa: E731
+        self.n, self.bw, self.from_, self.to = int(n), arr(bw), arr(from_), arr(to)
+        self.c = DensitySpecC(self.n, float(adjust), float(clip[0]), float(clip[1]), ptr(self.bw), ptr(self.from_), ptr(self.to))
+
+    def fits(self, ncol):
+        for a in (self.bw, self.from_, self.to):
+            if a is not None and a.size != ncol:
+                raise ValueError("bw, from_ and to take one entry per column (%d), NaN for a column's default" % ncol)
+        return self
+
+
+def _density_out(ncol, n):
+    n = min(max(int(n), 1), DENSITY_GRID)  # (a refused n still gets buffers)
+    return np.zeros(ncol, DENSITY_DTYPE), np.zeros((ncol, n)), np.zeros((ncol, n))
+
+
+def _density_dict(cols, x, y):
+    out = {name: cols[name].copy() for name in DENSITY_DTYPE.names}
+    out["x"], out["y"] = x, y
+    return out
+
+
+def rows_density(rows, nsteps, nc, n=512, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None):
+    """mcx_rows_density: Engine.density's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    spec = DensitySpec(n, adjust, clip, bw, from_, to).fits(ncol)
+    cols, x, y = _density_out(ncol, n)
+    check(load().mcx_rows_density(_fp(rows), nsteps, nc, ncol - 1, C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), _dp(x), _dp(y)))
+    return _density_dict(cols, x, y)
+
+
+def debug_density_grid(N, mean, sd, min_, max_, q25, q75, qclip=(np.nan, np.nan), is_last_col=False, col=0, spec=None):
+    """mcx_debug_density_grid (host only): the record (DENSITY_DTYPE) of one column from its statistics"""
+    spec = spec or DensitySpec()
+    out = np.zeros(1, DENSITY_DTYPE)
+    check(load().mcx_debug_density_grid(int(N), mean, sd, min_, max_, q25, q75, qclip[0], qclip[1], int(bool(is_last_col)), col,
+                                        C.byref(spec.c), out.ctypes.data_as(C.c_void_p)))
+    return out[0]
+
+
+def debug_density_finish(col, slots, n=512):
+    """mcx_debug_density_finish (host only): (x [n], y [n]) of one column from its record and slots [513, 2] uint64"""
+    rec = np.zeros(1, DENSITY_DTYPE)
+    rec[0] = col
+    sl = np.ascontiguousarray(slots, np.uint64)
+    if sl.shape != (DENSITY_GRID + 1, 2):
+        raise ValueError("slots must be [513, 2]")
+    x, y = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    check(load().mcx_debug_density_finish(rec.ctypes.data_as(C.c_void_p), sl.ctypes.data_as(C.POINTER(C.c_ulonglong)), n, _dp(x), _dp(y)))
+    return x, y
+
+
+def debug_rows_density_bins(rows, nsteps, nc, lo, up):
+    """mcx_debug_rows_density_bins: the binning sweep alone over rows [nsteps * nc, np + 1] on the grids lo [np + 1] < up
+    [np + 1] -- slots [np + 1, 513, 2] uint64 (cnt, frac)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    lo = np.ascontiguousarray(np.asarray(lo, np.float64).reshape(-1))
+    up = np.ascontiguousarray(np.asarray(up, np.float64).reshape(-1))
+    if lo.size != ncol or up.size != ncol:
+        raise ValueError("lo and up take one entry per column")
+    slots = np.zeros((ncol, DENSITY_GRID + 1, 2), np.uint64)
+    check(load().mcx_debug_rows_density_bins(_fp(rows), nsteps, nc, ncol - 1, _dp(lo), _dp(up),
+                                             slots.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+    return slots
+
+
 # ---- derived columns and bootstrap draws (include/mcx.h, DESIGN.md section 12) ----
 class DeriveSpec:
     """an mcx_derive and the arrays it points to"""
@@ -364,6 +445,21 @@ class DerivedStore:
         mean, cov, flags = np.zeros(ncol), np.zeros((ncol, ncol)), np.zeros(ncol, np.int32)
         check(load().mcx_store_covariance(self.h, _dp(mean), _dp(cov), flags.ctypes.data_as(C.POINTER(C.c_int))))
         return _covariance_dict(mean, cov, flags)
+
+    def density(self, n=512, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None):
+        """Engine.density's dict for the derived columns, then log L"""
+        ncol = self.shape[2]
+        spec = DensitySpec(n, adjust, clip, bw, from_, to).fits(ncol)
+        cols, x, y = _density_out(ncol, n)
+        check(load().mcx_store_density(self.h, C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), _dp(x), _dp(y)))
+        return _density_dict(cols, x, y)
+
+    def density_times(self, n=512, adjust=1.0, clip=(0, 1)):
+        """mcx_debug_store_density_times: Engine.density_times' four stage times for this store"""
+        spec = DensitySpec(n, adjust, clip)
+        ms = np.zeros(4)
+        check(load().mcx_debug_store_density_times(self.h, C.byref(spec.c), _dp(ms)))
+        return ms
 
     def draw(self, ndraw, seed):
         """ndraw rows with replacement: (rows [ndraw, ncol], index [ndraw] int64), the index Engine.draw gives for the
@@ -818,6 +914,23 @@ class Engine:
         """mcx_debug_covariance_times: ms of (the column-sum sweep, the covariance sweep, the partials' reducer) of one call"""
         ms = np.zeros(3)
         self._on_store(load().mcx_debug_covariance_times, first_step, nsteps, _dp(ms))
+        return ms
+
+    def density(self, n=512, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None, first_step=0, nsteps=None):
+        """mcx_samples_density: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps) the
+        kernel density estimate of R's density() / geom_density -- a dict of arrays [np + 1]: bw, from, to, lo, up, mean, sd,
+        nvalues, nbinned, flags; x and y [np + 1, n], the points and the density at them"""
+        spec = DensitySpec(n, adjust, clip, bw, from_, to).fits(self.np + 1)
+        cols, x, y = _density_out(self.np + 1, n)
+        self._on_store(load().mcx_samples_density, first_step, nsteps, C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), _dp(x), _dp(y))
+        return _density_dict(cols, x, y)
+
+    def density_times(self, n=512, adjust=1.0, clip=(0, 1), first_step=0, nsteps=None):
+        """mcx_debug_density_times: ms of (the statistics passes, the binning sweep, the host grid and finish, the whole call)
+        of one density() call"""
+        spec = DensitySpec(n, adjust, clip)
+        ms = np.zeros(4)
+        self._on_store(load().mcx_debug_density_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
         return ms
 
     def derive(self, spec, first_step=0, nsteps=None):
