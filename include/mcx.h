@@ -544,6 +544,72 @@ int mcx_debug_rows_density_bins(const float *rows, int nsteps, int nc, int np, c
 int mcx_debug_density_times(mcx_engine *e, int first_step, int nsteps, const mcx_density_spec *spec, double *ms);
 int mcx_debug_store_density_times(mcx_store *s, const mcx_density_spec *spec, double *ms); /* the same of a derived store */
 
+/* ---- tail-clipped rows of the sample store, on the device -----------
+ * The reference's mcparam.clip.tails (src/anly/mcpar-analysis.R:60-78): every row that lies in the tail of any column is
+ * dropped, jointly, and the remaining rows are handed on.  The source is a step range of an engine's store, host rows in
+ * MCout layout, or a derived store: N = nsteps * nc >= 1 rows of ncol columns (the parameters or derived columns, then
+ * log L); row r is step r / nc, chain r % nc.
+ *   thresholds  per column c doubles lo[c], hi[c]: by default mcx_samples_summary's type-7 quantiles of the column for the
+ *               probabilities qlo and qhi, bit for bit.  The last column's upper threshold is ll_hi when that is not NaN
+ *               (the reference: the literal 0.0, "its theoretical maximum"; +inf: no upper clip; NaN: the qhi quantile,
+ *               like any other column).  A non-NaN spec->lo[c] / spec->hi[c] replaces the default of that column and side
+ *               (+-inf: that side is not clipped), for the last column also ll_hi.  With both bounds of every column given
+ *               no quantile pass runs and every flags is 0
+ *   predicate   a row is kept iff for every column (double)v[c] > lo[c] && (double)v[c] < hi[c]: strict, as in R.  A NaN
+ *               value or a NaN threshold fails both comparisons: a column whose default quantiles are NaN (a NaN among
+ *               its values) drops every row unless both its bounds are given.  +-inf values compare as IEEE says
+ *   row set     the K kept rows in source order, compacted on the device as x'[K][np], ly'[K], and with each its source
+ *               row index r (int64, ascending).  K = 0 is a valid row set
+ *   per column  nbelow[c] = the rows with !(v > lo[c]), nabove[c] = the rows with !(v < hi[c]), each counted whatever the
+ *               row's other columns say (a NaN value counts in both); flags[c] = MCX_SUMMARY_NONFINITE from the quantile pass
+ * Only integers are added and every kept row has one position: the same source and arguments give the same bytes. */
+typedef struct mcx_clip_spec {
+  double qlo, qhi;       /* 0 <= qlo < qhi <= 1 */
+  double ll_hi;          /* upper threshold of log L; NaN = its qhi quantile; the reference: 0.0 */
+  const double *lo, *hi; /* NULL, or [ncol]; a NaN entry = the default of that column and side */
+} mcx_clip_spec;
+typedef struct mcx_col_clip {
+  double lo, hi;         /* the thresholds used */
+  long long nbelow, nabove;
+  int flags;             /* MCX_SUMMARY_* */
+} mcx_col_clip;
+/* A row set: it owns its device memory and a stream, and depends neither on the engine nor on the store it came from -- a
+ * later mcx_run or mcx_destroy of that engine, or mcx_store_destroy of that store, leaves it intact.  One thread at a time
+ * per row set. */
+typedef struct mcx_rowset mcx_rowset;
+/* Steps [first_step, first_step + nsteps) of the engine's store, nsteps >= 1; cols[np + 1], *nkept = K.  out == NULL: the
+ * thresholds, the counts and K only, nothing is compacted or allocated.  MCX_ERR_INVALID for a NULL spec, cols or nkept
+ * and for probabilities out of order or outside [0, 1] (checked before a device is touched), and in the cases
+ * mcx_samples_summary refuses (the store does not hold the range); MCX_ERR_UNSUPPORTED for more rows than a grid of
+ * workgroups covers (2^31 - 1 tiles of 32 to 256 rows).  A queued MCX_OPT_ASYNC_RUN run is finished first. */
+int mcx_samples_clip(mcx_engine *e, int first_step, int nsteps, const mcx_clip_spec *spec, mcx_col_clip *cols, long long *nkept,
+                     mcx_rowset **out);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows), and for a derived store */
+int mcx_rows_clip(const float *rows, int nsteps, int nc, int np, const mcx_clip_spec *spec, mcx_col_clip *cols, long long *nkept,
+                  mcx_rowset **out);
+int mcx_store_clip(mcx_store *s, const mcx_clip_spec *spec, mcx_col_clip *cols, long long *nkept, mcx_rowset **out);
+int mcx_rowset_destroy(mcx_rowset *r);
+int mcx_rowset_shape(const mcx_rowset *r, long long *nrows, int *ncol, long long *nsource); /* K, ncol, N */
+/* kept rows [first_row, first_row + nrows) in MCout layout, rows[nrows][ncol], and their source row indices */
+int mcx_rowset_copy(mcx_rowset *r, long long first_row, long long nrows, float *rows);
+int mcx_rowset_index(mcx_rowset *r, long long first_row, long long nrows, long long *index);
+/* mcx_samples_draw's rule with N = K: draw i is kept row (r * K) >> 64, so this is mcparam.sample(mcparam.clip.tails(d)).
+ * index[ndraw] (may be NULL): the position in the row set.  ndraw > 0 with K = 0 is MCX_ERR_INVALID. */
+int mcx_rowset_draw(mcx_rowset *r, uint32_t seed, int64_t ndraw, float *rows, int64_t *index);
+/* How the analyses of sections 9 to 13 reach the kept rows: they work on series of chains, and a flat row set has none.  So
+ * the caller names a shape: kept rows [first_row, first_row + nsteps * nc) are copied, device to device, into a new store of
+ * nsteps steps of nc pseudo-chains (the flat layouts are identical).  mean, sd, min, max, quantiles, covariance, density
+ * and draws of that store are those of exactly these rows; its R-hat and ESS are of pseudo-chains and mean nothing.  The
+ * caller chooses nc and leaves out at most nc - 1 rows, knowingly.  MCX_ERR_INVALID when the range is not inside the row
+ * set or nsteps or nc < 1.  The store is the caller's (mcx_store_destroy) and outlives the row set. */
+int mcx_rowset_store(mcx_rowset *r, long long first_row, int nsteps, int nc, mcx_store **out);
+/* host only, no device: lo[ncol], hi[ncol] from q[ncol][2], the columns' (qlo, qhi) quantiles (NULL: all NaN), and the
+ * spec by the rule above.  The product path calls this very function. */
+int mcx_debug_clip_thresholds(int ncol, const double *q, const mcx_clip_spec *spec, double *lo, double *hi);
+/* one mcx_samples_clip call with a row set, its results let go: ms[0] the thresholds (the quantile passes; wall clock),
+ * ms[1] the mark sweep, ms[2] the scan, ms[3] the scatter sweep (HIP events), ms[4] the whole call (wall clock) */
+int mcx_debug_clip_times(mcx_engine *e, int first_step, int nsteps, const mcx_clip_spec *spec, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -35,6 +35,12 @@ class DensitySpecC(C.Structure):
                 ("bw", C.POINTER(C.c_double)), ("from_", C.POINTER(C.c_double)), ("to", C.POINTER(C.c_double))]
 
 
+class ClipSpecC(C.Structure):
+    """include/mcx.h mcx_clip_spec"""
+    _fields_ = [("qlo", C.c_double), ("qhi", C.c_double), ("ll_hi", C.c_double),
+                ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double))]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -143,6 +149,17 @@ def load():
         "mcx_debug_rows_density_bins": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_ulonglong)],
         "mcx_debug_density_times": [vp, C.c_int, C.c_int, C.POINTER(DensitySpecC), dp],
         "mcx_debug_store_density_times": [vp, C.POINTER(DensitySpecC), dp],
+        "mcx_samples_clip": [vp, C.c_int, C.c_int, C.POINTER(ClipSpecC), vp, C.POINTER(C.c_longlong), C.POINTER(vp)],
+        "mcx_rows_clip": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(ClipSpecC), vp, C.POINTER(C.c_longlong), C.POINTER(vp)],
+        "mcx_store_clip": [vp, C.POINTER(ClipSpecC), vp, C.POINTER(C.c_longlong), C.POINTER(vp)],
+        "mcx_rowset_destroy": [vp],
+        "mcx_rowset_shape": [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)],
+        "mcx_rowset_copy": [vp, C.c_longlong, C.c_longlong, fp],
+        "mcx_rowset_index": [vp, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong)],
+        "mcx_rowset_draw": [vp, C.c_uint32, C.c_int64, fp, C.POINTER(C.c_int64)],
+        "mcx_rowset_store": [vp, C.c_longlong, C.c_int, C.c_int, C.POINTER(vp)],
+        "mcx_debug_clip_thresholds": [C.c_int, dp, C.POINTER(ClipSpecC), dp, dp],
+        "mcx_debug_clip_times": [vp, C.c_int, C.c_int, C.POINTER(ClipSpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

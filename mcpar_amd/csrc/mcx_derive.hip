@@ -9,7 +9,7 @@
 //   mcx_samples_draw / mcx_store_draw      rows drawn with replacement; the index of draw i is a function of (seed, i, N) only
 #include "mcx_derive.hpp"
 
-#include "mcx_summary_kernels.hpp"
+#include "mcx_store.hpp"
 
 #include <map>
 
@@ -133,22 +133,7 @@ int derive_user_kernel(const char *source, int np, int nout, hipFunction_t *fn)
 // ---------------------------------------------------------------------------------------------------------------------
 // the derived store
 // ---------------------------------------------------------------------------------------------------------------------
-struct mcx_store {
-  int device = 0, nc = 0, nout = 0, T = 0;
-  DevBuf<float> x, ly;  // x'[T][nc][nout], ly'[T][nc]
-  DevBuf<double> d;     // the analyses' scratch, as on_rows has it
-  DevBuf<unsigned long long> h;
-  DevBuf<uint32_t> u;
-  DevStream st;
-  StoreSpan span() const { return StoreSpan{x.p, ly.p, nc, nout, (int64_t)T}; }
-  Bufs bufs() { return Bufs{&d, &h, &u}; }
-  size_t rows() const { return (size_t)T * nc; }
-  ~mcx_store()
-  {
-    if (st) (void)hipStreamSynchronize(st);  // (before the members go)
-  }
-};
-
+// (struct mcx_store: mcx_store.hpp)
 namespace {
 
 // the sweep over a span on stream st (the span's own stream: what wrote it is ordered before) -> a new store.  ms
@@ -230,6 +215,15 @@ int gather_to_host(hipStream_t st, const StoreSpan &s, uint32_t seed, uint64_t i
   if (rc != MCX_OK) (void)hipStreamSynchronize(st);  // (before the chunk buffers go)
   return rc;
 }
+
+}  // namespace
+
+int gather_span(hipStream_t st, const StoreSpan &s, bool draw, uint32_t seed, uint64_t i0, uint64_t n, float *rows, int64_t *index)
+{
+  return draw ? gather_to_host<true>(st, s, seed, i0, n, rows, index) : gather_to_host<false>(st, s, 0u, i0, n, rows, nullptr);
+}
+
+namespace {
 
 int draw_args(int64_t ndraw, const float *rows)
 {

@@ -1,0 +1,26 @@
+// mcx_store.hpp -- the derived store as the units that make one see it: mcx_derive.hip (a derive sweep writes one, and the
+// mcx_store_* entry points live there) and mcx_clip.hip (mcx_rowset_store copies kept rows into one).
+// Internal, as everything under csrc/ is.
+#pragma once
+#include "mcx_summary_kernels.hpp"
+
+struct mcx_store {
+  int device = 0, nc = 0, nout = 0, T = 0;
+  DevBuf<float> x, ly;  // x'[T][nc][nout], ly'[T][nc]
+  DevBuf<double> d;     // the analyses' scratch, as on_rows has it
+  DevBuf<unsigned long long> h;
+  DevBuf<uint32_t> u;
+  DevStream st;
+  StoreSpan span() const { return StoreSpan{x.p, ly.p, nc, nout, (int64_t)T}; }
+  Bufs bufs() { return Bufs{&d, &h, &u}; }
+  size_t rows() const { return (size_t)T * nc; }
+  ~mcx_store()
+  {
+    if (st) (void)hipStreamSynchronize(st);  // (before the members go)
+  }
+};
+
+// mcx_derive.hip's gather (k_gather_rows in chunks through one device buffer) for a span of any unit: n rows from row i0 on,
+// or with draw the rows of draws i0 .. i0 + n - 1 of seed among the span's T * nc rows and their indices (index may be NULL),
+// to the host in MCout layout
+MCXI int gather_span(hipStream_t st, const StoreSpan &s, bool draw, uint32_t seed, uint64_t i0, uint64_t n, float *rows, int64_t *index);

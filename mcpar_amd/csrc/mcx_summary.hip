@@ -316,7 +316,10 @@ int finish_column(const SummaryPass &p, int c, const float *os, int nprobs, mcx_
   std::vector<double> a(p.acov[c].size());
   for (size_t t = 0; t < a.size(); ++t) a[t] = p.acov[c][t] / ((double)v.n * (double)v.M);
   const double mean = p.cs[c] / (double)v.N, vm = p.cs[2 * v.ncol + c] / (double)(v.M - 1), va = p.ss[c] / (double)(v.N - 1);
-  return mcx_debug_summary_finish((int)v.n, (int)v.M, mean, va, vm, a.data(), (int)a.size(), os, v.N, p.probs, nprobs,
+  // (summary_thresholds on a range of fewer than four steps, for a clip, section 14: n < 2.  Without lags the finish reads
+  // its n nowhere -- mean, sd, the order statistics and the quantiles -- and every caller with lags has nsteps >= 4)
+  const int n = (int)std::max<int64_t>(v.n, 2);
+  return mcx_debug_summary_finish(n, (int)v.M, mean, va, vm, a.data(), (int)a.size(), os, v.N, p.probs, nprobs,
                                   std::isfinite(p.cs[c]) ? 0 : MCX_SUMMARY_NONFINITE, col, quantiles, need);
 }
 

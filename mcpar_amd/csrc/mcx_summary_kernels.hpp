@@ -4,7 +4,8 @@
 // store is a third way: a span handed to summary_span / rank_span / covariance_span below), pass 1 of every analysis (k_sum_moments: per-series fp64 sums), the
 // fixed-order reducer k_sum_rows that every cross-chain or cross-workgroup sum goes through, and the stage timer of the
 // mcx_debug_*_times entry points.  Internal to the three analysis units (each gets its own copy of the kernels).
-// mcx_derive.hip and mcx_density.hip (section 13, which has its own sweep and gets its statistics from summary_spread below)
+// mcx_derive.hip, mcx_density.hip (section 13, which has its own sweep and gets its statistics from summary_spread below) and
+// mcx_clip.hip (section 14: its thresholds are summary_thresholds')
 // include it for the view plumbing alone (on_store, on_rows with its k_sum_deinterleave, StageTimer); the
 // other kernels' copies in those units are never launched;
 // nothing here is part of the library's interface.
@@ -25,7 +26,8 @@ struct StoreSpan {
 };
 
 // mcx_summary.hip's passes for mcx_ranks.hip, each a subset of mcx_samples_summary's:
-// summary_thresholds: moments, order statistics, finish -- rhat, ess, ess_lag and mcse_mean of cols are not valid;
+// summary_thresholds: moments, order statistics, finish -- rhat, ess, ess_lag and mcse_mean of cols are not valid (any range
+// of N >= 1 values: mcx_clip.hip, section 14, asks for fewer than four steps);
 // summary_mixing: moments, autocovariance windows, finish -- min and max of cols are not valid
 MCXI int summary_thresholds(hipStream_t st, Bufs B, const StoreSpan &s, const double *probs, int nprobs, mcx_col_summary *cols,
                             double *quantiles);

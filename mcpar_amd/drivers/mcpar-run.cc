@@ -8,6 +8,7 @@
 //             [--derived-summary FILE] [--derived-rank-summary FILE] [--derived-covariance FILE]
 //             [--draws FILE --ndraw N [--draw-seed S]]
 //             [--density FILE] [--derived-density FILE] [--density-n N] [--density-clip QLO,QHI]
+//             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -35,6 +36,12 @@
 // lines `name x y` per column p0 .. LL.  --density-clip QLO,QHI: from the QLO to the QHI quantile of a column instead of min to
 // max (log L keeps its maximum).  --derived-density FILE: the same for the derived columns d0 .. LL.  Both under the
 // conditions of --summary.
+// --clip QLO,QHI (default 0.01,0.99) and --clip-ll-hi V (default 0): the reference's mcparam.clip.tails on the GPU
+// (mcx_rows_clip): the kept rows lie strictly between the QLO and QHI quantiles of every column, log L below V.
+// --clip-report FILE: a header `column lo hi nbelow nabove`, one line per column p0 .. LL, then `kept K of N`.  --clipped FILE:
+// the kept rows as the text of the sample output.  --clipped-density FILE [--clip-nc NC]: the file of --density for the kept
+// rows, as many whole steps of NC (default 1024) pseudo-chains as they fill (mcx_rowset_store); the report's last line
+// names the rows that leaves out.  All under the conditions of --summary.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -202,6 +209,88 @@ static int write_density(const char *path, const mcx_density_spec &spec, MCout &
   return print_density(path, x, y, np, spec.n, 'p');
 }
 
+// --clip-report / --clipped / --clipped-density: one clip of MCout's rows, the row set's files
+static int write_clip(const mcx_clip_spec &spec, const char *report_path, const char *rows_path, const char *dens_path, int clip_nc,
+                      const mcx_density_spec &dspec, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--clip-*: " << rows.size() << " rows stored, a clip needs nsamp * nc of them\n";
+    return 1;
+  }
+  const size_t ncol = (size_t)np + 1;
+  std::vector<mcx_col_clip> cols(ncol);
+  long long K = 0;
+  mcx_rowset *rs = 0;
+  if (mcx_rows_clip(rows.getpset(0), nsamp, nc, np, &spec, cols.data(), &K, &rs) != MCX_OK) {
+    std::cerr << "--clip: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  int rc = 0;
+  const long long dsteps = clip_nc > 0 ? K / clip_nc : 0, drows = dsteps * clip_nc;
+  if (rows_path) {
+    FILE *f = fopen(rows_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << rows_path << "\n";
+      rc = 1;
+    }
+    const long long chunk = 65536;
+    std::vector<float> part;
+    std::vector<char> text;
+    for (long long done = 0; rc == 0 && done < K; done += chunk) {
+      const long long k = K - done < chunk ? K - done : chunk;
+      size_t nb = 0;
+      part.resize((size_t)k * ncol);
+      if (mcx_rowset_copy(rs, done, k, part.data()) != MCX_OK || mcx_format_rows(part.data(), (size_t)k, (int)ncol, 0, 0, &nb) != MCX_OK) {
+        std::cerr << "--clipped: " << mcx_last_error() << "\n";
+        rc = 1;
+        break;
+      }
+      text.resize(nb);
+      if (mcx_format_rows(part.data(), (size_t)k, (int)ncol, text.data(), nb, &nb) != MCX_OK) {
+        std::cerr << "--clipped: " << mcx_last_error() << "\n";
+        rc = 1;
+      } else if (fwrite(text.data(), 1, nb, f) != nb) rc = 1;
+    }
+    if (f && fclose(f) != 0) rc = 1;
+  }
+  if (rc == 0 && dens_path) {
+    mcx_store *st = 0;
+    if (dsteps < 1 || dsteps > 2000000000LL) {
+      std::cerr << "--clipped-density: " << K << " kept rows do not fill one step of --clip-nc " << clip_nc << " pseudo-chains\n";
+      rc = 1;
+    } else if (mcx_rowset_store(rs, 0, (int)dsteps, clip_nc, &st) != MCX_OK) {
+      std::cerr << "--clipped-density: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else {
+      const size_t n = (size_t)(dspec.n > 0 ? dspec.n : 1);
+      std::vector<mcx_col_density> dc(ncol);
+      std::vector<double> x(ncol * n), y(ncol * n);
+      if (mcx_store_density(st, &dspec, dc.data(), x.data(), y.data()) != MCX_OK) {
+        std::cerr << "--clipped-density: " << mcx_last_error() << "\n";
+        rc = 1;
+      } else rc = print_density(dens_path, x, y, np, dspec.n, 'p');
+      mcx_store_destroy(st);
+    }
+  }
+  if (rc == 0 && report_path) {
+    FILE *f = fopen(report_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << report_path << "\n";
+      rc = 1;
+    } else {
+      fprintf(f, "column lo hi nbelow nabove\n");
+      for (int c = 0; c <= np; ++c)
+        fprintf(f, "%s %.17g %.17g %lld %lld\n", colname('p', c, np).c_str(), cols[c].lo, cols[c].hi, cols[c].nbelow, cols[c].nabove);
+      fprintf(f, "kept %lld of %lld", K, (long long)nsamp * nc);
+      if (dens_path) fprintf(f, ", density of %lld rows (%lld x %d), %lld left out", drows, dsteps, clip_nc, K - drows);
+      fprintf(f, "\n");
+      if (fclose(f) != 0) rc = 1;
+    }
+  }
+  mcx_rowset_destroy(rs);
+  return rc;
+}
+
 // --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
 static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
                          const mcx_density_spec &dspec, MCout &rows, int nsamp, int nc, int np)
@@ -356,7 +445,9 @@ int main(int argc, char *argv[])
   bool quiet = false, iter = false, binary = false, stream_text = false;
   std::string out_file, func_source, summary_file, rank_summary_file, covariance_file, proposal_file, incov_file;
   std::string derive_source_file, derive_linear_file, derived_summary_file, derived_rank_summary_file, derived_covariance_file, draws_file;
-  std::string density_file, derived_density_file;
+  std::string density_file, derived_density_file, clip_report_file, clipped_file, clipped_density_file;
+  mcx_clip_spec clip_spec = {0.01, 0.99, 0.0, 0, 0};
+  int clip_nc = 1024;
   mcx_density_spec density_spec = {512, 1.0, 0.0, 1.0, 0, 0, 0};
   std::vector<float> user_par, derive_par;
   int derive_nout = 0;
@@ -407,6 +498,17 @@ int main(int argc, char *argv[])
         return 2;
       }
     }
+    else if (a == "--clip") {
+      if (sscanf(val(), "%lf,%lf", &clip_spec.qlo, &clip_spec.qhi) != 2) {
+        std::cerr << "--clip takes QLO,QHI\n";
+        return 2;
+      }
+    }
+    else if (a == "--clip-ll-hi") clip_spec.ll_hi = atof(val());
+    else if (a == "--clip-report") clip_report_file = val();
+    else if (a == "--clipped") clipped_file = val();
+    else if (a == "--clipped-density") clipped_density_file = val();
+    else if (a == "--clip-nc") clip_nc = atoi(val());
     else if (a == "--draws") draws_file = val();
     else if (a == "--ndraw") ndraw = atoll(val());
     else if (a == "--draw-seed") draw_seed = (unsigned)strtoul(val(), 0, 10);
@@ -440,6 +542,14 @@ int main(int argc, char *argv[])
   if (!density_file.empty() && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--density needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  const bool want_clip = !clip_report_file.empty() || !clipped_file.empty() || !clipped_density_file.empty();
+  if (want_clip && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--clip-report, --clipped and --clipped-density need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -553,6 +663,13 @@ int main(int argc, char *argv[])
     return 2;
   }
   if (!density_file.empty() && write_density(density_file.c_str(), density_spec, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_clip && write_clip(clip_spec, clip_report_file.empty() ? 0 : clip_report_file.c_str(),
+                              clipped_file.empty() ? 0 : clipped_file.c_str(),
+                              clipped_density_file.empty() ? 0 : clipped_density_file.c_str(), clip_nc, density_spec, rslts, nsamp, nc,
+                              np) != 0) {
     MPI_Finalize();
     return 2;
   }

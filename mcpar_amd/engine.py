@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, Counters, DensitySpecC, Derive, PlanItem, Profile,
-                   VLFunc, check, load)
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ClipSpecC, Counters, DensitySpecC, Derive, PlanItem,
+                   Profile, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -46,6 +46,10 @@ DENSITY_DTYPE = np.dtype([("bw", np.float64), ("from", np.float64), ("to", np.fl
                           ("mean", np.float64), ("sd", np.float64), ("nvalues", np.int64), ("nbinned", np.int64),
                           ("flags", np.int32)], align=True)
 assert DENSITY_DTYPE.itemsize == 80
+# include/mcx.h mcx_col_clip
+CLIP_DTYPE = np.dtype([("lo", np.float64), ("hi", np.float64), ("nbelow", np.int64), ("nabove", np.int64), ("flags", np.int32)],
+                      align=True)
+assert CLIP_DTYPE.itemsize == 40
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
@@ -468,6 +472,12 @@ class DerivedStore:
         check(load().mcx_store_draw(self.h, seed, ndraw, _fp(rows), index.ctypes.data_as(C.POINTER(C.c_int64))))
         return rows, index
 
+    def clip(self, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, count_only=False):
+        """Engine.clip's RowSet for the rows of this store (the derived columns, then log L)"""
+        t, nc, ncol = self.shape
+        spec = ClipSpec(qlo, qhi, ll_hi, lo, hi).fits(ncol)
+        return _clip_call(lambda *a: load().mcx_store_clip(self.h, *a), spec, ncol, t * nc, count_only)
+
 
 def derive_rows(rows, nsteps, nc, spec):
     """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
@@ -475,6 +485,106 @@ def derive_rows(rows, nsteps, nc, spec):
     h = C.c_void_p()
     check(load().mcx_rows_derive(_fp(rows), nsteps, nc, rows.shape[1] - 1, None if spec is None else C.byref(spec.c), C.byref(h)))
     return DerivedStore(h)
+
+
+# ---- tail-clipped rows (include/mcx.h) ----
+class ClipSpec:
+    """an mcx_clip_spec and the arrays it points to: the probabilities (qlo, qhi) of the default thresholds, ll_hi the upper
+    threshold of log L (NaN: its qhi quantile; inf: none), lo / hi = None or [ncol] with NaN for a column's default"""
+
+    def __init__(self, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None):
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1))  # noqa: E731
+        self.lo, self.hi = arr(lo), arr(hi)
+        self.c = ClipSpecC(float(qlo), float(qhi), float(ll_hi), None if self.lo is None else _dp(self.lo),
+                           None if self.hi is None else _dp(self.hi))
+
+    def fits(self, ncol):
+        for a in (self.lo, self.hi):
+            if a is not None and a.size != ncol:
+                raise ValueError("lo and hi take one entry per column (%d), NaN for a column's default" % ncol)
+        return self
+
+
+class RowSet:
+    """an mcx_rowset: the rows a clip kept, in source order, with their source row indices.  It owns its device memory.
+    report: CLIP_DTYPE [ncol] (lo, hi, nbelow, nabove, flags); nrows = K, nsource = N.  After count_only there is no handle:
+    report, nrows, nsource and ncol are all it has."""
+
+    def __init__(self, handle, report, nrows, nsource):
+        self.h, self.report, self.nrows, self.nsource, self.ncol = handle, report, int(nrows), int(nsource), len(report)
+        self.dropped = 0  # on the DerivedStore of store(): the kept rows from first_row on that its shape left out
+
+    def close(self):
+        if self.h:
+            load().mcx_rowset_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _span(self, first, n):
+        return max(self.nrows - first, 0) if n is None else n
+
+    def rows(self, first=0, n=None):
+        """MCout rows [n, ncol] of kept rows [first, first + n) -- n None: to the end"""
+        n = self._span(first, n)
+        out = np.empty((max(n, 0), self.ncol), np.float32)
+        check(load().mcx_rowset_copy(self.h, first, n, _fp(out)))
+        return out
+
+    def index(self, first=0, n=None):
+        """the source row (step * nc + chain of the clipped range) of kept rows [first, first + n), int64, ascending"""
+        n = self._span(first, n)
+        out = np.empty(max(n, 0), np.int64)
+        check(load().mcx_rowset_index(self.h, first, n, out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
+    def draw(self, ndraw, seed):
+        """ndraw kept rows with replacement: (rows [ndraw, ncol], index [ndraw] int64 into the row set), the index
+        debug_draw_indices(seed, nrows, 0, ndraw) gives"""
+        rows, index = np.empty((max(ndraw, 0), self.ncol), np.float32), np.empty(max(ndraw, 0), np.int64)
+        check(load().mcx_rowset_draw(self.h, seed, ndraw, _fp(rows), index.ctypes.data_as(C.POINTER(C.c_int64))))
+        return rows, index
+
+    def store(self, nc=1024, first_row=0, nsteps=None):
+        """mcx_rowset_store: kept rows [first_row, first_row + nsteps * nc) as a DerivedStore of nsteps steps of nc
+        pseudo-chains, for summary / covariance / density / draw of exactly these rows (its R-hat and ESS mean nothing).
+        nsteps None: (nrows - first_row) // nc; the store's .dropped = the kept rows behind first_row it leaves out"""
+        if nsteps is None:
+            nsteps = (self.nrows - first_row) // nc if nc > 0 else 0
+        h = C.c_void_p()
+        check(load().mcx_rowset_store(self.h, first_row, nsteps, nc, C.byref(h)))
+        st = DerivedStore(h)
+        st.dropped = self.dropped = self.nrows - first_row - nsteps * nc
+        return st
+
+
+def _clip_call(fn, spec, ncol, nsource, count_only):
+    """fn(spec, cols, nkept, out) of one of the three clip entry points over nsource rows -> RowSet"""
+    cols, k, h = np.zeros(ncol, CLIP_DTYPE), C.c_longlong(0), C.c_void_p()
+    check(fn(C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), C.byref(k), None if count_only else C.byref(h)))
+    return RowSet(h, cols, k.value, nsource)
+
+
+def clip_rows(rows, nsteps, nc, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, count_only=False):
+    """mcx_rows_clip: Engine.clip's RowSet for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    spec = ClipSpec(qlo, qhi, ll_hi, lo, hi).fits(ncol)
+    return _clip_call(lambda *a: load().mcx_rows_clip(_fp(rows), nsteps, nc, ncol - 1, *a), spec, ncol, nsteps * nc, count_only)
+
+
+def debug_clip_thresholds(q, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, spec=None):
+    """mcx_debug_clip_thresholds (host only): (lo [ncol], hi [ncol]) from q [ncol, 2], the columns' (qlo, qhi) quantiles"""
+    q = np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1, 2))
+    ncol = q.shape[0]
+    spec = spec or ClipSpec(qlo, qhi, ll_hi, lo, hi).fits(ncol)
+    tl, th = np.zeros(max(ncol, 1)), np.zeros(max(ncol, 1))
+    check(load().mcx_debug_clip_thresholds(ncol, _dp(q), C.byref(spec.c), _dp(tl), _dp(th)))
+    return tl[:ncol], th[:ncol]
 
 
 def debug_live_resources():
@@ -931,6 +1041,27 @@ class Engine:
         spec = DensitySpec(n, adjust, clip)
         ms = np.zeros(4)
         self._on_store(load().mcx_debug_density_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
+        return ms
+
+    def clip(self, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, first_step=0, nsteps=None, count_only=False):
+        """mcx_samples_clip, the reference's mcparam.clip.tails: the RowSet of the rows of kept steps [first_step, first_step
+        + nsteps) that lie strictly between the thresholds of every column (the parameters, then log L) -- by default a
+        column's (qlo, qhi) quantiles, summary()'s numbers, and ll_hi as the upper threshold of log L; lo / hi [np + 1]
+        replace them where not NaN.  count_only: the report and the count, no rows"""
+        spec = ClipSpec(qlo, qhi, ll_hi, lo, hi).fits(self.np + 1)
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        return _clip_call(lambda *a: load().mcx_samples_clip(self.h, first_step, nsteps, *a), spec, self.np + 1,
+                          max(nsteps, 0) * self.nc, count_only)
+
+    def clip_times(self, qlo=0.01, qhi=0.99, ll_hi=0.0, first_step=0, nsteps=None):
+        """mcx_debug_clip_times: ms of (the thresholds, the mark sweep, the scan, the scatter sweep, the whole call) of one
+        clip() call"""
+        spec = ClipSpec(qlo, qhi, ll_hi)
+        ms = np.zeros(5)
+        self._on_store(load().mcx_debug_clip_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
         return ms
 
     def derive(self, spec, first_step=0, nsteps=None):
