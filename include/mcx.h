@@ -610,6 +610,28 @@ int mcx_debug_clip_thresholds(int ncol, const double *q, const mcx_clip_spec *sp
  * ms[1] the mark sweep, ms[2] the scan, ms[3] the scatter sweep (HIP events), ms[4] the whole call (wall clock) */
 int mcx_debug_clip_times(mcx_engine *e, int first_step, int nsteps, const mcx_clip_spec *spec, double *ms);
 
+/* host only, no device: the launch geometry of the store analyses of sections 11, 12 and 14 for a store of nsteps steps of
+ * nc chains of np parameters and a derive to nout outputs (nout = 0: none; the derive fields are then the clip's), N =
+ * nsteps * nc rows.  Every field comes from the function or constant the launch code itself uses, so a test can assert
+ * that its shape lies on the side of a size switch it is there for.  MCX_ERR_INVALID for np outside 1..256, nout outside
+ * 0..256, nsteps or nc < 1, or g NULL. */
+typedef struct mcx_store_geometry {
+  long long nrows;              /* N */
+  long long derive_rows;        /* rows per workgroup of the derive sweep: 256, 128, 64, 32 or 16 */
+  long long derive_lds_bytes;   /* of its two tiles, at most 40 960 */
+  long long derive_workgroups;
+  long long clip_rows;          /* rows per workgroup of the clip's mark and scatter sweeps: 256 down to 32 */
+  long long clip_mask_words;    /* 64-bit keep-mask words per workgroup, ceil(clip_rows / 64) */
+  long long clip_lds_bytes;
+  long long clip_workgroups;
+  long long clip_scan_blocks;   /* blocks of 256 workgroup counts; the top level of the scan carries over steps of 256 blocks */
+  long long rank_tiles;         /* sort tiles of 8192 keys per column; the scan of a (column, digit) row carries over steps of 256 */
+  long long rank_step_chunk;    /* steps per workgroup of the key and transform sweeps */
+  long long rank_grid_y;        /* their grid.y, ceil(nsteps / rank_step_chunk) */
+  long long gather_chunk_rows;  /* rows of np + 1 floats that one chunk of a copy of N rows to the host holds */
+} mcx_store_geometry;
+int mcx_debug_store_geometry(int np, int nout, int nsteps, int nc, mcx_store_geometry *g);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -11,9 +11,9 @@ from .engine import (Engine, VL_DEVICE, VL_SOURCE, VL_DUALGAUSS, VL_GAUSSIAN, VL
                      make_vlfunc, vlfunc_eval)
 from .engine import (DerivedStore, debug_derive_compile, debug_draw_indices, derive_linear, derive_rows,  # noqa: F401
                      derive_source, user_source_available)
-from .engine import RowSet, clip_rows, debug_clip_thresholds  # noqa: F401
+from .engine import RowSet, clip_rows, debug_clip_thresholds, debug_store_geometry  # noqa: F401
 
 __all__ = ["Engine", "McxError", "load", "lib_path", "make_vlfunc", "vlfunc_eval", "device_info", "RowSet", "clip_rows",
-           "debug_clip_thresholds",
+           "debug_clip_thresholds", "debug_store_geometry",
            "debug_numerics", "debug_normals", "DerivedStore", "derive_linear", "derive_source", "derive_rows",
            "debug_draw_indices", "debug_derive_compile", "user_source_available"]

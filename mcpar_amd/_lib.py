@@ -41,6 +41,13 @@ class ClipSpecC(C.Structure):
                 ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double))]
 
 
+class StoreGeometry(C.Structure):
+    """include/mcx.h mcx_store_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("nrows", "derive_rows", "derive_lds_bytes", "derive_workgroups", "clip_rows",
+                                            "clip_mask_words", "clip_lds_bytes", "clip_workgroups", "clip_scan_blocks",
+                                            "rank_tiles", "rank_step_chunk", "rank_grid_y", "gather_chunk_rows")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -160,6 +167,7 @@ def load():
         "mcx_rowset_store": [vp, C.c_longlong, C.c_int, C.c_int, C.POINTER(vp)],
         "mcx_debug_clip_thresholds": [C.c_int, dp, C.POINTER(ClipSpecC), dp, dp],
         "mcx_debug_clip_times": [vp, C.c_int, C.c_int, C.POINTER(ClipSpecC), dp],
+        "mcx_debug_store_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(StoreGeometry)],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

@@ -230,8 +230,9 @@ int clip_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_clip_spec *s
   const uint64_t N = (uint64_t)s.T * (uint64_t)s.nc;
   if (np < 1 || np > DERIVE_MAXW) return fail(MCX_ERR_INVALID, "np = %d: a clip takes rows of 1 to %d parameters", np, DERIVE_MAXW);
   ClipArgs a{};
-  a.x = s.x; a.ly = s.ly; a.N = N; a.np = np; a.R = derive_rows(np, 0); a.wpw = (a.R + 63) / 64;
-  const uint64_t nwg = (N + a.R - 1) / a.R, nb = (nwg + CLIP_FAN - 1) / CLIP_FAN;
+  const ClipGeometry geo = clip_geometry(np, N);
+  a.x = s.x; a.ly = s.ly; a.N = N; a.np = np; a.R = geo.R; a.wpw = geo.wpw;
+  const uint64_t nwg = geo.nwg, nb = geo.nb;
   if (nwg > 0x7fffffffull)
     return fail(MCX_ERR_UNSUPPORTED, "clip: %llu rows in tiles of %d are more workgroups than a grid holds", (unsigned long long)N, a.R);
 
@@ -254,7 +255,7 @@ int clip_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_clip_spec *s
   MCXCHK(B.u->alloc(nwg));
   unsigned long long *H = B.h->p;
   a.thr = B.d->p; a.counts = H; a.mask = H + o_mask; a.cnt = B.u->p; a.offs = H + o_offs;
-  const size_t lds = (size_t)derive_lds_floats(np, 0, a.R) * sizeof(float);
+  const size_t lds = geo.lds_bytes;
   std::vector<unsigned long long> counts((size_t)ncol * 2);
   unsigned long long total = 0;
   auto run = [&]() -> int {
@@ -337,6 +338,17 @@ int rowset_range(const mcx_rowset *r, long long first_row, long long nrows)
 }
 
 }  // namespace
+
+ClipGeometry clip_geometry(int np, uint64_t N)
+{
+  ClipGeometry g;
+  g.R = derive_rows(np, 0);
+  g.wpw = (g.R + 63) / 64;
+  g.lds_bytes = (size_t)derive_lds_floats(np, 0, g.R) * sizeof(float);
+  g.nwg = sweep_tiles(N, g.R);
+  g.nb = (g.nwg + CLIP_FAN - 1) / CLIP_FAN;
+  return g;
+}
 
 extern "C" int mcx_samples_clip(mcx_engine *e, int first_step, int nsteps, const mcx_clip_spec *spec, mcx_col_clip *cols,
                                 long long *nkept, mcx_rowset **out)

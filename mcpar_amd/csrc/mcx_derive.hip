@@ -146,7 +146,7 @@ int derive_span(hipStream_t st, const StoreSpan &s, const mcx_derive *f, mcx_sto
   o->nc = s.nc; o->nout = f->nout; o->T = (int)s.T;
   DeriveArgs a;
   a.x = s.x; a.ly = s.ly; a.N = N; a.np = s.np; a.nout = f->nout; a.R = derive_rows(s.np, f->nout);
-  const uint64_t nwg = (N + a.R - 1) / a.R;
+  const uint64_t nwg = sweep_tiles(N, a.R);
   if (nwg > 0x7fffffffull) return fail(MCX_ERR_UNSUPPORTED, "derive: %llu rows in tiles of %d are more workgroups than a grid holds", (unsigned long long)N, a.R);
   hipFunction_t ufn = nullptr;
   if (f->kind == MCX_DERIVE_SOURCE) MCXCHK(derive_user_kernel(f->source, s.np, f->nout, &ufn));
@@ -192,9 +192,7 @@ int gather_to_host(hipStream_t st, const StoreSpan &s, uint32_t seed, uint64_t i
 {
   if (n == 0) return MCX_OK;
   const uint64_t N = (uint64_t)s.T * (uint64_t)s.nc, ncol = (uint64_t)s.np + 1;
-  uint64_t chunk = std::max<uint64_t>(DERIVE_BLOCK, std::min<uint64_t>(n, ((uint64_t)64 << 20) / (ncol * sizeof(float))));
-  // (a test knob, as MCX_RANK_GROUP_COLS is: rows per chunk, so that a small store goes through several chunks)
-  if (const char *cap = std::getenv("MCX_GATHER_CHUNK_ROWS")) chunk = (uint64_t)std::max(1LL, std::atoll(cap));
+  const uint64_t chunk = gather_chunk_rows(n, ncol);
   DevBuf<float> dr;
   DevBuf<long long> di;
   auto run = [&]() -> int {
@@ -217,6 +215,13 @@ int gather_to_host(hipStream_t st, const StoreSpan &s, uint32_t seed, uint64_t i
 }
 
 }  // namespace
+
+uint64_t gather_chunk_rows(uint64_t n, uint64_t ncol)
+{
+  // (a test knob, as MCX_RANK_GROUP_COLS is: rows per chunk, so that a small store goes through several chunks)
+  if (const char *cap = std::getenv("MCX_GATHER_CHUNK_ROWS")) return (uint64_t)std::max(1LL, std::atoll(cap));
+  return std::max<uint64_t>(DERIVE_BLOCK, std::min<uint64_t>(n, ((uint64_t)64 << 20) / (ncol * sizeof(float))));
+}
 
 int gather_span(hipStream_t st, const StoreSpan &s, bool draw, uint32_t seed, uint64_t i0, uint64_t n, float *rows, int64_t *index)
 {
@@ -366,6 +371,32 @@ extern "C" int mcx_debug_draw_indices(uint32_t seed, uint64_t N, uint64_t first,
   if (N < 1 || n < 0 || (n > 0 && !index)) return fail(MCX_ERR_INVALID, "N = %llu, n = %d: N >= 1, n >= 0, index not NULL", (unsigned long long)N, n);
   if (N > (uint64_t)1 << 63) return fail(MCX_ERR_INVALID, "N = %llu: at most 2^63 rows (an index is an int64_t)", (unsigned long long)N);
   for (int k = 0; k < n; ++k) index[k] = (int64_t)draw_index(seed, first + (uint64_t)k, N);
+  return MCX_OK;
+}
+
+// host only: the functions the launch code calls, on a shape
+extern "C" int mcx_debug_store_geometry(int np, int nout, int nsteps, int nc, mcx_store_geometry *g)
+{
+  if (!g) return fail(MCX_ERR_INVALID, "g is NULL");
+  if (np < 1 || np > DERIVE_MAXW) return fail(MCX_ERR_INVALID, "np = %d: 1 to %d parameters", np, DERIVE_MAXW);
+  if (nout < 0 || nout > DERIVE_MAXW) return fail(MCX_ERR_INVALID, "nout = %d: 0 (no derive) to %d outputs", nout, DERIVE_MAXW);
+  if (nsteps < 1 || nc < 1) return fail(MCX_ERR_INVALID, "nsteps = %d, nc = %d: at least one step of one chain", nsteps, nc);
+  const uint64_t N = (uint64_t)nsteps * (uint64_t)nc;
+  g->nrows = (long long)N;
+  g->derive_rows = derive_rows(np, nout);
+  g->derive_lds_bytes = (long long)derive_lds_floats(np, nout, (int)g->derive_rows) * (long long)sizeof(float);
+  g->derive_workgroups = (long long)sweep_tiles(N, (int)g->derive_rows);
+  const ClipGeometry c = clip_geometry(np, N);
+  g->clip_rows = c.R;
+  g->clip_mask_words = c.wpw;
+  g->clip_lds_bytes = (long long)c.lds_bytes;
+  g->clip_workgroups = (long long)c.nwg;
+  g->clip_scan_blocks = (long long)c.nb;
+  const RankGeometry r = rank_geometry(nsteps, (int64_t)N);
+  g->rank_tiles = (long long)r.nblk;
+  g->rank_step_chunk = (long long)r.rchunk;
+  g->rank_grid_y = (long long)r.chunks;
+  g->gather_chunk_rows = (long long)gather_chunk_rows(N, (uint64_t)np + 1);
   return MCX_OK;
 }
 

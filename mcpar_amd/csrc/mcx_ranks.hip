@@ -266,10 +266,10 @@ struct RankPass {
   std::vector<double> thr;           // thresholds: [3][ncol] q05, median, q95 (S.thr on the device)
 
   RankPass(hipStream_t st_, Bufs B_, const StoreView &v_, double *ms, bool want_ranks_)
-      : st(st_), B(B_), v(v_), tm{st_, ms, RT_N, {}}, want_ranks(want_ranks_), rchunk(std::max(RCHUNK, (v_.T + 32767) / 32768)),
-        chunks((unsigned)((v_.T + rchunk - 1) / rchunk)), nblk((uint32_t)((v_.N + RTILE - 1) / RTILE)), c0s(v_.ncol),
-        thr(3 * (size_t)v_.ncol)
+      : st(st_), B(B_), v(v_), tm{st_, ms, RT_N, {}}, want_ranks(want_ranks_), c0s(v_.ncol), thr(3 * (size_t)v_.ncol)
   {
+    const RankGeometry g = rank_geometry(v_.T, v_.N);
+    rchunk = g.rchunk; chunks = g.chunks; nblk = g.nblk;
   }
 };
 
@@ -470,6 +470,15 @@ int rank_args(int nsteps, const void *cols)
 }
 
 }  // namespace
+
+RankGeometry rank_geometry(int64_t T, int64_t N)
+{
+  RankGeometry g;
+  g.rchunk = std::max(RCHUNK, (T + 32767) / 32768);
+  g.chunks = (unsigned)((T + g.rchunk - 1) / g.rchunk);
+  g.nblk = (uint32_t)((N + RTILE - 1) / RTILE);
+  return g;
+}
 
 int rank_span(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_rank_summary *cols)
 {

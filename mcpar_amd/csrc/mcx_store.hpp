@@ -24,3 +24,16 @@ struct mcx_store {
 // or with draw the rows of draws i0 .. i0 + n - 1 of seed among the span's T * nc rows and their indices (index may be NULL),
 // to the host in MCout layout
 MCXI int gather_span(hipStream_t st, const StoreSpan &s, bool draw, uint32_t seed, uint64_t i0, uint64_t n, float *rows, int64_t *index);
+// the rows of one chunk of that gather when n rows of ncol floats are asked for (mcx_derive.hip)
+MCXI uint64_t gather_chunk_rows(uint64_t n, uint64_t ncol);
+
+// Launch geometry, one function per sweep so that mcx_debug_store_geometry (mcx_derive.hip) reports what is launched.
+// Workgroups of a sweep that gives each R consecutive rows of N (the derive and clip sweeps):
+inline uint64_t sweep_tiles(uint64_t N, int R) { return (N + (uint64_t)R - 1) / (uint64_t)R; }
+// the clip of N rows of np parameters (mcx_clip.hip)
+struct ClipGeometry {
+  int R, wpw;        // rows per workgroup, derive_rows(np, 0); mask words per workgroup
+  size_t lds_bytes;  // of a workgroup's tile
+  uint64_t nwg, nb;  // workgroups of the mark and scatter sweeps; scan blocks
+};
+MCXI ClipGeometry clip_geometry(int np, uint64_t N);

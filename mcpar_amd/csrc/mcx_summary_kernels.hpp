@@ -47,6 +47,15 @@ MCXI int covariance_span(hipStream_t st, Bufs B, const StoreSpan &s, double *mea
 MCXI int density_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_density_spec *spec, mcx_col_density *cols, double *x,
                       double *y, double *ms = nullptr);  // mcx_density.hip; ms: mcx_debug_density_times' four stages
 
+// The launch geometry of a rank pass over T steps and N = T * nc values per column (mcx_ranks.hip): what RankPass launches
+// with and what mcx_debug_store_geometry reports
+struct RankGeometry {
+  int64_t rchunk;   // steps per workgroup of the key and transform sweeps
+  unsigned chunks;  // their grid.y
+  uint32_t nblk;    // sort tiles per column
+};
+MCXI RankGeometry rank_geometry(int64_t T, int64_t N);
+
 namespace {
 
 constexpr int SB = 256;     // threads per workgroup of every summary kernel

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ClipSpecC, Counters, DensitySpecC, Derive, PlanItem,
-                   Profile, VLFunc, check, load)
+                   Profile, StoreGeometry, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -585,6 +585,14 @@ def debug_clip_thresholds(q, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, sp
     tl, th = np.zeros(max(ncol, 1)), np.zeros(max(ncol, 1))
     check(load().mcx_debug_clip_thresholds(ncol, _dp(q), C.byref(spec.c), _dp(tl), _dp(th)))
     return tl[:ncol], th[:ncol]
+
+
+def debug_store_geometry(np_, nout, nsteps, nc):
+    """mcx_debug_store_geometry (host only): the launch geometry of the derive, clip, rank and gather code for a store of
+    nsteps steps of nc chains of np_ parameters and nout derived outputs (0: none), as a dict of include/mcx.h's fields"""
+    g = StoreGeometry()
+    check(load().mcx_debug_store_geometry(np_, nout, nsteps, nc, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in StoreGeometry._fields_}
 
 
 def debug_live_resources():

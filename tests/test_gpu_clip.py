@@ -148,6 +148,204 @@ def test_all_kept_and_none_kept():
     none.close()
 
 
+# ---- the tile heights below 256 rows ----------------------------------------------------------------------------------------
+# np -> R = derive_rows(np, 0) rows per workgroup.  39 | 40: the two sides of the LDS budget's edge (39 uses all 40 960 bytes)
+TILE_NP = {39: 256, 40: 128, 100: 64, 256: 32}
+
+
+def tile_geometry(np_, N, R):
+    """the geometry a reduced-tile case is there for, asserted before any result"""
+    from mcpar_amd import engine as E
+    g = E.debug_store_geometry(np_, 0, N, 1)
+    assert g["clip_rows"] == R and g["clip_mask_words"] == (R + 63) // 64 and g["clip_workgroups"] == 3 - (N == 2 * R), g
+    return g
+
+
+@pytest.mark.parametrize("full", [False, True])  # N = 2 R + 5: a third, ragged workgroup; N = 2 R: two full tiles exactly
+@pytest.mark.parametrize("np_", sorted(TILE_NP))
+def test_tile_heights_marker_patterns(np_, full):
+    """k_clip_mark `if (wave < a.wpw)` and `a.mask[blockIdx.x * a.wpw + wave]`, k_clip_scatter `for (w < wave) pos +=
+    popc(mw[w])` and `mw = a.mask + blockIdx.x * a.wpw`: wpw = 2 with wavefronts 2 and 3 idle (R = 128), wpw = 1 with a
+    full wavefront (R = 64) and with half of one (R = 32) are run by no other test with more than one workgroup, and so
+    never with offs > 0 or a second row of mask words.  The marker column makes every kept row's place visible: a wpw off
+    by one or a workgroup reading another's mask words moves or drops rows of the patterns below, whose runs of 63, 64
+    and 65 rows put a run's edge at every lane of a mask word and across the tiles of every height."""
+    from mcpar_amd import engine as E
+    R_ = TILE_NP[np_]
+    N = 2 * R_ + (0 if full else 5)
+    g = tile_geometry(np_, N, R_)
+    assert (g["clip_lds_bytes"] == 40960) == (np_ == 39)
+    for name, keep in patterns(N):
+        rows, lo, hi = marker(N, np_, 1, keep)
+        rs = E.clip_rows(rows, N, 1, lo=lo, hi=hi, ll_hi=INF)
+        assert not rs.report["flags"].any(), name  # no quantile pass ran
+        assert rs.nrows == int(keep.sum()), name
+        idx, got = rs.index(), rs.rows()
+        assert np.array_equal(idx, np.flatnonzero(keep)), name
+        assert np.array_equal(got[:, 0], idx.astype(np.float32)), name
+        assert got.tobytes() == rows[keep].tobytes(), name
+        nb, na = rs.report["nbelow"], rs.report["nabove"]
+        assert nb[1] == N - keep.sum() and nb.sum() == nb[1] and na.sum() == 0, name
+        rs.close()
+
+
+def correlated(N, np_, seed):
+    """synth() with the parameters sharing one factor (plus a tenth of their own noise): the tails of up to 256 columns are
+    then mostly the same rows, and a joint clip leaves rows to compact"""
+    rng = np.random.default_rng(seed)
+    rows = synth(N, np_, 1, seed)
+    scale, shift = 1.0 + 0.25 * (np.arange(np_) % 7), np.arange(np_) % 5 - 2.0
+    rows[:, :-1] = (rng.normal(0.0, 1.0, (N, 1)) + 0.1 * rng.normal(0.0, 1.0, (N, np_))) * scale + shift
+    return rows
+
+
+@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("np_", sorted(TILE_NP))
+def test_tile_heights_default_quantiles(np_, full):
+    """the same heights with the thresholds of a quantile pass and every column clipping: `atomicAdd(&tails[2 * c], ...)`
+    of k_clip_mark counts per column over wpw wavefronts only, and k_clip_scatter's two store paths (16 bytes where a
+    workgroup's piece of x' starts on a 16-byte boundary, which depends on offs * np) both run at every height.  Kept rows,
+    indices and the per-column counts against the float64 restatement, exact."""
+    from mcpar_amd import engine as E
+    R_ = TILE_NP[np_]
+    N = 2 * R_ + (0 if full else 5)
+    tile_geometry(np_, N, R_)
+    rows = correlated(N, np_, seed=300 + np_)
+    rs = E.clip_rows(rows, N, 1, 0.05, 0.95)
+    assert not rs.report["flags"].any()
+    ref = R.check(rs, rows)
+    own = R.clip(rows, 0.05, 0.95)
+    np.testing.assert_allclose(rs.report["lo"], own["lo"], rtol=1e-12)
+    np.testing.assert_allclose(rs.report["hi"][:-1], own["hi"][:-1], rtol=1e-12)
+    assert np.array_equal(own["keep"], ref["keep"])
+    idx = rs.index()
+    assert 0 < rs.nrows < N and idx[0] < R_ <= idx[-1], (rs.nrows, idx[:1], idx[-1:])  # a workgroup behind the first has offs > 0
+    assert (rs.report["nbelow"] >= 1).all() and (rs.report["nabove"][:-1] >= 1).all()
+    assert N - rs.nrows > (rs.report["nbelow"] + rs.report["nabove"]).max()  # the columns' tails are not all the same rows
+    same_report(rs, E.clip_rows(rows, N, 1, 0.05, 0.95, count_only=True))
+    rs.close()
+
+
+@pytest.mark.parametrize("np_, nc, R_", [(41, 7, 128), (101, 3, 64), (255, 3, 32)])
+def test_tile_heights_from_an_unaligned_store(np_, nc, R_):
+    """clip_stage's `((unsigned long)gx & 15ul) == 0`: steps [1, T) of an engine's store with nc * np odd start off a
+    16-byte boundary, so derive_tile_copy<true> takes its 4-byte path at this tile height; the same steps given as host rows
+    are uploaded to a fresh allocation and take the 16-byte path.  Both must give the same row set, bit for bit."""
+    from mcpar_amd import engine as E
+    T = 2 + (2 * R_ + nc) // nc
+    ns = T - 1
+    g = E.debug_store_geometry(np_, 0, ns, nc)
+    assert g["clip_rows"] == R_ and g["clip_workgroups"] >= 3 and (nc * np_ * 4) % 16 != 0, g
+    eg = run(np_, nc, 30, T)
+    rows = eg.samples_range(1, ns)
+    # the quantiles of the first and the last parameter (the two ends of a row of the LDS tile) and of log L; a Metropolis
+    # store of up to 255 independent parameters has some column's extreme in nearly every row, so the others do not clip
+    lo, hi = np.full(np_ + 1, -INF), np.full(np_ + 1, INF)
+    lo[[0, np_ - 1, np_]] = hi[[0, np_ - 1]] = NAN
+    a = eg.clip(0.1, 0.9, INF, lo, hi, first_step=1, nsteps=ns)
+    b = E.clip_rows(rows, ns, nc, 0.1, 0.9, INF, lo, hi)
+    q = eg.summary((0.1, 0.9), first_step=1, nsteps=ns)["quantiles"]
+    assert a.report["lo"][0] == q[0, 0] and a.report["hi"][np_ - 1] == q[np_ - 1, 1] and a.report["lo"][np_] == q[np_, 0]
+    R.check(a, rows)
+    same_rowset(a, b)
+    assert 0 < a.nrows < a.nsource and a.index()[-1] >= R_
+    for r in (a, b):
+        r.close()
+    eg.close()
+
+
+# ---- the scan past two carries, the kept rows in their natural 64 MiB chunks ------------------------------------------------
+BIG_N = 2 * (1 << 24) + 256 * 300 + 77  # 33 631 309 rows of np = 1: 131 373 workgroups, 514 scan blocks
+BIG_LO, BIG_HI = (-1.0, -8.0), (1.5, -0.0009765625)  # float32-representable: the float32 comparison is the float64 rule
+BIG_PERIOD = 1000003  # rows of the random block the store repeats; prime: no two workgroups hold the same rows
+HOLE = slice(1 << 24, (1 << 24) + (1 << 20))
+
+
+@pytest.fixture(scope="module", params=[False, True], ids=["dense", "hole"])
+def big(request):
+    """[BIG_N, 2] float32 -- a normal parameter and log L = -z^2 / 2 of another normal, a block of BIG_PERIOD rows repeated --
+    and its clip at (BIG_LO, BIG_HI) by float32 comparisons on the host, made once per kind and left unchanged.
+    hole: no row of [2^24, 2^24 + 2^20) is kept (the parameter is 2 there, above its upper bound)."""
+    rng = np.random.default_rng(514)
+    block = rng.standard_normal((BIG_PERIOD, 2), np.float32)
+    block[:, 1] *= np.float32(-0.5) * block[:, 1]
+    rows = np.empty((BIG_N, 2), np.float32)
+    for i in range(0, BIG_N, BIG_PERIOD):
+        rows[i:i + BIG_PERIOD] = block[:BIG_N - i]
+    lo, hi = np.array(BIG_LO, np.float32), np.array(BIG_HI, np.float32)
+    assert np.array_equal(lo.astype(np.float64), BIG_LO) and np.array_equal(hi.astype(np.float64), BIG_HI)
+    # the comparisons of a periodic store are periodic: made on the block, repeated, and made again where the hole is
+    above_lo = [np.resize(block[:, c] > lo[c], BIG_N) for c in range(2)]
+    below_hi = [np.resize(block[:, c] < hi[c], BIG_N) for c in range(2)]
+    if request.param:
+        rows[HOLE, 0] = 2.0
+        above_lo[0][HOLE], below_hi[0][HOLE] = True, False
+    for c in range(2):  # (the repeated comparisons are the comparisons: a stretch across a period's end and the hole)
+        for part in (slice(BIG_PERIOD - 1000, BIG_PERIOD + 1000), slice(HOLE.start - 1000, HOLE.start + 1000)):
+            assert np.array_equal(above_lo[c][part], rows[part, c] > lo[c]) and np.array_equal(below_hi[c][part], rows[part, c] < hi[c])
+    keep = above_lo[0] & below_hi[0] & above_lo[1] & below_hi[1]
+    # kept rows per workgroup of 256: none in the hole, some in every other one, so every block sum of the scan counts
+    cnt = np.add.reduceat(keep.view(np.uint8), np.arange(0, BIG_N, 256), dtype=np.int64)
+    first, n = HOLE.start // 256, (HOLE.stop - HOLE.start) // 256
+    assert cnt[:first].all() and cnt[first + n:].all() and (not cnt[first:first + n].any() if request.param else cnt.all())
+    rows.setflags(write=False)
+    yield dict(hole=request.param, rows=rows, nwg=cnt.size, index=np.flatnonzero(keep), kept=rows.view(np.uint64)[:, 0][keep],
+               nbelow=[BIG_N - np.count_nonzero(a) for a in above_lo], nabove=[BIG_N - np.count_nonzero(b) for b in below_hi])
+
+
+def big_geometry(b, monkeypatch):
+    """the geometry the large case is there for, asserted before any result"""
+    from mcpar_amd import engine as E
+    monkeypatch.delenv("MCX_GATHER_CHUNK_ROWS", raising=False)
+    g = E.debug_store_geometry(1, 0, BIG_N, 1)
+    assert g["clip_rows"] == 256 and g["clip_scan_blocks"] > 2 * 256 and BIG_N % 256 != 0, g  # a third step of k_clip_scan<1>
+    assert g["clip_workgroups"] == b["nwg"] and HOLE.start == 256 * 256 * 256, g  # the hole begins the second step
+    K = b["index"].size
+    assert 0.7 < K / BIG_N < 0.8 and E.debug_store_geometry(1, 0, K, 1)["gather_chunk_rows"] * 2 < K  # more than two chunks
+    return g
+
+
+def big_report(rs, b):
+    assert not rs.report["flags"].any()  # no quantile pass ran
+    assert (rs.nrows, rs.nsource, rs.ncol) == (b["index"].size, BIG_N, 2)
+    assert rs.report["nbelow"].tolist() == b["nbelow"] and rs.report["nabove"].tolist() == b["nabove"]
+    assert rs.report["lo"].tolist() == list(BIG_LO) and rs.report["hi"].tolist() == list(BIG_HI)
+
+
+def test_scan_past_two_carries_with_natural_gather_chunks(big, monkeypatch):
+    """np = 1, one chain, N = 2 * 2^24 + 256 * 300 + 77 rows.
+      k_clip_scan<1>, `carry += s[DERIVE_BLOCK - 1]` and `boff[i] = carry + (incl - v)`: 514 scan blocks are three steps of
+        CLIP_FAN = 256, two full and one of two blocks (the last workgroup ragged, 77 rows); every other test has at most two
+        blocks and never adds a carry.  About three rows in four are kept in every workgroup, so every bsum is non-zero and
+        every offset behind block 255 is wrong without the first carry, behind block 511 without the second: the kept rows
+        of those workgroups would land on other rows' places, which index() and rows() show.
+      hole: no row of [2^24, 2^24 + 2^20) is kept -- bsum is zero for blocks 256 .. 271, the first of the second step, so
+        a scan that mishandles empty blocks, or a carry taken from the wrong element, shows as well; k_clip_scatter's
+        `if (kw == 0) return` is taken by 4096 workgroups in a row.
+      gather_to_host, `for (done = 0; done < n; done += chunk)` with its natural chunk of 64 MiB / 8 bytes = 8 388 608 rows:
+        the 25 M kept rows leave in three chunks without MCX_GATHER_CHUNK_ROWS.
+    Explicit bounds on both columns: no quantile pass runs.  No row-number marker: row numbers above 2^24 are not floats."""
+    from mcpar_amd import engine as E
+    big_geometry(big, monkeypatch)
+    rs = E.clip_rows(big["rows"], BIG_N, 1, lo=BIG_LO, hi=BIG_HI)
+    big_report(rs, big)
+    idx = rs.index()
+    assert np.array_equal(idx, big["index"]), np.flatnonzero(idx != big["index"])[:4]
+    del idx
+    assert np.array_equal(rs.rows().view(np.uint64)[:, 0], big["kept"])
+    rs.close()
+
+
+def test_scan_past_two_carries_count_only(big, monkeypatch):
+    """the same store with count_only: the total K is `boff[nb] = carry` after the last step of k_clip_scan<1>, the one
+    number of the report that depends on every carry"""
+    from mcpar_amd import engine as E
+    big_geometry(big, monkeypatch)
+    rs = E.clip_rows(big["rows"], BIG_N, 1, lo=BIG_LO, hi=BIG_HI, count_only=True)
+    assert not rs.h
+    big_report(rs, big)
+
+
 # ---- values on and around a threshold ---------------------------------------------------------------------------------------
 def test_ties_on_a_threshold_are_dropped():
     from mcpar_amd import engine as E

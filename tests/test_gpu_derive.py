@@ -169,6 +169,100 @@ def test_store_analyses_are_the_rows_analyses(shape):
     assert_same_bytes(ident.covariance(), eg.covariance(first_step=first, nsteps=nsteps), "identity covariance")
 
 
+# ---- 3b. the tile heights below 256 rows -------------------------------------------------------------------------------------
+# (np, nout) -> R = derive_rows(np, nout), the rows a workgroup takes.  The shapes above have R = 256, or R = 32 / 16 with
+# fewer rows than one tile.  (20, 19) | (20, 21): the two sides of the LDS budget's edge, (20, 19) using all 40 960 bytes
+TILES = {(20, 19): 256, (20, 21): 128, (40, 17): 128, (17, 40): 128, (100, 3): 64, (3, 100): 64, (256, 2): 32, (2, 256): 32,
+         (256, 256): 16}
+
+
+def host_rows(N, d, seed):
+    rng = np.random.default_rng(seed)
+    rows = rng.standard_normal((N, d + 1)).astype(np.float32)
+    rows[:, -1] = -np.abs(rows[:, -1])
+    return rows
+
+
+@pytest.mark.parametrize("full", [False, True])  # N = 2 R + 5: a third, ragged workgroup; N = 2 R: two full tiles exactly
+@pytest.mark.parametrize("d, nout", sorted(TILES))
+def test_tile_heights_linear_is_the_numpy_float32_loop(d, nout, full):
+    """derive_body's `os = derive_lds + R * sx`, `row0 = blockIdx.x * R`, `mine = tid < rows` and the two
+    derive_tile_copy calls with R < 256: lanes R .. 255 have no row but copy, the second workgroup's tiles start at row R
+    of x and x', and the last one is ragged.  A workgroup that read or wrote at a stride of 256 rows, or an output tile
+    placed for another R, changes rows R .. N - 1, which the bit-for-bit comparison with the numpy loop shows."""
+    import mcpar_amd as M
+    R_ = TILES[(d, nout)]
+    N = 2 * R_ + (0 if full else 5)
+    g = M.debug_store_geometry(d, nout, N, 1)
+    assert g["derive_rows"] == R_ and g["derive_workgroups"] == (2 if full else 3), g
+    assert (g["derive_lds_bytes"] == 40960) == ((d, nout) == (20, 19)), g
+    A, b = linear_map(d, nout)
+    rows = host_rows(N, d, 7 * d + nout)
+    st = M.derive_rows(rows, N, 1, M.derive_linear(A, b))
+    assert st.shape == (N, 1, nout + 1)
+    got, want = st.rows(), linear_ref(rows, A, b)
+    assert same_bits(got, want), np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4]
+    st.close()
+
+
+@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("d, nout", sorted(TILES))
+def test_tile_heights_source_restating_linear(d, nout, full):
+    """the same shapes through the run-time build, which gets np and nout as constants: a different kernel per shape, held
+    to LINEAR's bytes (which the test above holds to the numpy loop's)"""
+    import mcpar_amd as M
+    need_hiprtc()
+    R_ = TILES[(d, nout)]
+    N = 2 * R_ + (0 if full else 5)
+    g = M.debug_store_geometry(d, nout, N, 1)
+    assert g["derive_rows"] == R_ and g["derive_workgroups"] == (2 if full else 3), g
+    A, b = linear_map(d, nout)
+    rows = host_rows(N, d, 7 * d + nout)
+    lin = M.derive_rows(rows, N, 1, M.derive_linear(A, b))
+    src = M.derive_rows(rows, N, 1, M.derive_source(example("derive_linear.hip"), nout, np.concatenate([A.reshape(-1), b])))
+    assert src.shape == (N, 1, nout + 1) and src.rows().tobytes() == lin.rows().tobytes()
+    lin.close()
+    src.close()
+
+
+@pytest.mark.parametrize("d, nc, nout, R_", [(41, 7, 17, 128), (101, 3, 3, 64), (255, 3, 2, 32)])
+def test_tile_heights_from_an_unaligned_store(d, nc, nout, R_):
+    """derive_body's `((unsigned long)gx & 15ul) == 0`: steps [1, T) of an engine's store with nc * np odd start off a
+    16-byte boundary, so derive_tile_copy<true> takes its 4-byte path at this tile height; the same steps given as host rows
+    are uploaded to a fresh allocation and take the 16-byte path.  Both give the numpy loop's bits."""
+    import mcpar_amd as M
+    T = 2 + (2 * R_ + nc) // nc
+    ns = T - 1
+    g = M.debug_store_geometry(d, nout, ns, nc)
+    assert g["derive_rows"] == R_ and g["derive_workgroups"] >= 3 and (nc * d * 4) % 16 != 0, g
+    eg = engine(nc, d, T)
+    A, b = linear_map(d, nout)
+    spec = M.derive_linear(A, b)
+    rows = eg.samples_range(1, ns)
+    want = linear_ref(rows, A, b)
+    for st in (eg.derive(spec, first_step=1, nsteps=ns), M.derive_rows(rows, ns, nc, spec)):
+        assert st.shape == (ns, nc, nout + 1)
+        got = st.rows()
+        assert same_bits(got, want), np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4]
+        st.close()
+
+
+def test_store_analyses_at_a_reduced_tile_height():
+    """a store written by workgroups of 64 rows is a store like any other: its summary and covariance are those of its rows"""
+    import mcpar_amd as M
+    from mcpar_amd import engine as E
+    d, nout, T, nc = 100, 3, 19, 7
+    g = M.debug_store_geometry(d, nout, T, nc)
+    assert g["derive_rows"] == 64 and g["derive_workgroups"] == 3, g
+    rows = host_rows(T * nc, d, 64)
+    st = M.derive_rows(rows, T, nc, M.derive_linear(*linear_map(d, nout)))
+    out = st.rows()
+    assert same_bits(out, linear_ref(rows, *linear_map(d, nout)))
+    assert_same_bytes(st.summary(PROBS), E.rows_summary(out, T, nc, PROBS), "summary")
+    assert_same_bytes(st.covariance(), E.rows_covariance(out, T, nc), "covariance")
+    st.close()
+
+
 # ---- 4. non-finite outputs -------------------------------------------------------------------------------------------------
 PLANT = """
 // par = (on, x0 of the row that gets par[3] in output 1, x0 of the row that gets par[4] in output 2, NaN, -inf)

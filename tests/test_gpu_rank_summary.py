@@ -38,33 +38,7 @@ def ordered(z):
 
 # ---- 1. ranks exact, z within one float ulp
 SHAPES = [(1, 1, 4), (5, 33, 37), (16, 64, 600), (17, 3, 257), (33, 2, 64), (2, 513, 257), (256, 2, 8)]  # np, nc, T
-KINDS = ["equal", "two", "top-byte", "low-byte", "zeros", "mh", "ascending", "descending", "normal"]
-
-
-def content(kind, T, nc, rng):
-    """one column [T, nc] float32"""
-    N = T * nc
-    if kind == "equal":
-        return np.full((T, nc), 1.5, np.float32)
-    if kind == "two":
-        return rng.choice(np.array([-2.0, 3.0], np.float32), (T, nc))
-    if kind == "top-byte":  # +-2^(16 j): the keys differ in their top byte only
-        return (rng.choice([-1.0, 1.0], (T, nc)) * 2.0 ** (16 * rng.integers(-3, 4, (T, nc)))).astype(np.float32)
-    if kind == "low-byte":  # consecutive floats: the keys differ in their lowest byte only
-        return (np.float32(1.0).view(np.uint32) + rng.integers(0, 200, (T, nc)).astype(np.uint32)).view(np.float32)
-    if kind == "zeros":
-        return rng.choice(np.array([-0.0, 0.0, 1e-45, -1e-45, 1e-40, -1e-40, 1.1754942e-38, -3e-39], np.float32), (T, nc))
-    if kind == "mh":  # every value repeats its predecessor in the chain with probability 0.7
-        x = rng.standard_normal((T, nc)).astype(np.float32)
-        keep = rng.random((T, nc)) < 0.7
-        for s in range(1, T):
-            x[s] = np.where(keep[s], x[s - 1], x[s])
-        return x
-    if kind == "ascending":
-        return (np.arange(N, dtype=np.float32) - np.float32(N // 3)).reshape(T, nc)
-    if kind == "descending":
-        return (np.float32(N // 3) - np.arange(N, dtype=np.float32) * np.float32(0.5)).reshape(T, nc)
-    return rng.standard_normal((T, nc)).astype(np.float32)
+KINDS, content = K.KINDS, K.content  # (shared with tests/test_rank_summary_cpu.py)
 
 
 @pytest.mark.parametrize("np_,nc,T", SHAPES)
@@ -94,6 +68,70 @@ def test_ranks_exact_and_scores_within_an_ulp(np_, nc, T, monkeypatch):
                 assert np.array_equal(out[:, :, c], ref[c][ik]), (KINDS[(k0 + c) % len(KINDS)], "column", c, ik)
     STATS["z_ulp"] = max(STATS.get("z_ulp", 0), worst)
     print("largest z difference: %d ulp (N = %d)" % (worst, N))
+
+
+# ---- 1b. the rank sort past two carries of its scan, and more than 64 steps per workgroup of the sweeps
+@pytest.fixture(scope="module")
+def big():
+    """rank_cases.big_columns() as rows, with the float64 reference of both columns, made once: the average ranks from one
+    sort (rank_ref.ranks_by_sort; tests/test_rank_summary_cpu.py holds it equal to rank_ref.ranks and the content to what
+    the test below says of it) and the thresholds.  np = 1, nc = 2, T = 2 101 267: the smallest shape past all three size
+    switches of mcx_ranks.hip at once."""
+    np_, nc, T = K.BIG_SHAPE
+    cols = K.big_columns()
+    yield dict(T=T, nc=nc, N=T * nc, cols=cols, rows=K.rows_of(cols), ranks=[RR.ranks_by_sort(c) for c in cols],
+               thr=[RR.thresholds(c) for c in cols])
+
+
+def big_geometry(b):
+    """the geometry the large case is there for, asserted before any result"""
+    from mcpar_amd import engine as E
+    g = E.debug_store_geometry(1, 0, b["T"], b["nc"])
+    assert g["rank_tiles"] > 2 * 256 and b["N"] % 8192 != 0, g  # a third step of k_rank_scan, a ragged last tile
+    assert g["rank_step_chunk"] > 64 and g["rank_grid_y"] == -(-b["T"] // g["rank_step_chunk"]), g
+    return g
+
+
+def test_ranks_past_two_scan_carries_and_a_longer_step_chunk(big, monkeypatch):
+    """k_rank_scan, `carry += sh[SB - 1]` at the end of its loop over steps of 256 tiles: 514 tiles are three steps, two full
+        and one of two tiles, so the offsets of tiles 256 .. 513 are right only with both carries.  Normal values have every
+        low-byte digit in every full tile and their share of each higher digit in every stretch of 256 tiles, so in each of
+        the four passes every digit row that holds keys has non-zero counts behind tile 255 and behind tile 511; a wrong
+        offset puts keys at wrong places of the sorted column, and a rank is a position in it.
+      k_rank_rowsum, `for (i = threadIdx.x; i < nblk; i += SB)`: the same 514 counts, three a thread for threads 0 and 1.
+      k_rank_keys / k_rank_transform, `s0 = blockIdx.y * rchunk`: rchunk = 65 here and 64 in every other test.  A step
+        left out leaves its key unwritten or its rank and score zero, which is why every value is compared, not a sample.
+      The last tile is ragged (38 keys), and tie runs (a value repeats its predecessor in the chain with probability 0.3,
+      a rejected step repeating the whole row) lie across tile boundaries: with nc = 2 a run's keys are two apart.
+    The average ranks are exact on every value of both columns; the scores are within the one ulp of section 1 on 20 000
+    fixed positions (rank_ref.normal_scores is a Python loop over the distinct ranks)."""
+    from mcpar_amd import engine as E
+    monkeypatch.delenv("MCX_RANK_GROUP_COLS", raising=False)
+    g = big_geometry(big)
+    T, nc, N = big["T"], big["nc"], big["N"]
+    out, ranks = E.debug_rows_rank_transform(big["rows"], T, nc, E.RANK_Z, want_ranks=True)
+    pos = np.random.default_rng(5).choice(N, 20000, replace=False)
+    worst = 0
+    for c, want in enumerate(big["ranks"]):
+        assert np.array_equal(ranks[:, c], want), ("ranks, column", c, np.flatnonzero(ranks[:, c] != want)[:8])
+        d = np.abs(ordered(out[pos, c]) - ordered(RR.normal_scores(want[pos], N))).max()
+        worst = max(worst, int(d))
+        assert d <= 1, ("z, column", c)
+    print("largest z difference: %d ulp (N = %d, %d tiles, %d steps a workgroup)" % (worst, N, g["rank_tiles"], g["rank_step_chunk"]))
+
+
+@pytest.mark.parametrize("what, k", [(2, 0), (3, 2)])  # RANK_I05 against q05, RANK_I95 against q95
+def test_indicators_with_a_longer_step_chunk(big, what, k):
+    """k_rank_transform's indicator branch, `for (s = s0; s < s1; ++s) q[s * t.rs] = p[s * t.rs] <= lim`, with
+    s0 = blockIdx.y * rchunk and rchunk = 65: a step left out stays 0 in the transformed store, and about one value in twenty
+    (I05) or nineteen in twenty (I95) are 1 everywhere along the chains, so the indicators are exact on every value."""
+    from mcpar_amd import engine as E
+    big_geometry(big)
+    out = E.debug_rows_rank_transform(big["rows"], big["T"], big["nc"], what)
+    for c, col in enumerate(big["cols"]):
+        want = (col.reshape(-1).astype(np.float64) <= big["thr"][c][k]).astype(np.float32)
+        assert 0.04 < want.mean() - (0.0 if k == 0 else 0.9) < 0.06
+        assert np.array_equal(out[:, c], want), ("indicator", what, "column", c)
 
 
 # ---- 2. / 3. diagnostics

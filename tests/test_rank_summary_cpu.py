@@ -50,6 +50,47 @@ def test_reference_ranks_are_the_counting_definition(k):
     assert r.sum() == v.size * (v.size + 1) / 2
 
 
+def test_sort_based_ranks_are_the_reference_ranks():
+    """rank_ref.ranks_by_sort (for the multi-million-value GPU case) against rank_ref.ranks: the small arrays above, every
+    content kind of the GPU test at two of its shapes, NaNs, and the vectorised "mh" content"""
+    rng = np.random.default_rng(11)
+    cases = [np.array(a, np.float32) for a in RANK_ARRAYS]
+    cases += [K.content(kind, T, nc, rng) for kind in K.KINDS for T, nc in ((37, 33), (257, 3))]
+    cases.append(np.array([2.0, np.nan, -1.0, np.nan, 2.0, np.inf, -np.inf], np.float32))
+    cases.append(np.array([7.0], np.float32))
+    src = K.repeats(5000, 2, rng, 0.3)
+    mh = rng.standard_normal((5000, 2)).astype(np.float32)[src, np.arange(2)]
+    assert 0.25 < (np.diff(src, axis=0) == 0).mean() < 0.35 and (mh[1:] == mh[:-1]).mean() > 0.25
+    cases.append(mh)
+    for v in cases:
+        got, want = RR.ranks_by_sort(v), RR.ranks(v)
+        assert got.dtype == np.float64 and np.array_equal(got, want)
+    assert np.array_equal(RR.ranks_by_sort(cases[0]), counting_ranks(cases[0]))
+
+
+def test_the_large_case_is_what_its_gpu_test_says():
+    """rank_cases.big_columns(), the content of test_gpu_rank_summary.py's case past the size switches: all three switches
+    crossed, tie runs across the boundaries of the sort tiles, every byte of the keys varying behind tile 255 and behind
+    tile 511 too, log L negative -- and the sort-based ranks against rank_ref.ranks on a stretch of it"""
+    np_, nc, T = K.BIG_SHAPE
+    N = T * nc
+    assert -(-N // 8192) == 514 and N % 8192 == 38 and max(64, (T + 32767) // 32768) == 65
+    cols = K.big_columns()
+    assert (cols[1] < 0).all() and np.isfinite(cols[0]).all() and np.isfinite(cols[1]).all()
+    tiles = np.arange(N) // 8192
+    for c in cols:
+        flat = c.reshape(-1)
+        assert c.dtype == np.float32 and c.shape == (T, nc) and 0.29 < (c[1:] == c[:-1]).mean() < 0.31
+        tied = flat[2:] == flat[:-2]  # a chain's consecutive steps are nc = 2 apart
+        assert (tied & (tiles[2:] != tiles[:-2])).sum() > 100
+        k = R.okey(flat)
+        for lo in (0, 256 * 8192, 512 * 8192):
+            for shift, least in ((0, 256), (8, 256), (16, 256), (24, 4)):
+                assert np.count_nonzero(np.bincount((k[lo:] >> shift) & 255, minlength=256)) >= least, (lo, shift)
+        part = c[:50000]
+        assert np.array_equal(RR.ranks_by_sort(part), RR.ranks(part))
+
+
 def test_reference_normal_scores():
     N = 1221
     r = np.arange(1, N + 1, dtype=np.float64)
