@@ -544,6 +544,72 @@ int mcx_debug_rows_density_bins(const float *rows, int nsteps, int nc, int np, c
 int mcx_debug_density_times(mcx_engine *e, int first_step, int nsteps, const mcx_density_spec *spec, double *ms);
 int mcx_debug_store_density_times(mcx_store *s, const mcx_density_spec *spec, double *ms); /* the same of a derived store */
 
+/* ---- pair densities of the sample store, on the device --------------
+ * The corner plot: per pair (a, b) of columns, a != b, the binned product-Gaussian kernel density estimate of MASS::kde2d
+ * with bandwidth.nrd, which is what geom_density_2d evaluates, on the g x g nodes of the two columns' grids.  N = nsteps * nc
+ * rows, 2 <= N < 2^31; 8 <= g <= 64; F = 4096.
+ *   per column (the same in every pair the column is in)
+ *   mean, sd, min, max, q25, q75, from, to   as in section 13 above (clip, log L's upper end, spec->from / to)
+ *   bw         s = min(sd, (q75 - q25) / 1.34), or sd where that is 0, or |min|, or 1;  h = adjust * 1.06 * s * N^(-1/5)
+ *              (bandwidth.nrd / 4, as kde2d divides it).  A positive finite spec->bw[c] replaces it (adjust is not applied)
+ *   lo, up     from - 4 h, to + 4 h;  delta = (up - lo) / (g - 1),  inv = (g - 1) / (up - lo);  axis[c][j] = lo + j delta
+ *   a value v  xpos = (double(v) - lo) * inv; on the grid iff -1 <= xpos < g (a NaN is not);
+ *              s(v) = floor(xpos) + 1 in [0, g],  w(v) = floor((xpos - floor(xpos)) * F) in [0, F]
+ *   per pair
+ *   slots      a row whose two values are both on their grids adds to slot [s_a][s_b] of (g + 1) x (g + 1) slots the u64 sums
+ *              cnt += 1, Sa += w_a, Sb += w_b, Sab += w_a w_b; every other row is dropped from this pair only;
+ *              nbinned = the sum of cnt
+ *   masses     num[j][k] = (F^2 cnt - F Sa - F Sb + Sab)[j+1][k+1] + (F Sa - Sab)[j][k+1] + (F Sb - Sab)[j+1][k] + Sab[j][k],
+ *              an exact integer; mass[j][k] = double(num[j][k]) / (F^2 double(N)),  0 <= j, k < g
+ *   kernel     K_c[i] = exp(-(i delta_c / h_c)^2 / 2) / (h_c sqrt(2 pi)), i < g
+ *   z[j][k]    = sum over l of t[j][l] K_b[|l - k|],  t[j][l] = sum over m of mass[m][l] K_a[|m - j|], both ascending, plain
+ *              fp64 sums on the host; z is the density at (axis[a][j], axis[b][k]).  For a > b the pair is summed as (b, a) and
+ *              turned, so that z of (b, a) is the transpose of z of (a, b) bit for bit
+ * The sweeps add integers only: the same store and arguments give the same bytes.  A pair with a column that holds an inf or
+ * NaN has MCX_SUMMARY_NONFINITE, NaN in its z and nbinned = 0 (that column's record and axis are NaN, as in section 13); every
+ * other pair is what it would be without that column. */
+typedef struct mcx_density2d_spec {
+  int g;                    /* grid nodes per axis, 8..64 */
+  double adjust;            /* > 0; multiplies the bandwidth */
+  double clip_lo, clip_hi;  /* 0, 1 = the data's range; else 0 <= clip_lo < clip_hi <= 1 */
+  const double *bw, *from, *to; /* NULL, or [ncol]; a NaN entry = the default of that column */
+  int npairs;               /* 1..1024; not read when pairs is NULL */
+  const int *pairs;         /* [npairs][2] columns (a, b); NULL = every a < b in ascending order (at most 45 columns) */
+} mcx_density2d_spec;
+typedef struct mcx_pair_density {
+  int a, b;
+  long long nbinned;
+  int flags;                /* MCX_SUMMARY_* */
+} mcx_pair_density;
+/* Steps [first_step, first_step + nsteps) of the store; cols[ncol] (mcx_col_density with nbinned left 0), axes[ncol][g],
+ * pairs_out[npairs] and z[npairs][g][g], npairs = ncol (ncol - 1) / 2 when spec->pairs is NULL.  MCX_ERR_INVALID, before a
+ * device is touched, in the cases mcx_samples_density refuses and for g outside 8..64, a == b, a column outside [0, ncol),
+ * npairs outside 1..1024 (the default of more than 45 columns too: name the pairs); MCX_ERR_UNSUPPORTED for N >= 2^31;
+ * MCX_ERR_ALLOC with the bytes needed in mcx_last_error when the scratch does not fit.  A queued MCX_OPT_ASYNC_RUN run is
+ * finished first. */
+int mcx_samples_density2d(mcx_engine *e, int first_step, int nsteps, const mcx_density2d_spec *spec, mcx_col_density *cols,
+                          double *axes, mcx_pair_density *pairs_out, double *z);
+/* the same for host rows in MCout layout, and for a derived store (a clip's mcx_rowset_store too) */
+int mcx_rows_density2d(const float *rows, int nsteps, int nc, int np, const mcx_density2d_spec *spec, mcx_col_density *cols,
+                       double *axes, mcx_pair_density *pairs_out, double *z);
+int mcx_store_density2d(mcx_store *s, const mcx_density2d_spec *spec, mcx_col_density *cols, double *axes,
+                        mcx_pair_density *pairs_out, double *z);
+/* The two host steps (no device): the record of column `col` from its statistics, as mcx_debug_density_grid; and z[g][g] of
+ * one pair from its two records and slots[(g + 1)^2][4] = (cnt, Sa, Sb, Sab), b_first != 0 for the sums of a > b.  The
+ * product path calls these very functions. */
+int mcx_debug_density2d_grid(long long N, double mean, double sd, float min, float max, double q25, double q75,
+                             double qclip_lo, double qclip_hi, int is_last_col, int col, const mcx_density2d_spec *spec,
+                             mcx_col_density *out);
+int mcx_debug_density2d_finish(const mcx_col_density *ca, const mcx_col_density *cb, int g, const unsigned long long *slots,
+                               int b_first, double *z);
+/* the device sweeps alone on given grids lo[np + 1] < up[np + 1]: slots[npairs][(g + 1)^2][4]; pairs as in the spec */
+int mcx_debug_rows_density2d_bins(const float *rows, int nsteps, int nc, int np, const double *lo, const double *up, int g,
+                                  int npairs, const int *pairs, unsigned long long *slots);
+/* one mcx_samples_density2d call, its results let go: ms[0] the statistics passes (wall clock), ms[1] k_density2d_codes,
+ * ms[2] k_density2d_pairs, ms[3] k_density2d_reduce (HIP events), ms[4] the host grids and finish (wall clock), ms[5] the
+ * whole call (wall clock) */
+int mcx_debug_density2d_times(mcx_engine *e, int first_step, int nsteps, const mcx_density2d_spec *spec, double *ms);
+
 /* ---- tail-clipped rows of the sample store, on the device -----------
  * The reference's mcparam.clip.tails (src/anly/mcpar-analysis.R:60-78): every row that lies in the tail of any column is
  * dropped, jointly, and the remaining rows are handed on.  The source is a step range of an engine's store, host rows in

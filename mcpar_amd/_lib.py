@@ -35,6 +35,13 @@ class DensitySpecC(C.Structure):
                 ("bw", C.POINTER(C.c_double)), ("from_", C.POINTER(C.c_double)), ("to", C.POINTER(C.c_double))]
 
 
+class Density2dSpecC(C.Structure):
+    """include/mcx.h mcx_density2d_spec"""
+    _fields_ = [("g", C.c_int), ("adjust", C.c_double), ("clip_lo", C.c_double), ("clip_hi", C.c_double),
+                ("bw", C.POINTER(C.c_double)), ("from_", C.POINTER(C.c_double)), ("to", C.POINTER(C.c_double)),
+                ("npairs", C.c_int), ("pairs", C.POINTER(C.c_int))]
+
+
 class ClipSpecC(C.Structure):
     """include/mcx.h mcx_clip_spec"""
     _fields_ = [("qlo", C.c_double), ("qhi", C.c_double), ("ll_hi", C.c_double),
@@ -156,6 +163,15 @@ def load():
         "mcx_debug_rows_density_bins": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_ulonglong)],
         "mcx_debug_density_times": [vp, C.c_int, C.c_int, C.POINTER(DensitySpecC), dp],
         "mcx_debug_store_density_times": [vp, C.POINTER(DensitySpecC), dp],
+        "mcx_samples_density2d": [vp, C.c_int, C.c_int, C.POINTER(Density2dSpecC), vp, dp, vp, dp],
+        "mcx_rows_density2d": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(Density2dSpecC), vp, dp, vp, dp],
+        "mcx_store_density2d": [vp, C.POINTER(Density2dSpecC), vp, dp, vp, dp],
+        "mcx_debug_density2d_grid": [C.c_longlong, C.c_double, C.c_double, C.c_float, C.c_float, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Density2dSpecC), vp],
+        "mcx_debug_density2d_finish": [vp, vp, C.c_int, C.POINTER(C.c_ulonglong), C.c_int, dp],
+        "mcx_debug_rows_density2d_bins": [fp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_ulonglong)],
+        "mcx_debug_density2d_times": [vp, C.c_int, C.c_int, C.POINTER(Density2dSpecC), dp],
         "mcx_samples_clip": [vp, C.c_int, C.c_int, C.POINTER(ClipSpecC), vp, C.POINTER(C.c_longlong), C.POINTER(vp)],
         "mcx_rows_clip": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(ClipSpecC), vp, C.POINTER(C.c_longlong), C.POINTER(vp)],
         "mcx_store_clip": [vp, C.POINTER(ClipSpecC), vp, C.POINTER(C.c_longlong), C.POINTER(vp)],

@@ -217,6 +217,11 @@ int density_device(hipStream_t st, Bufs B, const StoreView &v, const mcx_density
 
 }  // namespace
 
+int density_spec_args(const mcx_density_spec *spec, int ncol, int64_t N, const mcx_col_density *cols, const double *x, const double *y)
+{
+  return density_args(spec, ncol, N, cols, x, y);
+}
+
 int density_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_density_spec *spec, mcx_col_density *cols, double *x, double *y,
                  double *ms)
 {

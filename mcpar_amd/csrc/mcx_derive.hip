@@ -336,6 +336,13 @@ extern "C" int mcx_store_density(mcx_store *s, const mcx_density_spec *spec, mcx
   return density_span(s->st, s->bufs(), s->span(), spec, cols, x, y);
 }
 
+extern "C" int mcx_store_density2d(mcx_store *s, const mcx_density2d_spec *spec, mcx_col_density *cols, double *axes,
+                                   mcx_pair_density *pairs_out, double *z)
+{
+  MCXCHK(store_enter(s));
+  return density2d_span(s->st, s->bufs(), s->span(), spec, cols, axes, pairs_out, z);
+}
+
 // mcx_store_density with its stages timed (mcx_debug_density_times' ms[4]), for tools/density_bench.py; the results are let go
 extern "C" int mcx_debug_store_density_times(mcx_store *s, const mcx_density_spec *spec, double *ms)
 {

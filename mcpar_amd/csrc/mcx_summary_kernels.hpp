@@ -46,6 +46,11 @@ MCXI int rank_span(hipStream_t st, Bufs B, const StoreSpan &s, mcx_col_rank_summ
 MCXI int covariance_span(hipStream_t st, Bufs B, const StoreSpan &s, double *mean, double *cov, int *flags);  // mcx_covariance.hip
 MCXI int density_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_density_spec *spec, mcx_col_density *cols, double *x,
                       double *y, double *ms = nullptr);  // mcx_density.hip; ms: mcx_debug_density_times' four stages
+MCXI int density2d_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_density2d_spec *spec, mcx_col_density *cols,
+                        double *axes, mcx_pair_density *pairs_out, double *z);  // mcx_density2d.hip (section 15)
+// what mcx_density.hip refuses before a device is touched, for mcx_density2d.hip, whose spec shares those fields
+MCXI int density_spec_args(const mcx_density_spec *spec, int ncol, int64_t N, const mcx_col_density *cols, const double *x,
+                           const double *y);
 
 // The launch geometry of a rank pass over T steps and N = T * nc values per column (mcx_ranks.hip): what RankPass launches
 // with and what mcx_debug_store_geometry reports

@@ -8,6 +8,7 @@
 //             [--derived-summary FILE] [--derived-rank-summary FILE] [--derived-covariance FILE]
 //             [--draws FILE --ndraw N [--draw-seed S]]
 //             [--density FILE] [--derived-density FILE] [--density-n N] [--density-clip QLO,QHI]
+//             [--density2d FILE] [--derived-density2d FILE] [--density2d-n G] [--density2d-pairs a:b,c:d,...]
 //             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -36,6 +37,11 @@
 // lines `name x y` per column p0 .. LL.  --density-clip QLO,QHI: from the QLO to the QHI quantile of a column instead of min to
 // max (log L keeps its maximum).  --derived-density FILE: the same for the derived columns d0 .. LL.  Both under the
 // conditions of --summary.
+// --density2d FILE: the joint kernel density estimate of pairs of columns of the kept rows on the GPU (mcx_rows_density2d;
+// MASS::kde2d / geom_density_2d, the corner plot) in long form: a header `a b x y density`, then G * G lines `name_a name_b x y
+// z` per pair, x varying slowest, with the names of --density's file.  --density2d-n G (default 64, 8 to 64): nodes per axis.
+// --density2d-pairs a:b,c:d,...: these pairs of column indices (log L is np) instead of every a < b.  --density-clip applies.
+// --derived-density2d FILE: the same for the derived columns d0 .. LL.  Both under the conditions of --summary.
 // --clip QLO,QHI (default 0.01,0.99) and --clip-ll-hi V (default 0): the reference's mcparam.clip.tails on the GPU
 // (mcx_rows_clip): the kept rows lie strictly between the QLO and QHI quantiles of every column, log L below V.
 // --clip-report FILE: a header `column lo hi nbelow nabove`, one line per column p0 .. LL, then `kept K of N`.  --clipped FILE:
@@ -209,6 +215,58 @@ static int write_density(const char *path, const mcx_density_spec &spec, MCout &
   return print_density(path, x, y, np, spec.n, 'p');
 }
 
+// the long form of a pair density call: G * G lines per pair
+static int print_density2d(const char *path, const std::vector<mcx_pair_density> &pairs, const std::vector<double> &axes,
+                           const std::vector<double> &z, int np, int g, char prefix)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "a b x y density\n");
+  for (size_t p = 0; p < pairs.size(); ++p) {
+    const std::string na = colname(prefix, pairs[p].a, np), nb = colname(prefix, pairs[p].b, np);
+    const double *xa = axes.data() + (size_t)pairs[p].a * g, *xb = axes.data() + (size_t)pairs[p].b * g;
+    for (int j = 0; j < g; ++j)
+      for (int k = 0; k < g; ++k)
+        fprintf(f, "%s %s %.17g %.17g %.17g\n", na.c_str(), nb.c_str(), xa[j], xb[k], z[(p * g + j) * g + k]);
+  }
+  return fclose(f) == 0 ? 0 : 1;
+}
+
+// the outputs of a pair density call of ncol columns, sized for the spec (a refused spec still gets buffers)
+struct Density2dOut {
+  std::vector<mcx_col_density> cols;
+  std::vector<mcx_pair_density> pairs;
+  std::vector<double> axes, z;
+  Density2dOut(const mcx_density2d_spec &spec, size_t ncol)
+  {
+    const size_t g = (size_t)(spec.g > 0 && spec.g <= 64 ? spec.g : 64);
+    size_t n = spec.pairs ? (size_t)(spec.npairs > 0 ? spec.npairs : 1) : ncol * (ncol - 1) / 2;
+    if (n < 1 || n > 1024) n = 1;
+    cols.resize(ncol);
+    pairs.resize(n);
+    axes.resize(ncol * g);
+    z.resize(n * g * g);
+  }
+};
+
+// --density2d: the joint density estimate of pairs of columns of MCout's rows
+static int write_density2d(const char *path, const mcx_density2d_spec &spec, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || (long long)nsamp * nc < 2) {
+    std::cerr << "--density2d: " << rows.size() << " rows stored, a density needs nsamp * nc >= 2 of them\n";
+    return 1;
+  }
+  Density2dOut o(spec, (size_t)np + 1);
+  if (mcx_rows_density2d(rows.getpset(0), nsamp, nc, np, &spec, o.cols.data(), o.axes.data(), o.pairs.data(), o.z.data()) != MCX_OK) {
+    std::cerr << "--density2d: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  return print_density2d(path, o.pairs, o.axes, o.z, np, spec.g, 'p');
+}
+
 // --clip-report / --clipped / --clipped-density: one clip of MCout's rows, the row set's files
 static int write_clip(const mcx_clip_spec &spec, const char *report_path, const char *rows_path, const char *dens_path, int clip_nc,
                       const mcx_density_spec &dspec, MCout &rows, int nsamp, int nc, int np)
@@ -293,7 +351,8 @@ static int write_clip(const mcx_clip_spec &spec, const char *report_path, const 
 
 // --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
 static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
-                         const mcx_density_spec &dspec, MCout &rows, int nsamp, int nc, int np)
+                         const mcx_density_spec &dspec, const char *dens2d_path, const mcx_density2d_spec &d2spec, MCout &rows, int nsamp,
+                         int nc, int np)
 {
   if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
     std::cerr << "--derived-*: " << rows.size() << " rows stored, a derive needs nsamp * nc of them\n";
@@ -336,6 +395,13 @@ static int write_derived(const mcx_derive &spec, const char *sum_path, const cha
       std::cerr << "--derived-density: " << mcx_last_error() << "\n";
       rc = 1;
     } else rc = print_density(dens_path, x, y, K, dspec.n, 'd');
+  }
+  if (rc == 0 && dens2d_path) {
+    Density2dOut o(d2spec, (size_t)K + 1);
+    if (mcx_store_density2d(st, &d2spec, o.cols.data(), o.axes.data(), o.pairs.data(), o.z.data()) != MCX_OK) {
+      std::cerr << "--derived-density2d: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_density2d(dens2d_path, o.pairs, o.axes, o.z, K, d2spec.g, 'd');
   }
   mcx_store_destroy(st);
   return rc;
@@ -449,6 +515,9 @@ int main(int argc, char *argv[])
   mcx_clip_spec clip_spec = {0.01, 0.99, 0.0, 0, 0};
   int clip_nc = 1024;
   mcx_density_spec density_spec = {512, 1.0, 0.0, 1.0, 0, 0, 0};
+  std::string density2d_file, derived_density2d_file;
+  mcx_density2d_spec density2d_spec = {64, 1.0, 0.0, 1.0, 0, 0, 0, 0, 0};
+  std::vector<int> density2d_pairs;
   std::vector<float> user_par, derive_par;
   int derive_nout = 0;
   long long ndraw = 0;
@@ -498,6 +567,21 @@ int main(int argc, char *argv[])
         return 2;
       }
     }
+    else if (a == "--density2d") density2d_file = val();
+    else if (a == "--derived-density2d") derived_density2d_file = val();
+    else if (a == "--density2d-n") density2d_spec.g = atoi(val());
+    else if (a == "--density2d-pairs") {
+      std::stringstream ss(val());
+      for (std::string tok; std::getline(ss, tok, ',');) {
+        int pa, pb;
+        if (sscanf(tok.c_str(), "%d:%d", &pa, &pb) != 2) {
+          std::cerr << "--density2d-pairs takes a:b,c:d,...\n";
+          return 2;
+        }
+        density2d_pairs.push_back(pa);
+        density2d_pairs.push_back(pb);
+      }
+    }
     else if (a == "--clip") {
       if (sscanf(val(), "%lf,%lf", &clip_spec.qlo, &clip_spec.qhi) != 2) {
         std::cerr << "--clip takes QLO,QHI\n";
@@ -513,6 +597,12 @@ int main(int argc, char *argv[])
     else if (a == "--ndraw") ndraw = atoll(val());
     else if (a == "--draw-seed") draw_seed = (unsigned)strtoul(val(), 0, 10);
     else { std::cerr << "unknown option " << a << "\n"; return 2; }
+  }
+  density2d_spec.clip_lo = density_spec.clip_lo;  // --density-clip applies to both
+  density2d_spec.clip_hi = density_spec.clip_hi;
+  if (!density2d_pairs.empty()) {
+    density2d_spec.npairs = (int)(density2d_pairs.size() / 2);
+    density2d_spec.pairs = density2d_pairs.data();
   }
   MPI_Init(&argc, &argv);
   int size, rank;
@@ -539,6 +629,13 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
+  if (!density2d_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--density2d needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
   if (!density_file.empty() && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--density needs the rows on the host of a single rank: not with "
@@ -555,7 +652,7 @@ int main(int argc, char *argv[])
     return 2;
   }
   const bool want_derived = !derived_summary_file.empty() || !derived_rank_summary_file.empty() || !derived_covariance_file.empty() ||
-                            !derived_density_file.empty();
+                            !derived_density_file.empty() || !derived_density2d_file.empty();
   const bool have_derive = !derive_source_file.empty() || !derive_linear_file.empty();
   if ((want_derived || !draws_file.empty()) && (stream_text || size > 1)) {
     if (rank == 0)
@@ -666,6 +763,10 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
+  if (!density2d_file.empty() && write_density2d(density2d_file.c_str(), density2d_spec, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
   if (want_clip && write_clip(clip_spec, clip_report_file.empty() ? 0 : clip_report_file.c_str(),
                               clipped_file.empty() ? 0 : clipped_file.c_str(),
                               clipped_density_file.empty() ? 0 : clipped_density_file.c_str(), clip_nc, density_spec, rslts, nsamp, nc,
@@ -699,7 +800,8 @@ int main(int argc, char *argv[])
     if (write_derived(spec, derived_summary_file.empty() ? 0 : derived_summary_file.c_str(),
                       derived_rank_summary_file.empty() ? 0 : derived_rank_summary_file.c_str(),
                       derived_covariance_file.empty() ? 0 : derived_covariance_file.c_str(),
-                      derived_density_file.empty() ? 0 : derived_density_file.c_str(), density_spec, rslts, nsamp, nc, np) != 0) {
+                      derived_density_file.empty() ? 0 : derived_density_file.c_str(), density_spec,
+                      derived_density2d_file.empty() ? 0 : derived_density2d_file.c_str(), density2d_spec, rslts, nsamp, nc, np) != 0) {
       MPI_Finalize();
       return 2;
     }

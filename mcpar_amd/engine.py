@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ClipSpecC, Counters, DensitySpecC, Derive, PlanItem,
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ClipSpecC, Counters, Density2dSpecC, DensitySpecC, Derive, PlanItem,
                    Profile, StoreGeometry, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
@@ -50,6 +50,9 @@ assert DENSITY_DTYPE.itemsize == 80
 CLIP_DTYPE = np.dtype([("lo", np.float64), ("hi", np.float64), ("nbelow", np.int64), ("nabove", np.int64), ("flags", np.int32)],
                       align=True)
 assert CLIP_DTYPE.itemsize == 40
+# include/mcx.h mcx_pair_density
+PAIR_DENSITY_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("nbinned", np.int64), ("flags", np.int32)], align=True)
+assert PAIR_DENSITY_DTYPE.itemsize == 24
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
@@ -369,6 +372,95 @@ def debug_rows_density_bins(rows, nsteps, nc, lo, up):
     return slots
 
 
+# ---- pair densities (include/mcx.h) ----
+DENSITY2D_F = 4096  # the fixed-point unit of a value's fraction between two nodes
+
+
+class Density2dSpec:
+    """an mcx_density2d_spec and the arrays it points to: g nodes per axis, pairs = None (every a < b) or [npairs, 2]
+    columns, the other fields as DensitySpec's"""
+
+    def __init__(self, g=64, pairs=None, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None):
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1))  # noqa: E731
+        ptr = lambda a: None if a is None else _dp(a)  # noqa: E731
+        self.g, self.bw, self.from_, self.to = int(g), arr(bw), arr(from_), arr(to)
+        self.pairs = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        self.c = Density2dSpecC(self.g, float(adjust), float(clip[0]), float(clip[1]), ptr(self.bw), ptr(self.from_), ptr(self.to),
+                                0 if self.pairs is None else self.pairs.shape[0],
+                                None if self.pairs is None else self.pairs.ctypes.data_as(C.POINTER(C.c_int)))
+
+    def fits(self, ncol):
+        for a in (self.bw, self.from_, self.to):
+            if a is not None and a.size != ncol:
+                raise ValueError("bw, from_ and to take one entry per column (%d), NaN for a column's default" % ncol)
+        return self
+
+    def npairs(self, ncol):
+        return ncol * (ncol - 1) // 2 if self.pairs is None else self.pairs.shape[0]
+
+
+def _density2d_call(fn, spec, ncol):
+    """fn(spec, cols, axes, pairs_out, z) -> the dict of a pair density call"""
+    g = min(max(spec.g, 1), 64)  # (a refused g or list of pairs still gets buffers)
+    npairs = min(max(spec.npairs(ncol), 1), 1024)
+    cols, axes = np.zeros(ncol, DENSITY_DTYPE), np.zeros((ncol, g))
+    po, z = np.zeros(npairs, PAIR_DENSITY_DTYPE), np.zeros((npairs, g, g))
+    check(fn(C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), _dp(axes), po.ctypes.data_as(C.c_void_p), _dp(z)))
+    out = {name: cols[name].copy() for name in DENSITY_DTYPE.names if name not in ("nbinned", "flags")}
+    out["col_flags"] = cols["flags"].copy()
+    out["axes"], out["z"] = axes, z
+    out["pairs"] = np.stack([po["a"], po["b"]], axis=1)
+    out["nbinned"], out["flags"] = po["nbinned"].copy(), po["flags"].copy()
+    return out
+
+
+def rows_density2d(rows, nsteps, nc, g=64, pairs=None, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None):
+    """mcx_rows_density2d: Engine.density2d's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    spec = Density2dSpec(g, pairs, adjust, clip, bw, from_, to).fits(ncol)
+    return _density2d_call(lambda *a: load().mcx_rows_density2d(_fp(rows), nsteps, nc, ncol - 1, *a), spec, ncol)
+
+
+def debug_density2d_grid(N, mean, sd, min_, max_, q25, q75, qclip=(np.nan, np.nan), is_last_col=False, col=0, spec=None):
+    """mcx_debug_density2d_grid (host only): the record (DENSITY_DTYPE) of one column from its statistics"""
+    spec = spec or Density2dSpec()
+    out = np.zeros(1, DENSITY_DTYPE)
+    check(load().mcx_debug_density2d_grid(int(N), mean, sd, min_, max_, q25, q75, qclip[0], qclip[1], int(bool(is_last_col)), col,
+                                          C.byref(spec.c), out.ctypes.data_as(C.c_void_p)))
+    return out[0]
+
+
+def debug_density2d_finish(col_a, col_b, slots, g, b_first=False):
+    """mcx_debug_density2d_finish (host only): z [g, g] of one pair from its two records and slots [(g + 1)^2, 4] uint64 =
+    (cnt, Sa, Sb, Sab); b_first: the order of the sums of a pair a > b"""
+    rec = np.zeros(2, DENSITY_DTYPE)
+    rec[0], rec[1] = col_a, col_b
+    sl = np.ascontiguousarray(slots, np.uint64).reshape(-1, 4)
+    if not 1 <= g <= 64 or sl.shape[0] != (g + 1) ** 2:
+        raise ValueError("slots must be [(g + 1)^2, 4]")
+    z = np.zeros((g, g))
+    check(load().mcx_debug_density2d_finish(rec[0:1].ctypes.data_as(C.c_void_p), rec[1:2].ctypes.data_as(C.c_void_p), g,
+                                            sl.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(bool(b_first)), _dp(z)))
+    return z
+
+
+def debug_rows_density2d_bins(rows, nsteps, nc, lo, up, g, pairs=None):
+    """mcx_debug_rows_density2d_bins: the code, pair and reduce sweeps alone over rows [nsteps * nc, np + 1] on the grids lo
+    [np + 1] < up [np + 1] -- slots [npairs, (g + 1)^2, 4] uint64 = (cnt, Sa, Sb, Sab)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    lo = np.ascontiguousarray(np.asarray(lo, np.float64).reshape(-1))
+    up = np.ascontiguousarray(np.asarray(up, np.float64).reshape(-1))
+    if lo.size != ncol or up.size != ncol:
+        raise ValueError("lo and up take one entry per column")
+    spec = Density2dSpec(g, pairs)
+    slots = np.zeros((min(max(spec.npairs(ncol), 1), 1024), (min(max(g, 1), 64) + 1) ** 2, 4), np.uint64)
+    check(load().mcx_debug_rows_density2d_bins(_fp(rows), nsteps, nc, ncol - 1, _dp(lo), _dp(up), g, spec.c.npairs, spec.c.pairs,
+                                               slots.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+    return slots
+
+
 # ---- derived columns and bootstrap draws (include/mcx.h, DESIGN.md section 12) ----
 class DeriveSpec:
     """an mcx_derive and the arrays it points to"""
@@ -457,6 +549,12 @@ class DerivedStore:
         cols, x, y = _density_out(ncol, n)
         check(load().mcx_store_density(self.h, C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), _dp(x), _dp(y)))
         return _density_dict(cols, x, y)
+
+    def density2d(self, g=64, pairs=None, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None):
+        """Engine.density2d's dict for the derived columns, then log L"""
+        ncol = self.shape[2]
+        spec = Density2dSpec(g, pairs, adjust, clip, bw, from_, to).fits(ncol)
+        return _density2d_call(lambda *a: load().mcx_store_density2d(self.h, *a), spec, ncol)
 
     def density_times(self, n=512, adjust=1.0, clip=(0, 1)):
         """mcx_debug_store_density_times: Engine.density_times' four stage times for this store"""
@@ -1049,6 +1147,23 @@ class Engine:
         spec = DensitySpec(n, adjust, clip)
         ms = np.zeros(4)
         self._on_store(load().mcx_debug_density_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
+        return ms
+
+    def density2d(self, g=64, pairs=None, adjust=1.0, clip=(0, 1), bw=None, from_=None, to=None, first_step=0, nsteps=None):
+        """mcx_samples_density2d, the corner plot: per pair of columns (pairs [npairs, 2]; None: every a < b) of kept steps
+        [first_step, first_step + nsteps) the joint kernel density estimate of MASS::kde2d / geom_density_2d on g x g nodes --
+        a dict of the column arrays [np + 1] bw, from, to, lo, up, mean, sd, nvalues, col_flags; axes [np + 1, g]; pairs
+        [npairs, 2], nbinned and flags [npairs]; z [npairs, g, g], z[p, j, k] the density at (axes[a, j], axes[b, k])"""
+        spec = Density2dSpec(g, pairs, adjust, clip, bw, from_, to).fits(self.np + 1)
+        return _density2d_call(lambda *a: self._on_store(load().mcx_samples_density2d, first_step, nsteps, *a) or 0, spec,
+                               self.np + 1)
+
+    def density2d_times(self, g=64, pairs=None, adjust=1.0, clip=(0, 1), first_step=0, nsteps=None):
+        """mcx_debug_density2d_times: ms of (the statistics passes, k_density2d_codes, k_density2d_pairs, k_density2d_reduce,
+        the host grids and finish, the whole call) of one density2d() call"""
+        spec = Density2dSpec(g, pairs, adjust, clip)
+        ms = np.zeros(6)
+        self._on_store(load().mcx_debug_density2d_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
         return ms
 
     def clip(self, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, first_step=0, nsteps=None, count_only=False):
