@@ -698,6 +698,93 @@ typedef struct mcx_store_geometry {
 } mcx_store_geometry;
 int mcx_debug_store_geometry(int np, int nout, int nsteps, int nc, mcx_store_geometry *g);
 
+/* ---- the per-chain table of the sample store, and stores of chosen chains, on the device ----
+ * The one analysis whose unit is the chain: what every chain of a step range did, a rule that names the chains to drop, and a
+ * store of the chains that stay, for every analysis above.  The source is a step range of an engine's store, host rows in
+ * MCout layout, or a derived store: T = nsteps >= 1 steps of nc chains (indices local to the shard) and ncol = np + 1 columns
+ * (the parameters or derived columns, then log L).
+ *   per (chain, column) series x_0 .. x_{T-1}, fp64 throughout, centred (two passes):
+ *     mean       = the sum over the steps / T
+ *     sd         = sqrt(sum c_i^2 / (T - 1)), c_i = x_i - mean; NaN at T = 1
+ *     rho1       = sum_{i < T-1} c_i c_{i+1} / sum_i c_i^2, the lag-1 autocorrelation; NaN when T < 2 or the series is constant
+ *     a series holding an inf or NaN has NaN in all three
+ *   per chain:
+ *     moves         the steps t in [1, T) whose row differs from step t - 1's in the bits of any of its ncol floats (-0 and +0
+ *                   differ, one NaN pattern equals itself, a change in log L alone is a move)
+ *     longest_stay  the steps of the longest run of bit-identical consecutive rows: 1 when no row repeats, T when none moved
+ *     ll_max, ll_max_step   the largest log L in float order (-inf < finite < +inf, -0 before +0) and the first step of the
+ *                   range, counted from 0, that holds it; NaN and -1 when the chain's log L holds a NaN
+ *     flags         MCX_SUMMARY_NONFINITE when any series of the chain holds an inf or NaN
+ * Every number has one writer and a fixed order of operations: the same source and arguments give the same bytes. */
+typedef struct mcx_chain_col { double mean, sd, rho1; } mcx_chain_col;
+typedef struct mcx_chain_row {
+  long long moves, longest_stay;
+  float ll_max;
+  int ll_max_step;
+  int flags;            /* MCX_SUMMARY_* */
+} mcx_chain_row;
+/* Steps [first_step, first_step + nsteps) of the engine's store, nsteps >= 1; cols[nc][np + 1], chains[nc].  MCX_ERR_INVALID
+ * for a NULL cols or chains (checked before a device is touched) and in the cases mcx_samples_summary refuses (the store
+ * does not hold the range).  A queued MCX_OPT_ASYNC_RUN run is finished first. */
+int mcx_samples_chain_table(mcx_engine *e, int first_step, int nsteps, mcx_chain_col *cols, mcx_chain_row *chains);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows), and for a derived store */
+int mcx_rows_chain_table(const float *rows, int nsteps, int nc, int np, mcx_chain_col *cols, mcx_chain_row *chains);
+int mcx_store_chain_table(mcx_store *s, mcx_chain_col *cols, mcx_chain_row *chains);
+
+/* host only, no device: which chains of a table to keep.  Per column that takes part, over the chains whose mean of that
+ * column is finite: med = the median of the chain means (the mean of the two middle values of an even count), mad = the
+ * median of |mean - med|, scale = 1.4826 mad.
+ *   MCX_CHAIN_NONFINITE  flags has MCX_SUMMARY_NONFINITE (or a mean of the chain is not finite); such a chain gets this alone
+ *   MCX_CHAIN_STUCK      moves < min_moves, or max_stay > 0 and longest_stay > max_stay
+ *   MCX_CHAIN_OUTLIER    |mean - med| > z scale in a column that takes part: strict, so scale = 0 names exactly the chains
+ *                        whose mean differs from med; z = +inf: no outlier test
+ * reasons[nc], 0 = kept; centre[ncol][2] = (med, scale), NaN for a column that takes no part (may be NULL); *nkept = the
+ * chains kept.  MCX_ERR_INVALID for nc or ncol < 1, a NULL cols, chains, rule, reasons or nkept, and z <= 0 or NaN.  The
+ * product path (mcpar-run --chain-keep, the Python binding's keep_chains) calls this very function. */
+enum { MCX_CHAIN_NONFINITE = 1, MCX_CHAIN_STUCK = 2, MCX_CHAIN_OUTLIER = 4 };
+typedef struct mcx_chain_rule {
+  double z;                      /* > 0 and finite, or +inf: no outlier test */
+  long long min_moves, max_stay; /* STUCK when moves < min_moves, or max_stay > 0 && longest_stay > max_stay */
+  const unsigned char *use_col;  /* NULL = every column; else [ncol], non-zero = the column takes part in the outlier test */
+} mcx_chain_rule;
+int mcx_chains_keep(int nc, int ncol, const mcx_chain_col *cols, const mcx_chain_row *chains, const mcx_chain_rule *rule,
+                    int *reasons, double *centre, int *nkept);
+
+/* A store of chosen chains: out[t][k][:] = in[t][chains[k]][:] for the T steps of the range, log L likewise -- nsel >= 1
+ * chains in any order and with repeats (chains resampled with replacement are the bootstrap of an ensemble), nsel may exceed
+ * nc.  The result is an ordinary mcx_store of T steps of nsel chains and the same columns: it owns its memory and a stream,
+ * outlives its source, and every analysis above works on it.  These are real chains: its R-hat and ESS mean what they say.
+ * MCX_ERR_INVALID, before a device is touched and with nothing allocated, for a NULL chains or out, nsel < 1 and an index
+ * outside [0, nc), the entry named in mcx_last_error; MCX_ERR_UNSUPPORTED for more elements than one grid copies (2^31 - 1
+ * workgroups of 256 quads or floats).  The same source and arguments give the same bytes. */
+int mcx_samples_select_chains(mcx_engine *e, int first_step, int nsteps, const int *chains, int nsel, mcx_store **out);
+int mcx_rows_select_chains(const float *rows, int nsteps, int nc, int np, const int *chains, int nsel, mcx_store **out);
+int mcx_store_select_chains(mcx_store *s, const int *chains, int nsel, mcx_store **out);
+
+/* host only, no device: the launch geometry of the three sweeps of this section for a store of nsteps steps of nc chains of np
+ * parameters and a selection of nsel chains, every field from the function the launch code itself uses.  MCX_ERR_INVALID for
+ * np outside 1..256, nsteps, nc or nsel < 1, or g NULL. */
+typedef struct mcx_chains_geometry {
+  long long block;                 /* threads per workgroup of the three sweeps: 256 */
+  long long lds_bytes;             /* of each: 0, every sweep works in registers */
+  long long series_tile_cols;      /* series sweep: adjacent parameter columns per tile, min(np, 16) */
+  long long series_tile_chains;    /* chains per tile, 256 / series_tile_cols */
+  long long series_col_tiles;      /* ceil(np / series_tile_cols) */
+  long long series_workgroups;     /* of the parameter columns: series_col_tiles * ceil(nc / series_tile_chains) */
+  long long series_ll_workgroups;  /* of log L, one lane per chain: ceil(nc / 256) */
+  long long rows_lanes_per_chain;  /* row sweep: min(64, the power of two >= np + 1) */
+  long long rows_values_per_lane;  /* ceil((np + 1) / rows_lanes_per_chain): 1 to 5 */
+  long long rows_chains_per_workgroup; /* 256 / rows_lanes_per_chain */
+  long long rows_workgroups;
+  long long select_vec4;           /* the gather's path when its bases are 16-byte aligned: 1 = 16 bytes per lane (np % 4 == 0), 0 = 4 */
+  long long select_items;          /* one per lane: the quads or floats of x', then the nsteps * nsel values of log L */
+  long long select_workgroups;
+} mcx_chains_geometry;
+int mcx_debug_chains_geometry(int np, int nsteps, int nc, int nsel, mcx_chains_geometry *g);
+/* one mcx_samples_chain_table call, its results let go: ms[0] the series sweep, ms[1] the row sweep (HIP events), ms[2] the
+ * whole call (wall clock) */
+int mcx_debug_chain_table_times(mcx_engine *e, int first_step, int nsteps, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

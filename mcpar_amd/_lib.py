@@ -55,6 +55,20 @@ class StoreGeometry(C.Structure):
                                             "rank_tiles", "rank_step_chunk", "rank_grid_y", "gather_chunk_rows")]
 
 
+class ChainRule(C.Structure):
+    """include/mcx.h mcx_chain_rule"""
+    _fields_ = [("z", C.c_double), ("min_moves", C.c_longlong), ("max_stay", C.c_longlong),
+                ("use_col", C.POINTER(C.c_ubyte))]
+
+
+class ChainsGeometry(C.Structure):
+    """include/mcx.h mcx_chains_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "lds_bytes", "series_tile_cols", "series_tile_chains", "series_col_tiles",
+                                            "series_workgroups", "series_ll_workgroups", "rows_lanes_per_chain",
+                                            "rows_values_per_lane", "rows_chains_per_workgroup", "rows_workgroups",
+                                            "select_vec4", "select_items", "select_workgroups")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -184,6 +198,15 @@ def load():
         "mcx_debug_clip_thresholds": [C.c_int, dp, C.POINTER(ClipSpecC), dp, dp],
         "mcx_debug_clip_times": [vp, C.c_int, C.c_int, C.POINTER(ClipSpecC), dp],
         "mcx_debug_store_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(StoreGeometry)],
+        "mcx_samples_chain_table": [vp, C.c_int, C.c_int, vp, vp],
+        "mcx_rows_chain_table": [fp, C.c_int, C.c_int, C.c_int, vp, vp],
+        "mcx_store_chain_table": [vp, vp, vp],
+        "mcx_chains_keep": [C.c_int, C.c_int, vp, vp, C.POINTER(ChainRule), C.POINTER(C.c_int), dp, C.POINTER(C.c_int)],
+        "mcx_samples_select_chains": [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)],
+        "mcx_rows_select_chains": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)],
+        "mcx_store_select_chains": [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)],
+        "mcx_debug_chains_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ChainsGeometry)],
+        "mcx_debug_chain_table_times": [vp, C.c_int, C.c_int, dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

@@ -10,6 +10,7 @@
 //             [--density FILE] [--derived-density FILE] [--density-n N] [--density-clip QLO,QHI]
 //             [--density2d FILE] [--derived-density2d FILE] [--density2d-n G] [--density2d-pairs a:b,c:d,...]
 //             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
+//             [--chain-table FILE] [--chain-keep Z[,MINMOVES[,MAXSTAY]]] [--kept-chains FILE] [--kept-summary FILE]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -48,6 +49,11 @@
 // the kept rows as the text of the sample output.  --clipped-density FILE [--clip-nc NC]: the file of --density for the kept
 // rows, as many whole steps of NC (default 1024) pseudo-chains as they fill (mcx_rowset_store); the report's last line
 // names the rows that leaves out.  All under the conditions of --summary.
+// --chain-table FILE: what every chain did, on the GPU (mcx_rows_chain_table): a header, then one line per chain: its index,
+// moves, longest_stay, ll_max, ll_max_step, flags, then mean sd rho1 per column p0 .. LL.  --chain-keep Z[,MINMOVES[,MAXSTAY]]
+// (default 5,1,0): the rule of mcx_chains_keep over every column.  --kept-chains FILE: a header, one line `chain reasons` per
+// chain (0 = kept, else 1 non-finite | 2 stuck | 4 outlier), then `kept K of NC`.  --kept-summary FILE: the file of --summary
+// for the store of the kept chains (mcx_rows_select_chains, mcx_store_summary).  All under the conditions of --summary.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -349,6 +355,88 @@ static int write_clip(const mcx_clip_spec &spec, const char *report_path, const 
   return rc;
 }
 
+// --chain-table / --kept-chains / --kept-summary: the chain table of MCout's rows, the rule's verdict on every chain and the
+// summary of the store of the chains it keeps
+static int write_chains(const mcx_chain_rule &rule, const char *table_path, const char *kept_path, const char *sum_path, MCout &rows,
+                        int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--chain-*: " << rows.size() << " rows stored, a chain table needs nsamp * nc of them\n";
+    return 1;
+  }
+  const int ncol = np + 1;
+  std::vector<mcx_chain_col> cols((size_t)nc * ncol);
+  std::vector<mcx_chain_row> chains((size_t)nc);
+  if (mcx_rows_chain_table(rows.getpset(0), nsamp, nc, np, cols.data(), chains.data()) != MCX_OK) {
+    std::cerr << "--chain-table: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  if (table_path) {
+    FILE *f = fopen(table_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << table_path << "\n";
+      return 1;
+    }
+    fprintf(f, "chain moves longest_stay ll_max ll_max_step flags");
+    for (int c = 0; c < ncol; ++c) {
+      const std::string n = colname('p', c, np);
+      fprintf(f, " %s_mean %s_sd %s_rho1", n.c_str(), n.c_str(), n.c_str());
+    }
+    fprintf(f, "\n");
+    for (int k = 0; k < nc; ++k) {
+      const mcx_chain_row &r = chains[k];
+      fprintf(f, "%d %lld %lld %.9g %d %d", k, r.moves, r.longest_stay, (double)r.ll_max, r.ll_max_step, r.flags);
+      for (int c = 0; c < ncol; ++c) {
+        const mcx_chain_col &s = cols[(size_t)k * ncol + c];
+        fprintf(f, " %.17g %.17g %.17g", s.mean, s.sd, s.rho1);
+      }
+      fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) return 1;
+  }
+  if (!kept_path && !sum_path) return 0;
+  std::vector<int> reasons((size_t)nc), kept;
+  int nkept = 0;
+  if (mcx_chains_keep(nc, ncol, cols.data(), chains.data(), &rule, reasons.data(), 0, &nkept) != MCX_OK) {
+    std::cerr << "--chain-keep: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  for (int k = 0; k < nc; ++k)
+    if (reasons[k] == 0) kept.push_back(k);
+  if (kept_path) {
+    FILE *f = fopen(kept_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << kept_path << "\n";
+      return 1;
+    }
+    fprintf(f, "chain reasons\n");
+    for (int k = 0; k < nc; ++k) fprintf(f, "%d %d\n", k, reasons[k]);
+    fprintf(f, "kept %d of %d\n", nkept, nc);
+    if (fclose(f) != 0) return 1;
+  }
+  if (sum_path) {
+    if (nkept < 1 || nsamp < 4) {
+      std::cerr << "--kept-summary: " << nkept << " chains kept over " << nsamp << " steps, a summary needs a chain and nsamp >= 4\n";
+      return 1;
+    }
+    mcx_store *st = 0;
+    if (mcx_rows_select_chains(rows.getpset(0), nsamp, nc, np, kept.data(), nkept, &st) != MCX_OK) {
+      std::cerr << "--kept-summary: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    std::vector<mcx_col_summary> sc((size_t)ncol);
+    std::vector<double> q((size_t)ncol * 3);
+    int rc = 0;
+    if (mcx_store_summary(st, SUMMARY_PROBS, 3, sc.data(), q.data()) != MCX_OK) {
+      std::cerr << "--kept-summary: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_summary(sum_path, sc, q, np, 'p');
+    mcx_store_destroy(st);
+    return rc;
+  }
+  return 0;
+}
+
 // --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
 static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
                          const mcx_density_spec &dspec, const char *dens2d_path, const mcx_density2d_spec &d2spec, MCout &rows, int nsamp,
@@ -514,6 +602,8 @@ int main(int argc, char *argv[])
   std::string density_file, derived_density_file, clip_report_file, clipped_file, clipped_density_file;
   mcx_clip_spec clip_spec = {0.01, 0.99, 0.0, 0, 0};
   int clip_nc = 1024;
+  std::string chain_table_file, kept_chains_file, kept_summary_file;
+  mcx_chain_rule chain_rule = {5.0, 1, 0, 0};
   mcx_density_spec density_spec = {512, 1.0, 0.0, 1.0, 0, 0, 0};
   std::string density2d_file, derived_density2d_file;
   mcx_density2d_spec density2d_spec = {64, 1.0, 0.0, 1.0, 0, 0, 0, 0, 0};
@@ -593,6 +683,15 @@ int main(int argc, char *argv[])
     else if (a == "--clipped") clipped_file = val();
     else if (a == "--clipped-density") clipped_density_file = val();
     else if (a == "--clip-nc") clip_nc = atoi(val());
+    else if (a == "--chain-table") chain_table_file = val();
+    else if (a == "--chain-keep") {
+      if (sscanf(val(), "%lf,%lld,%lld", &chain_rule.z, &chain_rule.min_moves, &chain_rule.max_stay) < 1) {
+        std::cerr << "--chain-keep takes Z[,MINMOVES[,MAXSTAY]]\n";
+        return 2;
+      }
+    }
+    else if (a == "--kept-chains") kept_chains_file = val();
+    else if (a == "--kept-summary") kept_summary_file = val();
     else if (a == "--draws") draws_file = val();
     else if (a == "--ndraw") ndraw = atoll(val());
     else if (a == "--draw-seed") draw_seed = (unsigned)strtoul(val(), 0, 10);
@@ -647,6 +746,14 @@ int main(int argc, char *argv[])
   if (want_clip && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--clip-report, --clipped and --clipped-density need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  const bool want_chains = !chain_table_file.empty() || !kept_chains_file.empty() || !kept_summary_file.empty();
+  if (want_chains && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--chain-table, --kept-chains and --kept-summary need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -771,6 +878,12 @@ int main(int argc, char *argv[])
                               clipped_file.empty() ? 0 : clipped_file.c_str(),
                               clipped_density_file.empty() ? 0 : clipped_density_file.c_str(), clip_nc, density_spec, rslts, nsamp, nc,
                               np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_chains && write_chains(chain_rule, chain_table_file.empty() ? 0 : chain_table_file.c_str(),
+                                  kept_chains_file.empty() ? 0 : kept_chains_file.c_str(),
+                                  kept_summary_file.empty() ? 0 : kept_summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

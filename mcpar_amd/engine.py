@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ClipSpecC, Counters, Density2dSpecC, DensitySpecC, Derive, PlanItem,
-                   Profile, StoreGeometry, VLFunc, check, load)
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, Counters, Density2dSpecC,
+                   DensitySpecC, Derive, PlanItem, Profile, StoreGeometry, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -53,6 +53,12 @@ assert CLIP_DTYPE.itemsize == 40
 # include/mcx.h mcx_pair_density
 PAIR_DENSITY_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("nbinned", np.int64), ("flags", np.int32)], align=True)
 assert PAIR_DENSITY_DTYPE.itemsize == 24
+# include/mcx.h mcx_chain_col, mcx_chain_row
+CHAIN_COL_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("rho1", np.float64)], align=True)
+CHAIN_ROW_DTYPE = np.dtype([("moves", np.int64), ("longest_stay", np.int64), ("ll_max", np.float32), ("ll_max_step", np.int32),
+                            ("flags", np.int32)], align=True)
+assert CHAIN_COL_DTYPE.itemsize == 24 and CHAIN_ROW_DTYPE.itemsize == 32
+CHAIN_NONFINITE, CHAIN_STUCK, CHAIN_OUTLIER = 1, 2, 4  # mcx_chains_keep's reasons
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
@@ -576,6 +582,15 @@ class DerivedStore:
         spec = ClipSpec(qlo, qhi, ll_hi, lo, hi).fits(ncol)
         return _clip_call(lambda *a: load().mcx_store_clip(self.h, *a), spec, ncol, t * nc, count_only)
 
+    def chain_table(self):
+        """Engine.chain_table's dict for the chains of this store"""
+        _, nc, ncol = self.shape
+        return _chain_table_call(lambda *a: load().mcx_store_chain_table(self.h, *a), nc, ncol)
+
+    def select_chains(self, chains):
+        """Engine.select_chains' DerivedStore of chains (any order, repeats allowed) of this store"""
+        return _select_call(lambda *a: load().mcx_store_select_chains(self.h, *a), chains)
+
 
 def derive_rows(rows, nsteps, nc, spec):
     """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
@@ -683,6 +698,71 @@ def debug_clip_thresholds(q, qlo=0.01, qhi=0.99, ll_hi=0.0, lo=None, hi=None, sp
     tl, th = np.zeros(max(ncol, 1)), np.zeros(max(ncol, 1))
     check(load().mcx_debug_clip_thresholds(ncol, _dp(q), C.byref(spec.c), _dp(tl), _dp(th)))
     return tl[:ncol], th[:ncol]
+
+
+# ---- the chain table and stores of chosen chains (include/mcx.h) ----
+def _chain_table_call(fn, nc, ncol):
+    """fn(cols, chains) of one of the three table entry points -> the dict of arrays: mean, sd, rho1 [nc, ncol]; moves,
+    longest_stay, ll_max, ll_max_step, flags [nc]"""
+    cols, rows = np.zeros((nc, ncol), CHAIN_COL_DTYPE), np.zeros(nc, CHAIN_ROW_DTYPE)
+    check(fn(cols.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+    out = {name: cols[name].copy() for name in CHAIN_COL_DTYPE.names}
+    out.update({name: rows[name].copy() for name in CHAIN_ROW_DTYPE.names})
+    return out
+
+
+def rows_chain_table(rows, nsteps, nc):
+    """mcx_rows_chain_table: Engine.chain_table's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    return _chain_table_call(lambda *a: load().mcx_rows_chain_table(_fp(rows), nsteps, nc, ncol - 1, *a), nc, ncol)
+
+
+def keep_chains(table, z=5.0, min_moves=1, max_stay=0, use_col=None):
+    """mcx_chains_keep (host only) on a chain_table dict: (reasons [nc] int32 -- 0 = kept, else CHAIN_NONFINITE | CHAIN_STUCK |
+    CHAIN_OUTLIER --, centre [ncol, 2] = (median, 1.4826 MAD) of the chain means per column that takes part, kept_indices
+    int32).  use_col: None = every column, else [ncol], non-zero = the column takes part in the outlier test"""
+    mean = np.asarray(table["mean"], np.float64)
+    nc, ncol = mean.shape
+    cols, rows = np.zeros((nc, ncol), CHAIN_COL_DTYPE), np.zeros(nc, CHAIN_ROW_DTYPE)
+    for name in CHAIN_COL_DTYPE.names:
+        cols[name] = table[name]
+    for name in CHAIN_ROW_DTYPE.names:
+        rows[name] = table[name]
+    use = None
+    if use_col is not None:
+        use = np.ascontiguousarray(np.asarray(use_col).reshape(-1) != 0, np.uint8)
+        if use.size != ncol:
+            raise ValueError("use_col takes one entry per column (%d)" % ncol)
+    rule = ChainRule(float(z), int(min_moves), int(max_stay), None if use is None else use.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    reasons, centre, nkept = np.zeros(nc, np.int32), np.zeros((ncol, 2)), C.c_int(0)
+    check(load().mcx_chains_keep(nc, ncol, cols.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), C.byref(rule),
+                                 reasons.ctypes.data_as(C.POINTER(C.c_int)), _dp(centre), C.byref(nkept)))
+    kept = np.flatnonzero(reasons == 0).astype(np.int32)
+    assert kept.size == nkept.value
+    return reasons, centre, kept
+
+
+def _select_call(fn, chains):
+    """fn(chains, nsel, out) of one of the three selection entry points -> DerivedStore"""
+    sel = np.ascontiguousarray(np.asarray(chains).reshape(-1), np.int32)
+    h = C.c_void_p()
+    check(fn(sel.ctypes.data_as(C.POINTER(C.c_int)), sel.size, C.byref(h)))
+    return DerivedStore(h)
+
+
+def select_chains_rows(rows, nsteps, nc, chains):
+    """mcx_rows_select_chains: Engine.select_chains' DerivedStore for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    return _select_call(lambda *a: load().mcx_rows_select_chains(_fp(rows), nsteps, nc, rows.shape[1] - 1, *a), chains)
+
+
+def debug_chains_geometry(np_, nsteps, nc, nsel=1):
+    """mcx_debug_chains_geometry (host only): the launch geometry of the series, row and gather sweeps for a store of nsteps
+    steps of nc chains of np_ parameters and a selection of nsel chains, as a dict of include/mcx.h's fields"""
+    g = ChainsGeometry()
+    check(load().mcx_debug_chains_geometry(np_, nsteps, nc, nsel, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in ChainsGeometry._fields_}
 
 
 def debug_store_geometry(np_, nout, nsteps, nc):
@@ -1186,6 +1266,32 @@ class Engine:
         ms = np.zeros(5)
         self._on_store(load().mcx_debug_clip_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
         return ms
+
+    def _nsteps(self, first_step, nsteps):
+        if nsteps is None:
+            ns = C.c_int(0)
+            check(load().mcx_samples_steps(self.h, C.byref(ns)))
+            nsteps = ns.value - first_step
+        return nsteps
+
+    def chain_table(self, first_step=0, nsteps=None):
+        """mcx_samples_chain_table: what every chain did over kept steps [first_step, first_step + nsteps) -- a dict of
+        arrays: mean, sd, rho1 [nc, np + 1] per (chain, column) series (the parameters, then log L); moves, longest_stay,
+        ll_max, ll_max_step, flags [nc] per chain"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _chain_table_call(lambda *a: load().mcx_samples_chain_table(self.h, first_step, nsteps, *a), self.nc, self.np + 1)
+
+    def chain_table_times(self, first_step=0, nsteps=None):
+        """mcx_debug_chain_table_times: ms of (the series sweep, the row sweep, the whole call) of one chain_table() call"""
+        ms = np.zeros(3)
+        self._on_store(load().mcx_debug_chain_table_times, first_step, nsteps, _dp(ms))
+        return ms
+
+    def select_chains(self, chains, first_step=0, nsteps=None):
+        """mcx_samples_select_chains: the DerivedStore of chains (any order, repeats allowed; e.g. keep_chains' kept_indices)
+        over kept steps [first_step, first_step + nsteps): real chains, for every analysis of a store"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _select_call(lambda *a: load().mcx_samples_select_chains(self.h, first_step, nsteps, *a), chains)
 
     def derive(self, spec, first_step=0, nsteps=None):
         """mcx_samples_derive: the DerivedStore of spec (derive_linear / derive_source) applied to every row of kept steps
