@@ -785,6 +785,112 @@ int mcx_debug_chains_geometry(int np, int nsteps, int nc, int nsel, mcx_chains_g
  * whole call (wall clock) */
 int mcx_debug_chain_table_times(mcx_engine *e, int first_step, int nsteps, double *ms);
 
+/* ---- the per-step table of the sample store on the device, and where the ensemble settled ----
+ * The one analysis whose unit is the step: what the ensemble of nc chains looked like at every kept step, and a rule that
+ * names the step from which it no longer drifts.  The source is a step range of an engine's store, host rows in MCout layout,
+ * or a derived store (of mcx_*_derive, mcx_rowset_store or mcx_*_select_chains): T = nsteps >= 1 steps of nc >= 1 chains
+ * (indices local to the shard) and ncol = np + 1 columns (the parameters or derived columns, then log L).
+ *   per (step t, column c), over the nc values x_0 .. x_{nc-1} of that step: cols[t * ncol + c]
+ *     mean       = the sum over the chains / nc, fp64
+ *     sd         = sqrt(sum (x_i - mean)^2 / (nc - 1)), fp64, centred (a second pass); NaN at nc = 1
+ *     min, max   exact, in float order (-inf < finite < +inf; -0 before +0)
+ *     quantiles  q[(t * ncol + c) * nprobs + k], R type 7 / numpy "linear" from exact order statistics with N = nc:
+ *                h = (nc - 1) p_k, lo = floor(h), g = h - lo; x(lo) when g = 0 or x(lo) = x(lo+1), else
+ *                x(lo) + g (x(lo+1) - x(lo)), fp64
+ *     a NaN among the nc values makes min, max and every quantile NaN (a NaN, payload unspecified); an inf or NaN among them
+ *     (the fp64 sum is not finite) sets flags = MCX_SUMMARY_NONFINITE and makes mean and sd NaN
+ *   per step t: steps[t]
+ *     moved         the chains whose row at step t differs from their row at step t - 1 in the bits of any of its ncol floats
+ *                   (-0 and +0 differ, one NaN pattern equals itself, a change in log L alone counts): the realised acceptance
+ *                   count of the step; -1 for the first step of the range
+ *     ll_max, ll_max_chain   the largest log L of the step in float order and the lowest chain index that holds it; NaN and
+ *                   -1 when the step's log L holds a NaN
+ *     flags         MCX_SUMMARY_NONFINITE when any column of the step has it
+ * No float atomics; every float sum is a fixed slot and a fixed-order tree; counts are integers: the same source and
+ * arguments give the same bytes. */
+enum { MCX_STEP_MAX_PROBS = 8 };
+typedef struct mcx_step_col {
+  double mean, sd;
+  float min, max;
+  int flags;            /* MCX_SUMMARY_* */
+  int reserved;         /* 0 */
+} mcx_step_col;
+typedef struct mcx_step_row {
+  int moved;            /* -1 for the first step of the range */
+  float ll_max;
+  int ll_max_chain;
+  int flags;            /* MCX_SUMMARY_* */
+} mcx_step_row;
+/* Steps [first_step, first_step + nsteps) of the engine's store, nsteps >= 1.  cols[nsteps * (np + 1)], steps[nsteps],
+ * quantiles[nsteps * (np + 1) * nprobs] (may be NULL only when nprobs == 0); probs[nprobs] in [0, 1], 0 <= nprobs <=
+ * MCX_STEP_MAX_PROBS.  MCX_ERR_INVALID, before a device is touched and with nothing allocated, for a NULL cols or steps, a
+ * NULL probs or quantiles with nprobs > 0, nsteps < 1, nprobs outside [0, 8] and a p that is NaN or outside [0, 1], the entry
+ * named in mcx_last_error; and in the cases mcx_samples_summary refuses (the store does not hold the range).
+ * MCX_ERR_UNSUPPORTED for more (step, column tile) pairs than one grid holds (2^31 - 1).  A queued MCX_OPT_ASYNC_RUN run is
+ * finished first. */
+int mcx_samples_step_table(mcx_engine *e, int first_step, int nsteps, const double *probs, int nprobs, mcx_step_col *cols,
+                           mcx_step_row *steps, double *quantiles);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows), and for a derived store */
+int mcx_rows_step_table(const float *rows, int nsteps, int nc, int np, const double *probs, int nprobs, mcx_step_col *cols,
+                        mcx_step_row *steps, double *quantiles);
+int mcx_store_step_table(mcx_store *s, const double *probs, int nprobs, mcx_step_col *cols, mcx_step_row *steps, double *quantiles);
+
+/* host only, no device: from which step on the ensemble of a step table no longer drifts.  The reference window is the last
+ * R = max(1, ceil(ref_frac T)) steps of the T = nsteps of the table.  Per column that takes part, fp64, summed in step order:
+ *   m_ref = the mean of the window's step means; s_ref = sqrt(the mean of the window's sd^2)
+ * Step t is in band when, for every column that takes part, |mean_t - m_ref| <= tol_mean s_ref and |sd_t - s_ref| <= tol_sd
+ * s_ref; a step with a non-finite mean or sd in such a column is out of band.
+ *   out_cols[ncol]: m_ref, s_ref; last_out = the last step out of band in that column alone, -1 if none; max_dev_mean =
+ *     max_t |mean_t - m_ref| / s_ref and max_dev_sd = max_t |sd_t - s_ref| / s_ref over the steps whose mean and sd are
+ *     finite, NaN when s_ref is 0 or not finite; a column that takes no part has NaN in the four doubles and last_out = -1
+ *   *settled_step = 1 + the last out-of-band step; 0 when every step is in band; -1, not settled, when that step lies inside
+ *     the reference window (1 + it > T - R), or when a column that takes part has s_ref = 0 or not finite -- a table of one
+ *     chain, whose every sd is NaN, is such a table
+ * MCX_ERR_INVALID for nsteps or ncol < 1, a NULL cols, rule, out_cols or settled_step, a tol_mean or tol_sd that is negative
+ * or NaN, a ref_frac outside (0, 1] or NaN, and a use_col that names no column.  The product path (mcpar-run --settle, the
+ * Python binding's settle_steps) calls this very function. */
+typedef struct mcx_step_rule {
+  double tol_mean, tol_sd;       /* in units of s_ref; the defaults of the driver and the binding: 0.1, 0.1 */
+  double ref_frac;               /* the share of the steps, from the end, that make the reference window; default 0.5 */
+  const unsigned char *use_col;  /* NULL = every column; else [ncol], non-zero = the column takes part */
+} mcx_step_rule;
+typedef struct mcx_step_settle_col {
+  double m_ref, s_ref, max_dev_mean, max_dev_sd;
+  int last_out;
+  int reserved;                  /* 0 */
+} mcx_step_settle_col;
+int mcx_steps_settle(int nsteps, int ncol, const mcx_step_col *cols, const mcx_step_rule *rule, mcx_step_settle_col *out_cols,
+                     int *settled_step);
+
+/* host only, no device: the launch geometry of the three sweeps of this section for a table of nsteps steps of nc chains of np
+ * parameters and nprobs probabilities, every field from the function the launch code itself uses.  MCX_ERR_INVALID for np
+ * outside 1..256, nsteps or nc < 1, nprobs outside [0, 8], or g NULL. */
+typedef struct mcx_steptable_geometry {
+  long long block;                  /* threads per workgroup of the three sweeps: 256 */
+  long long moments_tile_cols;      /* moments sweep: adjacent parameter columns per tile, min(np, 16) */
+  long long moments_stride_chains;  /* chains one stride of such a tile covers, 256 / moments_tile_cols (log L: 256) */
+  long long moments_col_tiles;      /* ceil(np / moments_tile_cols), and one more tile for log L */
+  long long moments_workgroups;     /* nsteps * (moments_col_tiles + 1) */
+  long long moments_lds_bytes;
+  long long select_slots;           /* histograms per column: the target ranks, 2 nprobs */
+  long long select_tile_cols;       /* select sweep: min(np, 16, 63 / select_slots); 0 when nprobs = 0 (no launch) */
+  long long select_stride_chains;   /* 256 / select_tile_cols */
+  long long select_col_tiles;       /* ceil(np / select_tile_cols), and one more tile for log L */
+  long long select_workgroups;      /* nsteps * (select_col_tiles + 1); 0 when nprobs = 0 */
+  long long select_lds_bytes;       /* select_tile_cols * select_slots KiB of bins and 1 KiB of state: at most 64 KiB */
+  long long rows_lanes_per_chain;   /* row sweep: section 16's grouping, min(64, the power of two >= np + 1) */
+  long long rows_values_per_lane;   /* ceil((np + 1) / rows_lanes_per_chain): 1 to 5 */
+  long long rows_chains_per_pass;   /* 256 / rows_lanes_per_chain */
+  long long rows_chunks;            /* workgroups per step: min(32, ceil(nc / rows_chains_per_pass)) */
+  long long rows_workgroups;        /* nsteps * rows_chunks */
+  long long scratch_doubles;        /* nsteps * (np + 1) * (4 + nprobs) */
+  long long scratch_words;          /* nsteps * 2 * (rows_chunks + 1) */
+} mcx_steptable_geometry;
+int mcx_debug_steptable_geometry(int np, int nsteps, int nc, int nprobs, mcx_steptable_geometry *g);
+/* one mcx_samples_step_table call, its results let go: ms[0] the moments sweep, ms[1] the select sweep, ms[2] the row sweep and
+ * its reducer (HIP events), ms[3] the whole call (wall clock) */
+int mcx_debug_step_table_times(mcx_engine *e, int first_step, int nsteps, const double *probs, int nprobs, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -69,6 +69,20 @@ class ChainsGeometry(C.Structure):
                                             "select_vec4", "select_items", "select_workgroups")]
 
 
+class StepRule(C.Structure):
+    """include/mcx.h mcx_step_rule"""
+    _fields_ = [("tol_mean", C.c_double), ("tol_sd", C.c_double), ("ref_frac", C.c_double), ("use_col", C.POINTER(C.c_ubyte))]
+
+
+class SteptableGeometry(C.Structure):
+    """include/mcx.h mcx_steptable_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "moments_tile_cols", "moments_stride_chains", "moments_col_tiles",
+                                            "moments_workgroups", "moments_lds_bytes", "select_slots", "select_tile_cols",
+                                            "select_stride_chains", "select_col_tiles", "select_workgroups", "select_lds_bytes",
+                                            "rows_lanes_per_chain", "rows_values_per_lane", "rows_chains_per_pass", "rows_chunks",
+                                            "rows_workgroups", "scratch_doubles", "scratch_words")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -207,6 +221,12 @@ def load():
         "mcx_store_select_chains": [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)],
         "mcx_debug_chains_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ChainsGeometry)],
         "mcx_debug_chain_table_times": [vp, C.c_int, C.c_int, dp],
+        "mcx_samples_step_table": [vp, C.c_int, C.c_int, dp, C.c_int, vp, vp, dp],
+        "mcx_rows_step_table": [fp, C.c_int, C.c_int, C.c_int, dp, C.c_int, vp, vp, dp],
+        "mcx_store_step_table": [vp, dp, C.c_int, vp, vp, dp],
+        "mcx_steps_settle": [C.c_int, C.c_int, vp, C.POINTER(StepRule), vp, C.POINTER(C.c_int)],
+        "mcx_debug_steptable_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SteptableGeometry)],
+        "mcx_debug_step_table_times": [vp, C.c_int, C.c_int, dp, C.c_int, dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

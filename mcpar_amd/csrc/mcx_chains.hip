@@ -155,22 +155,8 @@ template <bool VEC4> __global__ void __launch_bounds__(SB) k_chain_select(const 
   else a.xo[i] = a.x[src * (uint64_t)a.np + q];
 }
 
-// ---- launch geometry: what the launches below use and mcx_debug_chains_geometry reports
-struct RowsGeometry {
-  int lg, G, V, cpw;  // G = 1 << lg lanes per chain, V values per lane, cpw chains per workgroup
-  unsigned nwg;
-};
-RowsGeometry rows_geometry(int np, int nc)
-{
-  RowsGeometry g;
-  g.lg = 0;
-  while (g.lg < 6 && (1 << g.lg) < np + 1) ++g.lg;
-  g.G = 1 << g.lg;
-  g.V = (np + g.G) / g.G;  // ceil((np + 1) / G)
-  g.cpw = SB >> g.lg;
-  g.nwg = (unsigned)(((int64_t)nc + g.cpw - 1) / g.cpw);
-  return g;
-}
+// ---- launch geometry: what the launches below use and mcx_debug_chains_geometry reports (rows_geometry: the row sweep's
+// grouping, in mcx_summary_kernels.hpp, which the step table's row sweep shares)
 struct SelectGeometry {
   bool vec4;  // when the bases are 16-byte aligned
   int ipr;

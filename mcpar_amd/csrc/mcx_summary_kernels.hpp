@@ -161,6 +161,25 @@ inline TileSet tiles_l(const float *ly, int nc, int np)
   return t;
 }
 
+// The grouping of a row sweep (mcx_chains.hip's k_chain_rows, mcx_steptable.hip's k_step_rows): G = 1 << lg lanes per chain,
+// G = min(64, the power of two >= np + 1), lane j holding columns j, j + G, ... in V = ceil((np + 1) / G) <= 5 values; cpw chains
+// per workgroup and nwg = ceil(nc / cpw) workgroups when each takes its chains once
+struct RowsGeometry {
+  int lg, G, V, cpw;
+  unsigned nwg;
+};
+inline RowsGeometry rows_geometry(int np, int nc)
+{
+  RowsGeometry g;
+  g.lg = 0;
+  while (g.lg < 6 && (1 << g.lg) < np + 1) ++g.lg;
+  g.G = 1 << g.lg;
+  g.V = (np + g.G) / g.G;  // ceil((np + 1) / G)
+  g.cpw = SB >> g.lg;
+  g.nwg = (unsigned)(((int64_t)nc + g.cpw - 1) / g.cpw);
+  return g;
+}
+
 // a step range of a store with everything the passes derive from it, formed once
 struct StoreView : StoreSpan {
   int ncol;         // np + 1 columns: the parameters, then log L

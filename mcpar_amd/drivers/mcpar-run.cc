@@ -11,6 +11,7 @@
 //             [--density2d FILE] [--derived-density2d FILE] [--density2d-n G] [--density2d-pairs a:b,c:d,...]
 //             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
 //             [--chain-table FILE] [--chain-keep Z[,MINMOVES[,MAXSTAY]]] [--kept-chains FILE] [--kept-summary FILE]
+//             [--step-table FILE [--step-probs p1,p2,...] [--settle TOLM[,TOLS[,REF]]]]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -54,6 +55,12 @@
 // (default 5,1,0): the rule of mcx_chains_keep over every column.  --kept-chains FILE: a header, one line `chain reasons` per
 // chain (0 = kept, else 1 non-finite | 2 stuck | 4 outlier), then `kept K of NC`.  --kept-summary FILE: the file of --summary
 // for the store of the kept chains (mcx_rows_select_chains, mcx_store_summary).  All under the conditions of --summary.
+// --step-table FILE: what the ensemble looked like at every kept step, on the GPU (mcx_rows_step_table), in long form: a header
+// `step column mean sd min q<p>... max`, then one line per (step, column p0 .. LL); a header `step moved ll_max ll_max_chain`,
+// then one line per step.  The step column is the iteration the reference's mcparam.itercount puts back on every row.
+// --step-probs p1,p2,... (default 0.05,0.5,0.95; up to 8): the quantiles' probabilities.  --settle TOLM[,TOLS[,REF]] (default
+// 0.1,0.1,0.5): the rule of mcx_steps_settle over every column: a line `settled at step S of T` or `not settled`, a header
+// `column m_ref s_ref last_out max_dev_mean max_dev_sd` and one line per column.  Under the conditions of --summary.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -437,6 +444,55 @@ static int write_chains(const mcx_chain_rule &rule, const char *table_path, cons
   return 0;
 }
 
+// --step-table [--settle]: the step table of MCout's rows and the rule's verdict on it
+static int write_steps(const char *path, const std::vector<double> &probs, const mcx_step_rule *rule, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--step-table: " << rows.size() << " rows stored, a step table needs nsamp * nc of them\n";
+    return 1;
+  }
+  const int ncol = np + 1, nprobs = (int)probs.size();
+  std::vector<mcx_step_col> cols((size_t)nsamp * ncol);
+  std::vector<mcx_step_row> steps((size_t)nsamp);
+  std::vector<double> q(cols.size() * probs.size() + 1);
+  if (mcx_rows_step_table(rows.getpset(0), nsamp, nc, np, probs.data(), nprobs, cols.data(), steps.data(), q.data()) != MCX_OK) {
+    std::cerr << "--step-table: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  std::vector<mcx_step_settle_col> sc((size_t)ncol);
+  int settled = -1;
+  if (rule && mcx_steps_settle(nsamp, ncol, cols.data(), rule, sc.data(), &settled) != MCX_OK) {
+    std::cerr << "--settle: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "step column mean sd min");
+  for (double p : probs) fprintf(f, " q%g", p);
+  fprintf(f, " max\n");
+  for (int t = 0; t < nsamp; ++t)
+    for (int c = 0; c < ncol; ++c) {
+      const size_t i = (size_t)t * ncol + c;
+      fprintf(f, "%d %s %.17g %.17g %.9g", t, colname('p', c, np).c_str(), cols[i].mean, cols[i].sd, (double)cols[i].min);
+      for (int k = 0; k < nprobs; ++k) fprintf(f, " %.17g", q[i * nprobs + k]);
+      fprintf(f, " %.9g\n", (double)cols[i].max);
+    }
+  fprintf(f, "step moved ll_max ll_max_chain\n");
+  for (int t = 0; t < nsamp; ++t) fprintf(f, "%d %d %.9g %d\n", t, steps[t].moved, (double)steps[t].ll_max, steps[t].ll_max_chain);
+  if (rule) {
+    if (settled >= 0) fprintf(f, "settled at step %d of %d\n", settled, nsamp);
+    else fprintf(f, "not settled\n");
+    fprintf(f, "column m_ref s_ref last_out max_dev_mean max_dev_sd\n");
+    for (int c = 0; c < ncol; ++c)
+      fprintf(f, "%s %.17g %.17g %d %.17g %.17g\n", colname('p', c, np).c_str(), sc[c].m_ref, sc[c].s_ref, sc[c].last_out,
+              sc[c].max_dev_mean, sc[c].max_dev_sd);
+  }
+  return fclose(f) == 0 ? 0 : 1;
+}
+
 // --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
 static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
                          const mcx_density_spec &dspec, const char *dens2d_path, const mcx_density2d_spec &d2spec, MCout &rows, int nsamp,
@@ -604,6 +660,10 @@ int main(int argc, char *argv[])
   int clip_nc = 1024;
   std::string chain_table_file, kept_chains_file, kept_summary_file;
   mcx_chain_rule chain_rule = {5.0, 1, 0, 0};
+  std::string step_table_file;
+  std::vector<double> step_probs = {0.05, 0.5, 0.95};
+  mcx_step_rule step_rule = {0.1, 0.1, 0.5, 0};
+  bool settle = false;
   mcx_density_spec density_spec = {512, 1.0, 0.0, 1.0, 0, 0, 0};
   std::string density2d_file, derived_density2d_file;
   mcx_density2d_spec density2d_spec = {64, 1.0, 0.0, 1.0, 0, 0, 0, 0, 0};
@@ -691,6 +751,19 @@ int main(int argc, char *argv[])
       }
     }
     else if (a == "--kept-chains") kept_chains_file = val();
+    else if (a == "--step-table") step_table_file = val();
+    else if (a == "--step-probs") {
+      step_probs.clear();
+      std::stringstream ss(val());
+      for (std::string tok; std::getline(ss, tok, ',');) step_probs.push_back(atof(tok.c_str()));
+    }
+    else if (a == "--settle") {
+      settle = true;
+      if (sscanf(val(), "%lf,%lf,%lf", &step_rule.tol_mean, &step_rule.tol_sd, &step_rule.ref_frac) < 1) {
+        std::cerr << "--settle takes TOLM[,TOLS[,REF]]\n";
+        return 2;
+      }
+    }
     else if (a == "--kept-summary") kept_summary_file = val();
     else if (a == "--draws") draws_file = val();
     else if (a == "--ndraw") ndraw = atoll(val());
@@ -754,6 +827,18 @@ int main(int argc, char *argv[])
   if (want_chains && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--chain-table, --kept-chains and --kept-summary need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (settle && step_table_file.empty()) {
+    if (rank == 0) std::cerr << "--settle writes into the file of --step-table: give one\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!step_table_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--step-table needs the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -884,6 +969,10 @@ int main(int argc, char *argv[])
   if (want_chains && write_chains(chain_rule, chain_table_file.empty() ? 0 : chain_table_file.c_str(),
                                   kept_chains_file.empty() ? 0 : kept_chains_file.c_str(),
                                   kept_summary_file.empty() ? 0 : kept_summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (!step_table_file.empty() && write_steps(step_table_file.c_str(), step_probs, settle ? &step_rule : 0, rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

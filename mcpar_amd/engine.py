@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, Counters, Density2dSpecC,
-                   DensitySpecC, Derive, PlanItem, Profile, StoreGeometry, VLFunc, check, load)
+                   DensitySpecC, Derive, PlanItem, Profile, StepRule, SteptableGeometry, StoreGeometry, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -59,6 +59,13 @@ CHAIN_ROW_DTYPE = np.dtype([("moves", np.int64), ("longest_stay", np.int64), ("l
                             ("flags", np.int32)], align=True)
 assert CHAIN_COL_DTYPE.itemsize == 24 and CHAIN_ROW_DTYPE.itemsize == 32
 CHAIN_NONFINITE, CHAIN_STUCK, CHAIN_OUTLIER = 1, 2, 4  # mcx_chains_keep's reasons
+STEP_COL_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("min", np.float32), ("max", np.float32), ("flags", np.int32),
+                           ("reserved", np.int32)], align=True)
+STEP_ROW_DTYPE = np.dtype([("moved", np.int32), ("ll_max", np.float32), ("ll_max_chain", np.int32), ("flags", np.int32)], align=True)
+STEP_SETTLE_DTYPE = np.dtype([("m_ref", np.float64), ("s_ref", np.float64), ("max_dev_mean", np.float64), ("max_dev_sd", np.float64),
+                              ("last_out", np.int32), ("reserved", np.int32)], align=True)
+assert STEP_COL_DTYPE.itemsize == 32 and STEP_ROW_DTYPE.itemsize == 16 and STEP_SETTLE_DTYPE.itemsize == 40
+STEP_MAX_PROBS = 8  # include/mcx.h MCX_STEP_MAX_PROBS
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
@@ -591,6 +598,11 @@ class DerivedStore:
         """Engine.select_chains' DerivedStore of chains (any order, repeats allowed) of this store"""
         return _select_call(lambda *a: load().mcx_store_select_chains(self.h, *a), chains)
 
+    def step_table(self, probs=(0.05, 0.5, 0.95)):
+        """Engine.step_table's dict for the steps of this store"""
+        t, _, ncol = self.shape
+        return _step_table_call(lambda *a: load().mcx_store_step_table(self.h, *a), t, ncol, probs)
+
 
 def derive_rows(rows, nsteps, nc, spec):
     """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
@@ -763,6 +775,60 @@ def debug_chains_geometry(np_, nsteps, nc, nsel=1):
     g = ChainsGeometry()
     check(load().mcx_debug_chains_geometry(np_, nsteps, nc, nsel, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in ChainsGeometry._fields_}
+
+
+# ---- the step table and where the ensemble settled (include/mcx.h) ----
+def _step_table_call(fn, nsteps, ncol, probs):
+    """fn(probs, nprobs, cols, steps, quantiles) of one of the three table entry points -> the dict of arrays: mean, sd, min,
+    max, flags [T, ncol]; quantiles [T, ncol, nprobs]; moved, ll_max, ll_max_chain, step_flags [T]"""
+    p, pp = _probs(probs)
+    T = max(int(nsteps), 0)
+    cols, rows = np.zeros((T, ncol), STEP_COL_DTYPE), np.zeros(T, STEP_ROW_DTYPE)
+    q = np.zeros((T, ncol, len(p)), np.float64)
+    check(fn(pp if len(p) else None, len(p), cols.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+             _dp(q) if len(p) else None))
+    out = {name: cols[name].copy() for name in ("mean", "sd", "min", "max", "flags")}
+    out["quantiles"] = q
+    out.update({name: rows[name].copy() for name in ("moved", "ll_max", "ll_max_chain")})
+    out["step_flags"] = rows["flags"].copy()
+    return out
+
+
+def rows_step_table(rows, nsteps, nc, probs=(0.05, 0.5, 0.95)):
+    """mcx_rows_step_table: Engine.step_table's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    return _step_table_call(lambda *a: load().mcx_rows_step_table(_fp(rows), nsteps, nc, ncol - 1, *a), nsteps, ncol, probs)
+
+
+def settle_steps(table, tol_mean=0.1, tol_sd=0.1, ref_frac=0.5, use_col=None):
+    """mcx_steps_settle (host only) on a step_table dict: (settled_step, per-column dict).  settled_step = 1 + the last step
+    whose mean or sd of a column that takes part lies outside the band around the last ceil(ref_frac T) steps' (m_ref, s_ref);
+    0 when every step is in band; -1 = not settled.  The dict holds m_ref, s_ref, max_dev_mean, max_dev_sd (in units of s_ref)
+    and last_out [ncol].  use_col: None = every column, else [ncol], non-zero = the column takes part"""
+    mean = np.asarray(table["mean"], np.float64)
+    T, ncol = mean.shape
+    cols = np.zeros((T, ncol), STEP_COL_DTYPE)
+    for name in ("mean", "sd", "min", "max", "flags"):
+        cols[name] = table[name]
+    use = None
+    if use_col is not None:
+        use = np.ascontiguousarray(np.asarray(use_col).reshape(-1) != 0, np.uint8)
+        if use.size != ncol:
+            raise ValueError("use_col takes one entry per column (%d)" % ncol)
+    rule = StepRule(float(tol_mean), float(tol_sd), float(ref_frac), None if use is None else use.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    out, settled = np.zeros(ncol, STEP_SETTLE_DTYPE), C.c_int(0)
+    check(load().mcx_steps_settle(T, ncol, cols.ctypes.data_as(C.c_void_p), C.byref(rule), out.ctypes.data_as(C.c_void_p),
+                                  C.byref(settled)))
+    return settled.value, {name: out[name].copy() for name in ("m_ref", "s_ref", "max_dev_mean", "max_dev_sd", "last_out")}
+
+
+def debug_steptable_geometry(np_, nsteps, nc, nprobs=3):
+    """mcx_debug_steptable_geometry (host only): the launch geometry of the moments, select and row sweeps for a table of
+    nsteps steps of nc chains of np_ parameters and nprobs probabilities, as a dict of include/mcx.h's fields"""
+    g = SteptableGeometry()
+    check(load().mcx_debug_steptable_geometry(np_, nsteps, nc, nprobs, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in SteptableGeometry._fields_}
 
 
 def debug_store_geometry(np_, nout, nsteps, nc):
@@ -1285,6 +1351,22 @@ class Engine:
         """mcx_debug_chain_table_times: ms of (the series sweep, the row sweep, the whole call) of one chain_table() call"""
         ms = np.zeros(3)
         self._on_store(load().mcx_debug_chain_table_times, first_step, nsteps, _dp(ms))
+        return ms
+
+    def step_table(self, first_step=0, nsteps=None, probs=(0.05, 0.5, 0.95)):
+        """mcx_samples_step_table: what the ensemble looked like at every kept step of [first_step, first_step + nsteps) -- a
+        dict of arrays: mean, sd, min, max, flags [T, np + 1] per (step, column) over the nc chains (the parameters, then log
+        L); quantiles [T, np + 1, nprobs]; moved (the chains whose row changed from the step before, -1 for the first step),
+        ll_max, ll_max_chain, step_flags [T] per step"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _step_table_call(lambda *a: load().mcx_samples_step_table(self.h, first_step, nsteps, *a), nsteps, self.np + 1, probs)
+
+    def step_table_times(self, first_step=0, nsteps=None, probs=(0.05, 0.5, 0.95)):
+        """mcx_debug_step_table_times: ms of (the moments sweep, the select sweep, the row sweep and its reducer, the whole
+        call) of one step_table() call"""
+        p, pp = _probs(probs)
+        ms = np.zeros(4)
+        self._on_store(load().mcx_debug_step_table_times, first_step, nsteps, pp if len(p) else None, len(p), _dp(ms))
         return ms
 
     def select_chains(self, chains, first_step=0, nsteps=None):
