@@ -891,6 +891,60 @@ int mcx_debug_steptable_geometry(int np, int nsteps, int nc, int nprobs, mcx_ste
  * its reducer (HIP events), ms[3] the whole call (wall clock) */
 int mcx_debug_step_table_times(mcx_engine *e, int first_step, int nsteps, const double *probs, int nprobs, double *ms);
 
+/* ---- sample text read back, on the device ---------------------------
+ * The reference's read.mc.data (src/anly/mcpar-analysis.R: read.table(filename)) for the text MCout::output prints
+ * (src/mcout.cc:41-45), which mcx_samples_text, mcx_format_rows and the reference's own drivers write: lines of ncol numbers.
+ *   token      a maximal run of bytes other than blank, tab, \r and \n:
+ *              [+-]? ( D+ ( . D* )? | . D+ ) ( [eE] [+-]? D+ )?,  or  [+-]? inf | infinity | nan  in any letter case.
+ *              Nothing else is a number: hex floats, NA, 1e, nan(...) are refused.
+ *   value      the bits of glibc's strtof in the "C" locale: correctly rounded, ties to even, +-inf above the range, +-0
+ *              below 2^-150, denormals between, -0 kept; a nan token gives a NaN of unspecified sign and payload.  Converted on
+ *              the device, in integer arithmetic, for every token of at most 40 bytes and 19 digits from its first non-zero
+ *              one on; any other token of the grammar is converted by strtof on the host and counted in nfallback.
+ *   lines      end with \n (\r\n is accepted; the last line needs none); a line of separators only is skipped and not
+ *              counted as a row; every other line must hold exactly ncol tokens.
+ *   rows       row r of the text is (step r / nc, chain r % nc): the order of mcx_samples_text.  The result is an ordinary
+ *              mcx_store of ncol - 1 columns, then the last column as log L, T = nrows / nc: every mcx_store_* and
+ *              mcx_rowset_* entry point works on it.
+ *   pieces     the text goes to the device in pieces of at most piece_bytes bytes, each cut behind the last line end that
+ *              fits (the rest of the text, if it fits, is the last piece); the result does not depend on piece_bytes.
+ * MCX_ERR_INVALID, nothing left allocated and *out NULL: a NULL argument; ncol outside 2..257; nc < 1; a line with another
+ * number of tokens ("line L: K fields, expected ncol": L counts from 1 in the whole text, skipped and empty lines included; of
+ * several wrong lines the first is named, and its field count before its tokens); a token outside the grammar ("line L, field
+ * F"); no rows, or a number of rows that is no multiple of nc; a line longer than a piece.  MCX_ERR_ALLOC, with the bytes
+ * needed in mcx_last_error: the store (4 bytes per number, for as many rows as the text has lines) and three piece_bytes of
+ * text and token offsets do not fit.  The same text and arguments give the same bytes. */
+#define MCX_TEXT_FALLBACK_CAPACITY 1024 /* tokens of one piece the device hands to the host one by one; a piece with more of them
+                                           is tokenised on the host (same result, same nfallback) */
+typedef struct mcx_text_spec {
+  int ncol;            /* columns per line; 0: the token count of the first kept line that has any */
+  int nc;              /* chains: rows must be a multiple; step-major then chain, the order of mcx_samples_text */
+  int64_t skip_lines;  /* leading lines ignored, whatever they hold (read.table's skip): "nsamp = ..." of the reference's drivers */
+  int64_t max_rows;    /* < 0: to the end; else stop after that many rows (read.table's nrows): trailing "max likelihood" lines */
+  size_t piece_bytes;  /* 0: default (32 MiB); 64 to 2^30; must hold the longest line with its line end */
+} mcx_text_spec;
+typedef struct mcx_text_report {
+  int64_t nrows;       /* rows stored */
+  int64_t nlines;      /* lines read, the skipped and the empty ones included (with max_rows: to the end of the last piece read) */
+  int64_t ntokens;     /* nrows * ncol */
+  int64_t nfallback;   /* tokens converted by strtof on the host */
+  int64_t npieces;
+  int ncol;
+} mcx_text_report;
+int mcx_text_store(const char *text, size_t nbytes, const mcx_text_spec *spec, mcx_store **out, mcx_text_report *rep);
+/* the rows on the host, MCout layout rows[nrows][ncol]; MCX_ERR_INVALID when capacity_rows < nrows.  rows == NULL: the report only */
+int mcx_text_rows(const char *text, size_t nbytes, const mcx_text_spec *spec, float *rows, int64_t capacity_rows,
+                  mcx_text_report *rep);
+/* the same of a file, read in pieces (once to count its lines, once to parse): the file need not fit host memory */
+int mcx_file_store(const char *path, const mcx_text_spec *spec, mcx_store **out, mcx_text_report *rep);
+/* host only, no device: one token through parse_g.hpp as compiled into the library.  *status = 0 converted, 1 not a number,
+ * 2 of the grammar but left to the host: *bits is then strtof's, as in the store */
+int mcx_debug_parse_token(const char *tok, size_t len, uint32_t *bits, int *status);
+/* mcx_text_store with its stages timed, for tools/parse_bench.py; the store is let go.  ms[8]: the upload, the mark sweep, the
+ * scan, the scatter of the token starts, the parse sweep (HIP events, summed over the pieces), the host's line count, its
+ * staging of the pieces in pinned memory, the whole call (wall clock) */
+int mcx_debug_text_times(const char *text, size_t nbytes, const mcx_text_spec *spec, mcx_text_report *rep, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -83,6 +83,16 @@ class SteptableGeometry(C.Structure):
                                             "rows_workgroups", "scratch_doubles", "scratch_words")]
 
 
+class TextSpec(C.Structure):
+    """include/mcx.h mcx_text_spec"""
+    _fields_ = [("ncol", C.c_int), ("nc", C.c_int), ("skip_lines", C.c_int64), ("max_rows", C.c_int64), ("piece_bytes", C.c_size_t)]
+
+
+class TextReport(C.Structure):
+    """include/mcx.h mcx_text_report"""
+    _fields_ = [(n, C.c_int64) for n in ("nrows", "nlines", "ntokens", "nfallback", "npieces")] + [("ncol", C.c_int)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -227,6 +237,11 @@ def load():
         "mcx_steps_settle": [C.c_int, C.c_int, vp, C.POINTER(StepRule), vp, C.POINTER(C.c_int)],
         "mcx_debug_steptable_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SteptableGeometry)],
         "mcx_debug_step_table_times": [vp, C.c_int, C.c_int, dp, C.c_int, dp],
+        "mcx_text_store": [C.c_char_p, C.c_size_t, C.POINTER(TextSpec), C.POINTER(vp), C.POINTER(TextReport)],
+        "mcx_text_rows": [C.c_char_p, C.c_size_t, C.POINTER(TextSpec), fp, C.c_int64, C.POINTER(TextReport)],
+        "mcx_file_store": [C.c_char_p, C.POINTER(TextSpec), C.POINTER(vp), C.POINTER(TextReport)],
+        "mcx_debug_parse_token": [C.c_char_p, C.c_size_t, u32p, C.POINTER(C.c_int)],
+        "mcx_debug_text_times": [C.c_char_p, C.c_size_t, C.POINTER(TextSpec), C.POINTER(TextReport), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

@@ -12,6 +12,7 @@
 //             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
 //             [--chain-table FILE] [--chain-keep Z[,MINMOVES[,MAXSTAY]]] [--kept-chains FILE] [--kept-summary FILE]
 //             [--step-table FILE [--step-probs p1,p2,...] [--settle TOLM[,TOLS[,REF]]]]
+//   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
 // Output: the reference's row format (src/mcout.cc:41-45); --iter prepends the iteration index
@@ -61,6 +62,11 @@
 // --step-probs p1,p2,... (default 0.05,0.5,0.95; up to 8): the quantiles' probabilities.  --settle TOLM[,TOLS[,REF]] (default
 // 0.1,0.1,0.5): the rule of mcx_steps_settle over every column: a line `settled at step S of T` or `not settled`, a header
 // `column m_ref s_ref last_out max_dev_mean max_dev_sd` and one line per column.  Under the conditions of --summary.
+// --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
+// the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
+// one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
+// --np NP: FILE has NP + 1 columns (default: those of its first line); --read-skip K: leading lines to ignore (read.table's
+// skip), --read-rows N: rows to stop after (nrows).  Not with --func, --func-source, --nsamp, --nburn, --out or --stream-text.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -672,17 +678,25 @@ int main(int argc, char *argv[])
   int derive_nout = 0;
   long long ndraw = 0;
   unsigned draw_seed = 8675309u;
+  std::string read_file, run_only;  // run_only: the first option given that only a run takes
+  bool np_given = false, nc_given = false;
+  long long read_skip = 0, read_rows = -1;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : "0"; };
+    if (run_only.empty() && (a == "--func" || a == "--func-source" || a == "--nsamp" || a == "--nburn" || a == "--out" || a == "--stream-text"))
+      run_only = a;
     if (a == "--func") func = val();
     else if (a == "--func-source") func_source = val();
     else if (a == "--par") {
       std::stringstream ss(val());
       for (std::string tok; std::getline(ss, tok, ',');) user_par.push_back((float)atof(tok.c_str()));
     }
-    else if (a == "--np") np = atoi(val());
-    else if (a == "--nc") nc = atoi(val());
+    else if (a == "--np") { np = atoi(val()); np_given = true; }
+    else if (a == "--nc") { nc = atoi(val()); nc_given = true; }
+    else if (a == "--read") read_file = val();
+    else if (a == "--read-skip") read_skip = atoll(val());
+    else if (a == "--read-rows") read_rows = atoll(val());
     else if (a == "--nsamp") nsamp = atoi(val());
     else if (a == "--nburn") nburn = atoi(val());
     else if (a == "--pl") pl = (float)atof(val());
@@ -780,6 +794,19 @@ int main(int argc, char *argv[])
   int size, rank;
   MPI_Comm_size(MPI_COMM_WORLD, &size);
   MPI_Comm_rank(MPI_COMM_WORLD, &rank);
+  if (!read_file.empty() && (!run_only.empty() || !nc_given || size > 1)) {
+    if (rank == 0) {
+      if (!run_only.empty()) std::cerr << "--read parses a file, there is no run: not with " << run_only << "\n";
+      else std::cerr << "--read needs --nc, the chains of the run that wrote the file, and a single rank\n";
+    }
+    MPI_Finalize();
+    return 2;
+  }
+  if (read_file.empty() && (read_skip != 0 || read_rows != -1)) {
+    if (rank == 0) std::cerr << "--read-skip and --read-rows belong to --read FILE\n";
+    MPI_Finalize();
+    return 2;
+  }
   if (!summary_file.empty() && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--summary needs the rows on the host of a single rank: not with "
@@ -859,10 +886,37 @@ int main(int argc, char *argv[])
     return 2;
   }
 
+  // --read: the file's rows, parsed on the GPU, before MCout learns its width
+  std::vector<float> file_rows;
+  if (!read_file.empty()) {
+    mcx_text_spec tspec = {np_given ? np + 1 : 0, nc, read_skip, read_rows, 0};
+    mcx_text_report trep;
+    mcx_store *ts = 0;
+    if (mcx_file_store(read_file.c_str(), &tspec, &ts, &trep) != MCX_OK) {
+      std::cerr << "--read " << read_file << ": " << mcx_last_error() << "\n";
+      MPI_Finalize();
+      return 2;
+    }
+    np = trep.ncol - 1;
+    nsamp = (int)(trep.nrows / nc);
+    nburn = 0;
+    file_rows.resize((size_t)trep.nrows * (size_t)trep.ncol);
+    const int rc = mcx_store_copy(ts, 0, nsamp, file_rows.data());
+    mcx_store_destroy(ts);
+    if (rc != MCX_OK) {
+      std::cerr << "--read " << read_file << ": " << mcx_last_error() << "\n";
+      MPI_Finalize();
+      return 2;
+    }
+    std::cerr << "read " << trep.nrows << " rows of " << trep.ncol << " columns (" << nsamp << " steps of " << nc << " chains) from "
+              << trep.nlines << " lines in " << trep.npieces << " pieces, " << trep.nfallback << " tokens through strtof\n";
+  }
+
   VLFunc *L = 0;
   std::vector<float> means, w;
   try {
-    if (!func_source.empty()) {
+    if (!read_file.empty()) L = 0;  // (no run: no likelihood)
+    else if (!func_source.empty()) {
       FILE *f = fopen(func_source.c_str(), "rb");
       if (!f) { std::cerr << "cannot read " << func_source << "\n"; return 2; }
       std::string text;
@@ -904,11 +958,16 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
-  std::vector<float> pinit((size_t)nc * np);
-  for (int j = 0; j < nc; ++j)
+  if (!read_file.empty()) {
+    rslts.newsamps((int)(file_rows.size() / ((size_t)np + 1)));
+    rslts.add_rows(file_rows.data(), file_rows.size() / ((size_t)np + 1));
+    std::vector<float>().swap(file_rows);
+  }
+  std::vector<float> pinit(read_file.empty() ? (size_t)nc * np : 0);
+  for (int j = 0; j < nc && read_file.empty(); ++j)
     for (int i = 0; i < np; ++i)
       pinit[(size_t)j * np + i] = (float)(0.5 * std::sin(0.37 * ((double)(rank * nc + j) * np + i)));
-  try {
+  if (read_file.empty()) try {
     MCPar mcpar(np, nc, size, rank, pl, 0.2f, 0.5f, 0.2f, 1.5f, sync);
     auto t0 = std::chrono::steady_clock::now();
     mcpar.run(nsamp, nburn, pinit.data(), *L, rslts, incov.empty() ? 0 : incov.data());

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, Counters, Density2dSpecC,
-                   DensitySpecC, Derive, PlanItem, Profile, StepRule, SteptableGeometry, StoreGeometry, VLFunc, check, load)
+                   DensitySpecC, Derive, PlanItem, Profile, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -613,6 +613,63 @@ def derive_rows(rows, nsteps, nc, spec):
 
 
 # ---- tail-clipped rows (include/mcx.h) ----
+TEXT_FALLBACK_CAPACITY = 1024  # include/mcx.h MCX_TEXT_FALLBACK_CAPACITY
+PARSE_OK, PARSE_BAD, PARSE_NEEDS_HOST = 0, 1, 2  # mcx_debug_parse_token's status
+
+
+def _text_spec(nc, ncol, skip_lines, max_rows, piece_bytes):
+    return TextSpec(ncol, nc, skip_lines, max_rows, piece_bytes)
+
+
+def _text_report(rep):
+    return {n: getattr(rep, n) for n in ("nrows", "nlines", "ntokens", "nfallback", "npieces", "ncol")}
+
+
+def parse_text(text, nc, ncol=0, skip_lines=0, max_rows=-1, piece_bytes=0):
+    """mcx_text_rows: sample text (bytes: lines of ncol numbers, what MCout::output prints) parsed on the GPU ->
+    (rows [nrows, ncol] float32 in MCout layout, the report as a dict of include/mcx.h's fields)"""
+    text = bytes(text)
+    spec, rep = _text_spec(nc, ncol, skip_lines, max_rows, piece_bytes), TextReport()
+    if ncol == 0:  # the report first: it names the columns
+        check(load().mcx_text_rows(text, len(text), C.byref(spec), None, 0, C.byref(rep)))
+        ncol = rep.ncol
+    cap = text.count(b"\n") + 1  # (a row is a line)
+    rows = np.empty((cap, max(ncol, 1)), np.float32)
+    check(load().mcx_text_rows(text, len(text), C.byref(spec), _fp(rows), cap, C.byref(rep)))
+    return rows[:rep.nrows].copy(), _text_report(rep)
+
+
+def store_from_text(text, nc, ncol=0, skip_lines=0, max_rows=-1, piece_bytes=0):
+    """mcx_text_store: (DerivedStore of ncol - 1 columns, then the last column as log L, T = nrows / nc steps; the report)"""
+    text = bytes(text)
+    spec, rep, h = _text_spec(nc, ncol, skip_lines, max_rows, piece_bytes), TextReport(), C.c_void_p()
+    check(load().mcx_text_store(text, len(text), C.byref(spec), C.byref(h), C.byref(rep)))
+    return DerivedStore(h), _text_report(rep)
+
+
+def store_from_file(path, nc, ncol=0, skip_lines=0, max_rows=-1, piece_bytes=0):
+    """mcx_file_store: store_from_text of a file, read in pieces"""
+    spec, rep, h = _text_spec(nc, ncol, skip_lines, max_rows, piece_bytes), TextReport(), C.c_void_p()
+    check(load().mcx_file_store(str(path).encode(), C.byref(spec), C.byref(h), C.byref(rep)))
+    return DerivedStore(h), _text_report(rep)
+
+
+def debug_parse_token(tok):
+    """mcx_debug_parse_token (host only): one token (bytes or str) -> (float32 bit pattern, status PARSE_*)"""
+    tok = tok.encode() if isinstance(tok, str) else bytes(tok)
+    bits, status = C.c_uint32(0), C.c_int(0)
+    check(load().mcx_debug_parse_token(tok, len(tok), C.byref(bits), C.byref(status)))
+    return bits.value, status.value
+
+
+def debug_text_times(text, nc, ncol=0, piece_bytes=0):
+    """mcx_debug_text_times: (ms[8] = upload, mark, scan, scatter, parse, host line count, host staging, whole call; the report)"""
+    text = bytes(text)
+    spec, rep, ms = _text_spec(nc, ncol, 0, -1, piece_bytes), TextReport(), np.zeros(8)
+    check(load().mcx_debug_text_times(text, len(text), C.byref(spec), C.byref(rep), _dp(ms)))
+    return ms, _text_report(rep)
+
+
 class ClipSpec:
     """an mcx_clip_spec and the arrays it points to: the probabilities (qlo, qhi) of the default thresholds, ll_hi the upper
     threshold of log L (NaN: its qhi quantile; inf: none), lo / hi = None or [ncol] with NaN for a column's default"""
