@@ -698,6 +698,19 @@ typedef struct mcx_store_geometry {
 } mcx_store_geometry;
 int mcx_debug_store_geometry(int np, int nout, int nsteps, int nc, mcx_store_geometry *g);
 
+/* Two test hooks for the rule that no store analysis depends on what its scratch held before the call (DESIGN.md "Scratch and
+ * its history"; tests/test_gpu_scratch_history.py).
+ * mcx_debug_fill_allocations: host only, touches no device.  byte = -1 (off, the default) or 0..255: while on, every device
+ * allocation the library really makes (a buffer that is large enough is not allocated again) is filled with that byte before
+ * the allocating call goes on.  *nfilled (may be NULL): the allocations filled under the setting this call ends.  Process-wide.
+ * MCX_ERR_INVALID for any other byte; the setting then stays as it was.
+ * mcx_debug_fill_scratch: exactly one of e and s is not NULL; the three scratch buffers the analyses of that engine or store
+ * share (doubles, 64-bit words, 32-bit words) are filled with byte = 0..255 up to their present capacity, on the owner's stream,
+ * and the call waits for it.  bytes (may be NULL): the bytes filled per buffer, 0 for one that no analysis has allocated yet.
+ * MCX_ERR_INVALID, before any device is touched, for both or neither of e and s or a byte outside 0..255. */
+int mcx_debug_fill_allocations(int byte, unsigned long long *nfilled);
+int mcx_debug_fill_scratch(mcx_engine *e, mcx_store *s, int byte, size_t bytes[3]);
+
 /* ---- the per-chain table of the sample store, and stores of chosen chains, on the device ----
  * The one analysis whose unit is the chain: what every chain of a step range did, a rule that names the chains to drop, and a
  * store of the chains that stay, for every analysis above.  The source is a step range of an engine's store, host rows in

@@ -222,6 +222,8 @@ def load():
         "mcx_debug_clip_thresholds": [C.c_int, dp, C.POINTER(ClipSpecC), dp, dp],
         "mcx_debug_clip_times": [vp, C.c_int, C.c_int, C.POINTER(ClipSpecC), dp],
         "mcx_debug_store_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(StoreGeometry)],
+        "mcx_debug_fill_allocations": [C.c_int, C.POINTER(C.c_ulonglong)],
+        "mcx_debug_fill_scratch": [vp, vp, C.c_int, C.POINTER(C.c_size_t)],
         "mcx_samples_chain_table": [vp, C.c_int, C.c_int, vp, vp],
         "mcx_rows_chain_table": [fp, C.c_int, C.c_int, C.c_int, vp, vp],
         "mcx_store_chain_table": [vp, vp, vp],

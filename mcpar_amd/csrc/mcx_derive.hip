@@ -407,6 +407,36 @@ extern "C" int mcx_debug_store_geometry(int np, int nout, int nsteps, int nc, mc
   return MCX_OK;
 }
 
+// host only: DevBuf::alloc reads the setting (mcx_engine_internal.hpp)
+extern "C" int mcx_debug_fill_allocations(int byte, unsigned long long *nfilled)
+{
+  if (byte < -1 || byte > 255) return fail(MCX_ERR_INVALID, "byte = %d: -1 (off) or 0 to 255", byte);
+  g_alloc_fill.store(byte, std::memory_order_relaxed);
+  const unsigned long long n = g_alloc_filled.exchange(0, std::memory_order_relaxed);
+  if (nfilled) *nfilled = n;
+  return MCX_OK;
+}
+
+// the analyses' scratch of an engine (summ_d, summ_h, summ_u) or of a store (d, h, u), to its capacity, on the owner's stream
+extern "C" int mcx_debug_fill_scratch(mcx_engine *e, mcx_store *s, int byte, size_t bytes[3])
+{
+  if (!e == !s) return fail(MCX_ERR_INVALID, "exactly one of the engine e and the store s is given, not %s", e ? "both" : "neither");
+  if (byte < 0 || byte > 255) return fail(MCX_ERR_INVALID, "byte = %d: 0 to 255", byte);
+  if (e) MCXCHK(enter(e));
+  else MCXCHK(store_enter(s));
+  const hipStream_t st = e ? e->stream : (hipStream_t)s->st;
+  const Bufs B = e ? Bufs{&e->summ_d, &e->summ_h, &e->summ_u} : s->bufs();
+  void *const p[3] = {B.d->p, B.h->p, B.u->p};
+  const size_t nb[3] = {B.d->p ? B.d->n * sizeof(double) : 0, B.h->p ? B.h->n * sizeof(unsigned long long) : 0,
+                        B.u->p ? B.u->n * sizeof(uint32_t) : 0};
+  for (int k = 0; k < 3; ++k) {
+    if (nb[k]) HIPCHK(hipMemsetAsync(p[k], byte, nb[k], st));
+    if (bytes) bytes[k] = nb[k];
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return MCX_OK;
+}
+
 // the compile step alone (needs no GPU: hiprtc cross-compiles for gfx950)
 extern "C" int mcx_debug_derive_compile(const char *source, int np, int nout, size_t *code_bytes)
 {

@@ -107,6 +107,10 @@ enum { LIVE_DEVICE, LIVE_PINNED, LIVE_STREAMS, LIVE_EVENTS };
 inline std::atomic<uint64_t> g_live[4];
 static inline void live_add(int what) { g_live[what].fetch_add(1, std::memory_order_relaxed); }
 static inline void live_sub(int what) { g_live[what].fetch_sub(1, std::memory_order_relaxed); }
+// mcx_debug_fill_allocations (mcx_derive.hip; DESIGN.md "Scratch and its history"): -1, or the byte every new device
+// allocation is filled with, and how many were filled under the present setting
+inline std::atomic<int> g_alloc_fill{-1};
+inline std::atomic<unsigned long long> g_alloc_filled{0};
 
 template <typename T>
 struct DevBuf {
@@ -130,6 +134,16 @@ struct DevBuf {
     }
     live_add(LIVE_DEVICE);
     n = count;
+    const int fill = g_alloc_fill.load(std::memory_order_relaxed);
+    if (fill >= 0) {  // (a test hook: the fill is over before any stream can use the buffer)
+      e = hipMemset(p, fill, count * sizeof(T));
+      if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+      if (e != hipSuccess) {
+        release();
+        return fail(MCX_ERR_HIP, "filling a new allocation of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
+      }
+      g_alloc_filled.fetch_add(1, std::memory_order_relaxed);
+    }
     return MCX_OK;
   }
   void release()  // (the destructor's work; by name only where a buffer is freed in mid-life)

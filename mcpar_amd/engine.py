@@ -896,6 +896,23 @@ def debug_store_geometry(np_, nout, nsteps, nc):
     return {name: int(getattr(g, name)) for name, _ in StoreGeometry._fields_}
 
 
+def debug_fill_allocations(byte=-1):
+    """mcx_debug_fill_allocations (host only): from now on every device allocation the library makes is filled with byte
+    (0..255; -1: off, the default) before it is used.  Returns the allocations filled under the setting this call ends."""
+    n = C.c_ulonglong(0)
+    check(load().mcx_debug_fill_allocations(byte, C.byref(n)))
+    return int(n.value)
+
+
+def debug_fill_scratch(owner, byte):
+    """mcx_debug_fill_scratch: the analyses' three scratch buffers of an Engine or a DerivedStore filled with byte (0..255) to
+    their present capacity; returns the bytes filled per buffer (doubles, 64-bit words, 32-bit words; 0: not allocated yet)"""
+    out = (C.c_size_t * 3)()
+    e, s = (owner.h, None) if isinstance(owner, Engine) else (None, owner.h)
+    check(load().mcx_debug_fill_scratch(e, s, byte, out))
+    return tuple(int(v) for v in out)
+
+
 def debug_live_resources():
     """mcx_debug_live_resources (needs no GPU): (device allocations, pinned allocations, streams, events) the library holds now"""
     out = (C.c_uint64 * 4)()
