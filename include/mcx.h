@@ -958,6 +958,72 @@ int mcx_debug_parse_token(const char *tok, size_t len, uint32_t *bits, int *stat
  * staging of the pieces in pinned memory, the whole call (wall clock) */
 int mcx_debug_text_times(const char *text, size_t nbytes, const mcx_text_spec *spec, mcx_text_report *rep, double *ms);
 
+/* ---- two sample stores compared, on the device ----------------------
+ * Do stores A and B sample the same distribution?  Per column (the parameters, then log L; both stores have the same number of
+ * columns, any nc and nsteps on either side): na = nsteps_a * nc_a and nb = nsteps_b * nc_b values, each in [1, 2^31).
+ * Values are ordered by the key of the rank summary: -0 and +0 are one point, -inf and +inf ordinary end points, every NaN
+ * one point that sorts last.  cA(x), cB(x) = the number of values <= x in that order.
+ *   ks_plus_num   = max over the distinct values x of A of cA(x) nb - cB(x) na   (int64, >= 0, < 2^62)
+ *   ks_minus_num  = max over the distinct values x of B of cB(x) na - cA(x) nb
+ *   ks_plus_x, ks_minus_x   the smallest x that attains each maximum
+ *   ks            = (double)max(ks_plus_num, ks_minus_num) / ((double)na * (double)nb): the two-sample Kolmogorov-Smirnov
+ *                   distance, exact in integers up to that one division
+ *   w1            = the Wasserstein-1 distance, the area between the two ECDFs in the column's units: over the pooled distinct
+ *                   values x_0 < ... < x_m, sum_{k<m} |cA(x_k) nb - cB(x_k) na| (x_{k+1} - x_k) / (na nb), fp64, fixed order
+ *   mean_*, sd_*, ess_*   mcx_samples_summary's numbers of each side when that side has nsteps >= 4 and MCX_COMPARE_IID is
+ *                   not set; else ess = n, mean and sd (divisor n - 1; NaN for n = 1) as the summary gives them
+ *   z_mean        = (mean_a - mean_b) / sqrt(sd_a^2 / ess_a + sd_b^2 / ess_b)
+ *   ks_neff, ks_p mcx_ks_prob(ks, ess_a, ess_b): not an exact test -- the asymptotic Kolmogorov law with the ESS in the place
+ *                   of the sample sizes
+ * A side whose fp64 column sum is not finite has MCX_COMPARE_NONFINITE_A / _B: the KS fields stay (the order defines them);
+ * w1, mean_*, sd_*, ess_*, z_mean, ks_neff and ks_p of that column are NaN.  The same stores and arguments give the same
+ * bytes; the same store on both sides gives zeros and ks_p = 1.  MCX_ERR_INVALID before anything is allocated: a NULL store,
+ * rows or cols, unknown flags, different column counts, the two stores on different devices; MCX_ERR_UNSUPPORTED: 2^31 or more
+ * values on a side.  spec == NULL: flags = 0.  The call runs on A's stream with A's scratch after B's stream is idle. */
+enum { MCX_COMPARE_IID = 1 };                                   /* mcx_compare_spec.flags: treat every value as an independent draw */
+enum { MCX_COMPARE_NONFINITE_A = 1, MCX_COMPARE_NONFINITE_B = 2 }; /* mcx_col_compare.flags */
+typedef struct mcx_compare_spec {
+  int flags;
+} mcx_compare_spec;
+typedef struct mcx_col_compare {
+  long long ks_plus_num, ks_minus_num;
+  double ks_plus_x, ks_minus_x;
+  double ks, w1;
+  double mean_a, sd_a, ess_a;
+  double mean_b, sd_b, ess_b;
+  double z_mean, ks_neff, ks_p;
+  long long na, nb;
+  int flags, reserved;
+} mcx_col_compare;
+/* cols[ncol] */
+int mcx_store_compare(mcx_store *a, mcx_store *b, const mcx_compare_spec *spec, mcx_col_compare *cols);
+/* host rows in MCout layout on both sides (np + 1 columns) */
+int mcx_rows_compare(const float *rows_a, int nsteps_a, int nc_a, const float *rows_b, int nsteps_b, int nc_b, int np,
+                     const mcx_compare_spec *spec, mcx_col_compare *cols);
+/* two step ranges of one engine's store (they may overlap), and a range against a store.  MCX_ERR_INVALID in the cases
+ * mcx_samples_summary refuses; a queued MCX_OPT_ASYNC_RUN run is finished first */
+int mcx_samples_compare(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_compare_spec *spec,
+                        mcx_col_compare *cols);
+int mcx_samples_compare_store(mcx_engine *e, int first_step, int nsteps, mcx_store *b, const mcx_compare_spec *spec,
+                              mcx_col_compare *cols);
+/* host only: *neff = ess_a ess_b / (ess_a + ess_b), *p = Q((sqrt(neff) + 0.12 + 0.11 / sqrt(neff)) ks), Q the survival
+ * function of Kolmogorov's distribution.  MCX_ERR_INVALID: ks outside [0, 1], an ess <= 0, a NULL output; NaN in, NaN out */
+int mcx_ks_prob(double ks, double ess_a, double ess_b, double *neff, double *p);
+/* host only: the launch geometry of a comparison of na against nb values per column of ncol columns */
+typedef struct mcx_compare_geometry {
+  long long block, tile_keys;        /* threads per workgroup; keys per sort and sweep tile */
+  long long tiles_a, tiles_b;        /* sweep tiles per column of each side */
+  long long window_lds_keys;         /* a tile whose window of the other side has at most this many keys searches it in LDS */
+  long long lds_bytes;               /* of a sweep workgroup */
+  long long group_cols;              /* columns sorted and swept at a time before any halving for memory (MCX_COMPARE_GROUP_COLS caps it) */
+  long long scratch_bytes_per_col;   /* per-call scratch of one column of a group */
+} mcx_compare_geometry;
+int mcx_debug_compare_geometry(long long na, long long nb, int ncol, mcx_compare_geometry *g);
+/* one mcx_samples_compare call, its results let go, ms[10] by HIP events: 0 the two sides' summaries, 1 A's keys, 2 A's sort,
+ * 3 B's keys, 4 B's sort, 5 the bounds, 6 the sweep with self = A, 7 with self = B, 8 the reducer, 9 the whole call */
+int mcx_debug_compare_times(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_compare_spec *spec,
+                            double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -93,6 +93,17 @@ class TextReport(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("nrows", "nlines", "ntokens", "nfallback", "npieces")] + [("ncol", C.c_int)]
 
 
+class CompareSpecC(C.Structure):
+    """include/mcx.h mcx_compare_spec"""
+    _fields_ = [("flags", C.c_int)]
+
+
+class CompareGeometry(C.Structure):
+    """include/mcx.h mcx_compare_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "tile_keys", "tiles_a", "tiles_b", "window_lds_keys", "lds_bytes",
+                                            "group_cols", "scratch_bytes_per_col")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -244,6 +255,13 @@ def load():
         "mcx_file_store": [C.c_char_p, C.POINTER(TextSpec), C.POINTER(vp), C.POINTER(TextReport)],
         "mcx_debug_parse_token": [C.c_char_p, C.c_size_t, u32p, C.POINTER(C.c_int)],
         "mcx_debug_text_times": [C.c_char_p, C.c_size_t, C.POINTER(TextSpec), C.POINTER(TextReport), dp],
+        "mcx_store_compare": [vp, vp, C.POINTER(CompareSpecC), vp],
+        "mcx_rows_compare": [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.POINTER(CompareSpecC), vp],
+        "mcx_samples_compare": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CompareSpecC), vp],
+        "mcx_samples_compare_store": [vp, C.c_int, C.c_int, vp, C.POINTER(CompareSpecC), vp],
+        "mcx_ks_prob": [C.c_double, C.c_double, C.c_double, dp, dp],
+        "mcx_debug_compare_geometry": [C.c_longlong, C.c_longlong, C.c_int, C.POINTER(CompareGeometry)],
+        "mcx_debug_compare_times": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CompareSpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

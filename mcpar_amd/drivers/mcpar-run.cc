@@ -12,6 +12,7 @@
 //             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
 //             [--chain-table FILE] [--chain-keep Z[,MINMOVES[,MAXSTAY]]] [--kept-chains FILE] [--kept-summary FILE]
 //             [--step-table FILE [--step-probs p1,p2,...] [--settle TOLM[,TOLS[,REF]]]]
+//             [--compare FILE --compare-to OTHER [--compare-nc NC]] [--compare-halves FILE] [--compare-iid]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -62,6 +63,11 @@
 // --step-probs p1,p2,... (default 0.05,0.5,0.95; up to 8): the quantiles' probabilities.  --settle TOLM[,TOLS[,REF]] (default
 // 0.1,0.1,0.5): the rule of mcx_steps_settle over every column: a line `settled at step S of T` or `not settled`, a header
 // `column m_ref s_ref last_out max_dev_mean max_dev_sd` and one line per column.  Under the conditions of --summary.
+// --compare FILE --compare-to OTHER: do the kept rows (A) and the sample text OTHER (B: lines of np + 1 numbers from a run of NC
+// chains, default --nc; parsed on the GPU) sample the same distribution?  One row per column into FILE (mcx_rows_compare, DESIGN.md
+// section 20): the exact two-sample Kolmogorov-Smirnov distance, the Wasserstein-1 distance, each side's mean, sd and ESS, the z
+// of the means and the Kolmogorov probability at the effective sizes (--compare-iid: at the sample sizes).  --compare-halves
+// FILE: the same for the first floor(nsamp / 2) kept steps against the rest.
 // --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
 // the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
 // one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
@@ -499,6 +505,69 @@ static int write_steps(const char *path, const std::vector<double> &probs, const
   return fclose(f) == 0 ? 0 : 1;
 }
 
+// one row per column of a comparison
+static int print_compare(const char *path, const std::vector<mcx_col_compare> &cols, int np)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "name ks ks_plus_num ks_plus_x ks_minus_num ks_minus_x w1 mean_a sd_a ess_a mean_b sd_b ess_b z_mean ks_neff ks_p na nb flags\n");
+  for (int c = 0; c <= np; ++c) {
+    const mcx_col_compare &o = cols[c];
+    fprintf(f, "%s %.17g %lld %.17g %lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %lld %lld %d\n",
+            colname('p', c, np).c_str(), o.ks, o.ks_plus_num, o.ks_plus_x, o.ks_minus_num, o.ks_minus_x, o.w1, o.mean_a, o.sd_a, o.ess_a,
+            o.mean_b, o.sd_b, o.ess_b, o.z_mean, o.ks_neff, o.ks_p, o.na, o.nb, o.flags);
+  }
+  return fclose(f) == 0 ? 0 : 1;
+}
+
+// --compare FILE --compare-to OTHER: MCout's rows (A) against the sample text OTHER of other_nc chains (B), parsed on the GPU;
+// --compare-halves FILE: the first floor(nsamp / 2) kept steps (A) against the rest (B)
+static int write_compare(const char *path, const char *other, int other_nc, bool iid, const char *halves_path, MCout &rows, int nsamp,
+                         int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--compare: " << rows.size() << " rows stored, a comparison needs nsamp * nc of them\n";
+    return 1;
+  }
+  const mcx_compare_spec spec = {iid ? MCX_COMPARE_IID : 0};
+  std::vector<mcx_col_compare> cols((size_t)np + 1);
+  if (path) {
+    mcx_text_spec tspec = {np + 1, other_nc, 0, -1, 0};
+    mcx_text_report trep;
+    mcx_store *ts = 0;
+    if (mcx_file_store(other, &tspec, &ts, &trep) != MCX_OK) {
+      std::cerr << "--compare-to " << other << ": " << mcx_last_error() << "\n";
+      return 1;
+    }
+    const int tb = (int)(trep.nrows / other_nc);
+    std::vector<float> rb((size_t)trep.nrows * (size_t)trep.ncol);
+    int rc = mcx_store_copy(ts, 0, tb, rb.data());
+    mcx_store_destroy(ts);
+    if (rc == MCX_OK) rc = mcx_rows_compare(rows.getpset(0), nsamp, nc, rb.data(), tb, other_nc, np, &spec, cols.data());
+    if (rc != MCX_OK) {
+      std::cerr << "--compare: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    if (print_compare(path, cols, np) != 0) return 1;
+  }
+  if (halves_path) {
+    const int h = nsamp / 2;
+    if (h < 1) {
+      std::cerr << "--compare-halves: " << nsamp << " kept steps, two halves need at least 2\n";
+      return 1;
+    }
+    if (mcx_rows_compare(rows.getpset(0), h, nc, rows.getpset(0) + (size_t)h * nc * (np + 1), nsamp - h, nc, np, &spec, cols.data()) != MCX_OK) {
+      std::cerr << "--compare-halves: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    if (print_compare(halves_path, cols, np) != 0) return 1;
+  }
+  return 0;
+}
+
 // --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
 static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
                          const mcx_density_spec &dspec, const char *dens2d_path, const mcx_density2d_spec &d2spec, MCout &rows, int nsamp,
@@ -667,6 +736,9 @@ int main(int argc, char *argv[])
   std::string chain_table_file, kept_chains_file, kept_summary_file;
   mcx_chain_rule chain_rule = {5.0, 1, 0, 0};
   std::string step_table_file;
+  std::string compare_file, compare_to_file, compare_halves_file;
+  int compare_nc = 0;
+  bool compare_iid = false;
   std::vector<double> step_probs = {0.05, 0.5, 0.95};
   mcx_step_rule step_rule = {0.1, 0.1, 0.5, 0};
   bool settle = false;
@@ -766,6 +838,11 @@ int main(int argc, char *argv[])
     }
     else if (a == "--kept-chains") kept_chains_file = val();
     else if (a == "--step-table") step_table_file = val();
+    else if (a == "--compare") compare_file = val();
+    else if (a == "--compare-to") compare_to_file = val();
+    else if (a == "--compare-nc") compare_nc = atoi(val());
+    else if (a == "--compare-iid") compare_iid = true;
+    else if (a == "--compare-halves") compare_halves_file = val();
     else if (a == "--step-probs") {
       step_probs.clear();
       std::stringstream ss(val());
@@ -866,6 +943,22 @@ int main(int argc, char *argv[])
   if (!step_table_file.empty() && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--step-table needs the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  const bool want_compare = !compare_file.empty() || !compare_halves_file.empty();
+  if (compare_file.empty() != compare_to_file.empty() || (compare_nc != 0 && compare_file.empty()) || compare_nc < 0 ||
+      (compare_iid && !want_compare)) {
+    if (rank == 0)
+      std::cerr << "--compare FILE and --compare-to OTHER go together; --compare-nc belongs to them, --compare-iid to them or to "
+                   "--compare-halves\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_compare && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--compare and --compare-halves need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -1032,6 +1125,11 @@ int main(int argc, char *argv[])
     return 2;
   }
   if (!step_table_file.empty() && write_steps(step_table_file.c_str(), step_probs, settle ? &step_rule : 0, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_compare && write_compare(compare_file.empty() ? 0 : compare_file.c_str(), compare_to_file.c_str(), compare_nc ? compare_nc : nc,
+                                    compare_iid, compare_halves_file.empty() ? 0 : compare_halves_file.c_str(), rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

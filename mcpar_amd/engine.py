@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, Counters, Density2dSpecC,
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, Density2dSpecC,
                    DensitySpecC, Derive, PlanItem, Profile, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
@@ -65,6 +65,15 @@ STEP_ROW_DTYPE = np.dtype([("moved", np.int32), ("ll_max", np.float32), ("ll_max
 STEP_SETTLE_DTYPE = np.dtype([("m_ref", np.float64), ("s_ref", np.float64), ("max_dev_mean", np.float64), ("max_dev_sd", np.float64),
                               ("last_out", np.int32), ("reserved", np.int32)], align=True)
 assert STEP_COL_DTYPE.itemsize == 32 and STEP_ROW_DTYPE.itemsize == 16 and STEP_SETTLE_DTYPE.itemsize == 40
+# include/mcx.h mcx_col_compare
+COMPARE_DTYPE = np.dtype([("ks_plus_num", np.int64), ("ks_minus_num", np.int64), ("ks_plus_x", np.float64), ("ks_minus_x", np.float64),
+                          ("ks", np.float64), ("w1", np.float64), ("mean_a", np.float64), ("sd_a", np.float64), ("ess_a", np.float64),
+                          ("mean_b", np.float64), ("sd_b", np.float64), ("ess_b", np.float64), ("z_mean", np.float64),
+                          ("ks_neff", np.float64), ("ks_p", np.float64), ("na", np.int64), ("nb", np.int64), ("flags", np.int32),
+                          ("reserved", np.int32)], align=True)
+assert COMPARE_DTYPE.itemsize == 144
+COMPARE_IID = 1                                   # mcx_compare_spec.flags
+COMPARE_NONFINITE_A, COMPARE_NONFINITE_B = 1, 2   # mcx_col_compare.flags
 STEP_MAX_PROBS = 8  # include/mcx.h MCX_STEP_MAX_PROBS
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
@@ -603,6 +612,10 @@ class DerivedStore:
         t, _, ncol = self.shape
         return _step_table_call(lambda *a: load().mcx_store_step_table(self.h, *a), t, ncol, probs)
 
+    def compare(self, other, iid=False):
+        """compare_stores(self, other)"""
+        return compare_stores(self, other, iid)
+
 
 def derive_rows(rows, nsteps, nc, spec):
     """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
@@ -886,6 +899,48 @@ def debug_steptable_geometry(np_, nsteps, nc, nprobs=3):
     g = SteptableGeometry()
     check(load().mcx_debug_steptable_geometry(np_, nsteps, nc, nprobs, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in SteptableGeometry._fields_}
+
+
+# ---- two stores compared (include/mcx.h) ----
+def _compare_call(fn, ncol, iid):
+    """fn(spec, cols) of one of the four compare entry points -> the dict of arrays [ncol]: ks_plus_num, ks_minus_num (int64),
+    ks_plus_x, ks_minus_x, ks, w1, mean_a, sd_a, ess_a, mean_b, sd_b, ess_b, z_mean, ks_neff, ks_p, na, nb, flags"""
+    spec = CompareSpecC(COMPARE_IID if iid else 0)
+    cols = np.zeros(max(int(ncol), 1), COMPARE_DTYPE)
+    check(fn(C.byref(spec), cols.ctypes.data_as(C.c_void_p)))
+    return {name: cols[name].copy() for name in COMPARE_DTYPE.names if name != "reserved"}
+
+
+def compare_rows(rows_a, nsteps_a, nc_a, rows_b, nsteps_b, nc_b, iid=False):
+    """mcx_rows_compare: do rows_a [nsteps_a * nc_a, np + 1] and rows_b [nsteps_b * nc_b, np + 1] (MCout layout) sample the same
+    distribution?  Per column the exact two-sample Kolmogorov-Smirnov distance, the Wasserstein-1 distance, each side's mean,
+    sd and ESS, the z of the means and the Kolmogorov probability at the effective sizes (iid: at the sample sizes)"""
+    rows_a, rows_b = np.ascontiguousarray(rows_a, np.float32), np.ascontiguousarray(rows_b, np.float32)
+    ncol = rows_a.shape[1]
+    if rows_b.shape[1] != ncol:
+        raise ValueError("rows_a has %d columns and rows_b %d" % (ncol, rows_b.shape[1]))
+    return _compare_call(lambda *a: load().mcx_rows_compare(_fp(rows_a), nsteps_a, nc_a, _fp(rows_b), nsteps_b, nc_b, ncol - 1, *a),
+                         ncol, iid)
+
+
+def compare_stores(a, b, iid=False):
+    """mcx_store_compare: compare_rows' dict for two DerivedStores on one device"""
+    return _compare_call(lambda *args: load().mcx_store_compare(a.h, b.h, *args), a.shape[2], iid)
+
+
+def ks_prob(ks, ess_a, ess_b):
+    """mcx_ks_prob (host only): (ks_neff, ks_p) of a Kolmogorov-Smirnov distance between samples of effective sizes ess_a, ess_b"""
+    neff, p = C.c_double(0.0), C.c_double(0.0)
+    check(load().mcx_ks_prob(ks, ess_a, ess_b, C.byref(neff), C.byref(p)))
+    return neff.value, p.value
+
+
+def debug_compare_geometry(na, nb, ncol):
+    """mcx_debug_compare_geometry (host only): the launch geometry of a comparison of na against nb values per column, as a dict
+    of include/mcx.h's fields"""
+    g = CompareGeometry()
+    check(load().mcx_debug_compare_geometry(na, nb, ncol, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in CompareGeometry._fields_}
 
 
 def debug_store_geometry(np_, nout, nsteps, nc):
@@ -1434,6 +1489,24 @@ class Engine:
         ll_max, ll_max_chain, step_flags [T] per step"""
         nsteps = self._nsteps(first_step, nsteps)
         return _step_table_call(lambda *a: load().mcx_samples_step_table(self.h, first_step, nsteps, *a), nsteps, self.np + 1, probs)
+
+    def compare(self, first_a, nsteps_a, first_b, nsteps_b, iid=False):
+        """mcx_samples_compare: compare_rows' dict for kept steps [first_a, first_a + nsteps_a) against [first_b, first_b +
+        nsteps_b) of this engine's store (the ranges may overlap)"""
+        return _compare_call(lambda *a: load().mcx_samples_compare(self.h, first_a, nsteps_a, first_b, nsteps_b, *a), self.np + 1, iid)
+
+    def compare_store(self, first_step, nsteps, other, iid=False):
+        """mcx_samples_compare_store: kept steps [first_step, first_step + nsteps) (nsteps None: to the end) against the
+        DerivedStore other"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _compare_call(lambda *a: load().mcx_samples_compare_store(self.h, first_step, nsteps, other.h, *a), self.np + 1, iid)
+
+    def compare_times(self, first_a, nsteps_a, first_b, nsteps_b, iid=False):
+        """mcx_debug_compare_times: ms[10] of one compare() call -- the summaries, A's keys, A's sort, B's keys, B's sort, the
+        bounds, the sweep of A, the sweep of B, the reducer, the whole call"""
+        spec, ms = CompareSpecC(COMPARE_IID if iid else 0), np.zeros(10)
+        check(load().mcx_debug_compare_times(self.h, first_a, nsteps_a, first_b, nsteps_b, C.byref(spec), _dp(ms)))
+        return ms
 
     def step_table_times(self, first_step=0, nsteps=None, probs=(0.05, 0.5, 0.95)):
         """mcx_debug_step_table_times: ms of (the moments sweep, the select sweep, the row sweep and its reducer, the whole
