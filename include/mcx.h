@@ -1024,6 +1024,89 @@ int mcx_debug_compare_geometry(long long na, long long nb, int ncol, mcx_compare
 int mcx_debug_compare_times(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_compare_spec *spec,
                             double *ms);
 
+/* ---- two sample stores compared jointly, on the device -------------
+ * The energy distance (Szekely & Rizzo) between rows of stores A and B as points in column space, with a permutation test.
+ * Both stores have the same columns and any nc and nsteps; NA = nsteps_a * nc_a and NB rows in MCout order.  The columns
+ * used are the parameters (a derived store's outputs); MCX_ENERGY_WITH_LL adds the last column.
+ *   rows of a side  spec.n_a (n_b) > 0: that many draws with replacement by section 12's rule -- draw i of A is draw i of
+ *                   mcx_debug_draw_indices(seed, NA, ...), draw i of B is draw n_a + i of (seed, NB); 0: min(rows, 2048)
+ *                   draws; -1: every row of the side in store order.  2 <= n <= MCX_ENERGY_MAX_SIDE a side, 0 <= nperm <= 4095
+ *   scale[c]        the standard deviation of column c over the N = n_a + n_b pooled rows (A's, then B's): fp64, centred
+ *                   two-pass, divisor N - 1.  A used column with a value that is not finite has MCX_ENERGY_COL_NONFINITE, one
+ *                   with scale 0 MCX_ENERGY_COL_CONSTANT: both are left out of the distance.  MCX_ENERGY_RAW: scale = 1, only
+ *                   the first rule applies.  The last column without MCX_ENERGY_WITH_LL: MCX_ENERGY_COL_UNUSED, scale NaN
+ *   d_ij            sqrt(sum_c (z_ic - z_jc)^2), z_ic = (double)x_ic / scale[c], every difference formed directly, fp64
+ *   sums            for a label vector l in {0,1}^N with n_a ones: S = sum_ij d_ij, S_A = sum_i l_i sum_j d_ij,
+ *                   S_AA = sum_ij l_i l_j d_ij (ordered pairs); S_AB = S_A - S_AA, S_BB = S - 2 S_A + S_AA,
+ *                   E(l) = 2 S_AB / (n_a n_b) - S_AA / n_a^2 - S_BB / n_b^2
+ *   e, mean_*, h    E and the three normalised sums of l_0 = the first n_a rows; h = e / (2 mean_ab) (NaN at mean_ab = 0)
+ *   perm_e[p - 1]   E(l_p), p = 1 ... nperm: l_p is mcx_debug_energy_labels' vector (Philox stream 6)
+ *   nge, p_value    #{p : perm_e >= e} and (1 + nge) / (1 + nperm) (NaN at nperm = 0)
+ * If no column is left every statistic is NaN, nused = 0 and the call returns MCX_OK.  The permutation law is exact for
+ * exchangeable rows; the rows of a store are autocorrelated, so draw far fewer rows than the smallest column ESS that
+ * mcx_*_compare reports, or read the p-value as anticonservative (the result carries n_a, n_b, na_rows, nb_rows to judge by).
+ * The same stores and arguments give the same bytes.  MCX_ERR_INVALID before anything is allocated: a NULL store, rows or
+ * res, unknown flags, different column counts, stores on different devices, sizes outside the limits.  cols[ncol] and
+ * perm_e[nperm] may be NULL; spec == NULL is {0, 0, 999, 0, 0}.  While it makes the label vectors a call runs up to 15 threads of
+ * its own beside the caller's (at most one per block of 16 label vectors and per hardware thread), all joined before it returns. */
+enum { MCX_ENERGY_WITH_LL = 1, MCX_ENERGY_RAW = 2 };                                         /* mcx_energy_spec.flags */
+enum { MCX_ENERGY_COL_NONFINITE = 1, MCX_ENERGY_COL_CONSTANT = 2, MCX_ENERGY_COL_UNUSED = 4 }; /* mcx_energy_col.flags */
+enum { MCX_ENERGY_MAX_SIDE = 16384, MCX_ENERGY_MAX_PERM = 4095 };
+typedef struct mcx_energy_spec {
+  int n_a, n_b, nperm;
+  uint32_t seed;
+  unsigned flags;
+} mcx_energy_spec;
+typedef struct mcx_energy_result {
+  double e, h, mean_ab, mean_aa, mean_bb, p_value;
+  long long nge;
+  int n_a, n_b, nperm, nused;
+  long long na_rows, nb_rows;
+} mcx_energy_result;
+typedef struct mcx_energy_col {
+  double scale;
+  int flags;
+} mcx_energy_col;
+int mcx_store_energy(mcx_store *a, mcx_store *b, const mcx_energy_spec *spec, mcx_energy_result *res, mcx_energy_col *cols,
+                     double *perm_e);
+/* host rows in MCout layout on both sides (np + 1 columns) */
+int mcx_rows_energy(const float *rows_a, int nsteps_a, int nc_a, const float *rows_b, int nsteps_b, int nc_b, int np,
+                    const mcx_energy_spec *spec, mcx_energy_result *res, mcx_energy_col *cols, double *perm_e);
+/* two step ranges of one engine's store (they may overlap), and a range against a store.  MCX_ERR_INVALID in the cases
+ * mcx_samples_compare refuses; a queued MCX_OPT_ASYNC_RUN run is finished first */
+int mcx_samples_energy(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_energy_spec *spec,
+                       mcx_energy_result *res, mcx_energy_col *cols, double *perm_e);
+int mcx_samples_energy_store(mcx_engine *e, int first_step, int nsteps, mcx_store *b, const mcx_energy_spec *spec,
+                             mcx_energy_result *res, mcx_energy_col *cols, double *perm_e);
+/* host only: labels[n_a + n_b] of permutation p (0: the first n_a rows; 1 ... MCX_ENERGY_MAX_PERM: a partial Fisher-Yates on
+ * idx = [0, N) -- for i < n_a, w = philox4x32_10(counter (i, p, 0, 0), key (seed, 6)), r = w.x : w.y, j = i + ((r (N - i)) >> 64),
+ * swap idx[i] and idx[j], labels[idx[i]] = 1) */
+int mcx_debug_energy_labels(uint32_t seed, int n_a, int n_b, int p, uint8_t *labels);
+/* mcx_rows_energy's device sums: sums[0] = S, then (S_A, S_AA) of l_0 ... l_nperm, 3 + 2 nperm doubles (all NaN if no column
+ * is left) */
+int mcx_debug_energy_sums(const float *rows_a, int nsteps_a, int nc_a, const float *rows_b, int nsteps_b, int nc_b, int np,
+                          const mcx_energy_spec *spec, double *sums);
+/* host only: the launch geometry of n_a against n_b rows of nused columns with nperm permutations.  k_energy_pairs has a grid
+ * of (tiles, slabs, chunks) workgroups: tile_rows rows i each, against the slab_rows rows j of a slab (the last one shorter;
+ * MCX_ENERGY_SLAB_ROWS, a multiple of 64, lowers the default: a knob for tests only, since the partials grow as the slabs
+ * shrink -- about 17 GB at 64 rows and the largest call), for chunk_blocks blocks of 16 label columns (the
+ * power of two that holds label_blocks, 16 at most; the last chunk may hold fewer).  label_cols = nperm + 2: a column of ones,
+ * l_0, l_1 ... l_nperm */
+typedef struct mcx_energy_geometry {
+  long long block, tile_rows, tiles;
+  long long slab_rows, slabs;
+  long long label_cols, label_blocks, chunk_blocks, chunks;
+  long long col_chunk;      /* columns of z staged at a time */
+  long long workgroups;
+  long long lds_bytes;      /* of a k_energy_pairs workgroup */
+  long long scratch_bytes;  /* z, the packed labels, the partials and the sums */
+} mcx_energy_geometry;
+int mcx_debug_energy_geometry(int n_a, int n_b, int nused, int nperm, mcx_energy_geometry *g);
+/* one mcx_samples_energy call, its results let go, ms[7]: 0 the gather of both sides, 3 the uploads, 4 k_energy_pairs, 5 the
+ * reducer and its copy (HIP events); 1 scale and flags, 2 the label vectors, 6 the whole call (the host's clock) */
+int mcx_debug_energy_times(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_energy_spec *spec,
+                           double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -104,6 +104,23 @@ class CompareGeometry(C.Structure):
                                             "group_cols", "scratch_bytes_per_col")]
 
 
+class EnergySpecC(C.Structure):
+    """include/mcx.h mcx_energy_spec"""
+    _fields_ = [("n_a", C.c_int), ("n_b", C.c_int), ("nperm", C.c_int), ("seed", C.c_uint32), ("flags", C.c_uint)]
+
+
+class EnergyResultC(C.Structure):
+    """include/mcx.h mcx_energy_result"""
+    _fields_ = ([(n, C.c_double) for n in ("e", "h", "mean_ab", "mean_aa", "mean_bb", "p_value")] + [("nge", C.c_longlong)] +
+                [(n, C.c_int) for n in ("n_a", "n_b", "nperm", "nused")] + [("na_rows", C.c_longlong), ("nb_rows", C.c_longlong)])
+
+
+class EnergyGeometry(C.Structure):
+    """include/mcx.h mcx_energy_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "tile_rows", "tiles", "slab_rows", "slabs", "label_cols", "label_blocks",
+                                            "chunk_blocks", "chunks", "col_chunk", "workgroups", "lds_bytes", "scratch_bytes")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -262,6 +279,14 @@ def load():
         "mcx_ks_prob": [C.c_double, C.c_double, C.c_double, dp, dp],
         "mcx_debug_compare_geometry": [C.c_longlong, C.c_longlong, C.c_int, C.POINTER(CompareGeometry)],
         "mcx_debug_compare_times": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CompareSpecC), dp],
+        "mcx_store_energy": [vp, vp, C.POINTER(EnergySpecC), C.POINTER(EnergyResultC), vp, dp],
+        "mcx_rows_energy": [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), C.POINTER(EnergyResultC), vp, dp],
+        "mcx_samples_energy": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), C.POINTER(EnergyResultC), vp, dp],
+        "mcx_samples_energy_store": [vp, C.c_int, C.c_int, vp, C.POINTER(EnergySpecC), C.POINTER(EnergyResultC), vp, dp],
+        "mcx_debug_energy_labels": [C.c_uint32, C.c_int, C.c_int, C.c_int, vp],
+        "mcx_debug_energy_sums": [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), dp],
+        "mcx_debug_energy_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EnergyGeometry)],
+        "mcx_debug_energy_times": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

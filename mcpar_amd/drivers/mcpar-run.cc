@@ -13,6 +13,8 @@
 //             [--chain-table FILE] [--chain-keep Z[,MINMOVES[,MAXSTAY]]] [--kept-chains FILE] [--kept-summary FILE]
 //             [--step-table FILE [--step-probs p1,p2,...] [--settle TOLM[,TOLS[,REF]]]]
 //             [--compare FILE --compare-to OTHER [--compare-nc NC]] [--compare-halves FILE] [--compare-iid]
+//             [--energy FILE --compare-to OTHER [--compare-nc NC]] [--energy-halves FILE] [--energy-n NA[,NB]] [--energy-perm P]
+//             [--energy-seed S] [--energy-with-ll] [--energy-raw]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -68,6 +70,11 @@
 // section 20): the exact two-sample Kolmogorov-Smirnov distance, the Wasserstein-1 distance, each side's mean, sd and ESS, the z
 // of the means and the Kolmogorov probability at the effective sizes (--compare-iid: at the sample sizes).  --compare-halves
 // FILE: the same for the first floor(nsamp / 2) kept steps against the rest.
+// --energy FILE --compare-to OTHER: the same two sides compared as clouds of points (mcx_rows_energy): the
+// energy distance between NA rows of A and NB of B (--energy-n, default 0,0: min(rows, 2048) draws each; -1: every row) and its
+// law under --energy-perm P (default 999) permutations of seed --energy-seed (default 0); --energy-with-ll adds log L to the
+// columns, --energy-raw leaves them unscaled.  FILE: a header and one line of the result's fields, then a header `name scale
+// flags` and one line per column p0 .. LL.  --energy-halves FILE: the first floor(nsamp / 2) kept steps against the rest.
 // --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
 // the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
 // one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
@@ -523,6 +530,24 @@ static int print_compare(const char *path, const std::vector<mcx_col_compare> &c
   return fclose(f) == 0 ? 0 : 1;
 }
 
+// --compare-to OTHER: the sample text of other_nc chains parsed on the GPU -> its rows rb of tb whole steps.  The library's
+// code, or -1 when the text could not be read (said on stderr)
+static int read_other(const char *other, int other_nc, int np, std::vector<float> &rb, int &tb)
+{
+  mcx_text_spec tspec = {np + 1, other_nc, 0, -1, 0};
+  mcx_text_report trep;
+  mcx_store *ts = 0;
+  if (mcx_file_store(other, &tspec, &ts, &trep) != MCX_OK) {
+    std::cerr << "--compare-to " << other << ": " << mcx_last_error() << "\n";
+    return -1;
+  }
+  tb = (int)(trep.nrows / other_nc);
+  rb.resize((size_t)trep.nrows * (size_t)trep.ncol);
+  const int rc = mcx_store_copy(ts, 0, tb, rb.data());
+  mcx_store_destroy(ts);
+  return rc;
+}
+
 // --compare FILE --compare-to OTHER: MCout's rows (A) against the sample text OTHER of other_nc chains (B), parsed on the GPU;
 // --compare-halves FILE: the first floor(nsamp / 2) kept steps (A) against the rest (B)
 static int write_compare(const char *path, const char *other, int other_nc, bool iid, const char *halves_path, MCout &rows, int nsamp,
@@ -535,17 +560,10 @@ static int write_compare(const char *path, const char *other, int other_nc, bool
   const mcx_compare_spec spec = {iid ? MCX_COMPARE_IID : 0};
   std::vector<mcx_col_compare> cols((size_t)np + 1);
   if (path) {
-    mcx_text_spec tspec = {np + 1, other_nc, 0, -1, 0};
-    mcx_text_report trep;
-    mcx_store *ts = 0;
-    if (mcx_file_store(other, &tspec, &ts, &trep) != MCX_OK) {
-      std::cerr << "--compare-to " << other << ": " << mcx_last_error() << "\n";
-      return 1;
-    }
-    const int tb = (int)(trep.nrows / other_nc);
-    std::vector<float> rb((size_t)trep.nrows * (size_t)trep.ncol);
-    int rc = mcx_store_copy(ts, 0, tb, rb.data());
-    mcx_store_destroy(ts);
+    std::vector<float> rb;
+    int tb = 0;
+    int rc = read_other(other, other_nc, np, rb, tb);
+    if (rc < 0) return 1;
     if (rc == MCX_OK) rc = mcx_rows_compare(rows.getpset(0), nsamp, nc, rb.data(), tb, other_nc, np, &spec, cols.data());
     if (rc != MCX_OK) {
       std::cerr << "--compare: " << mcx_last_error() << "\n";
@@ -564,6 +582,61 @@ static int write_compare(const char *path, const char *other, int other_nc, bool
       return 1;
     }
     if (print_compare(halves_path, cols, np) != 0) return 1;
+  }
+  return 0;
+}
+
+// the result of a joint comparison and one row per column
+static int print_energy(const char *path, const mcx_energy_result &r, const std::vector<mcx_energy_col> &cols, int np)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "e h mean_ab mean_aa mean_bb p_value nge n_a n_b nperm nused na_rows nb_rows\n");
+  fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g %lld %d %d %d %d %lld %lld\n", r.e, r.h, r.mean_ab, r.mean_aa, r.mean_bb, r.p_value, r.nge,
+          r.n_a, r.n_b, r.nperm, r.nused, r.na_rows, r.nb_rows);
+  fprintf(f, "name scale flags\n");
+  for (int c = 0; c <= np; ++c) fprintf(f, "%s %.17g %d\n", colname('p', c, np).c_str(), cols[c].scale, cols[c].flags);
+  return fclose(f) == 0 ? 0 : 1;
+}
+
+// --energy FILE --compare-to OTHER: MCout's rows (A) against the sample text OTHER of other_nc chains (B);
+// --energy-halves FILE: the first floor(nsamp / 2) kept steps (A) against the rest (B)
+static int write_energy(const char *path, const char *other, int other_nc, const mcx_energy_spec &spec, const char *halves_path, MCout &rows,
+                        int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--energy: " << rows.size() << " rows stored, a comparison needs nsamp * nc of them\n";
+    return 1;
+  }
+  mcx_energy_result res;
+  std::vector<mcx_energy_col> cols((size_t)np + 1);
+  if (path) {
+    std::vector<float> rb;
+    int tb = 0;
+    int rc = read_other(other, other_nc, np, rb, tb);
+    if (rc < 0) return 1;
+    if (rc == MCX_OK) rc = mcx_rows_energy(rows.getpset(0), nsamp, nc, rb.data(), tb, other_nc, np, &spec, &res, cols.data(), 0);
+    if (rc != MCX_OK) {
+      std::cerr << "--energy: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    if (print_energy(path, res, cols, np) != 0) return 1;
+  }
+  if (halves_path) {
+    const int h = nsamp / 2;
+    if (h < 1) {
+      std::cerr << "--energy-halves: " << nsamp << " kept steps, two halves need at least 2\n";
+      return 1;
+    }
+    if (mcx_rows_energy(rows.getpset(0), h, nc, rows.getpset(0) + (size_t)h * nc * (np + 1), nsamp - h, nc, np, &spec, &res, cols.data(), 0) !=
+        MCX_OK) {
+      std::cerr << "--energy-halves: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    if (print_energy(halves_path, res, cols, np) != 0) return 1;
   }
   return 0;
 }
@@ -739,6 +812,9 @@ int main(int argc, char *argv[])
   std::string compare_file, compare_to_file, compare_halves_file;
   int compare_nc = 0;
   bool compare_iid = false;
+  std::string energy_file, energy_halves_file;
+  mcx_energy_spec energy_spec = {0, 0, 999, 0u, 0u};
+  bool energy_opts = false;
   std::vector<double> step_probs = {0.05, 0.5, 0.95};
   mcx_step_rule step_rule = {0.1, 0.1, 0.5, 0};
   bool settle = false;
@@ -843,6 +919,27 @@ int main(int argc, char *argv[])
     else if (a == "--compare-nc") compare_nc = atoi(val());
     else if (a == "--compare-iid") compare_iid = true;
     else if (a == "--compare-halves") compare_halves_file = val();
+    else if (a == "--energy") energy_file = val();
+    else if (a == "--energy-halves") energy_halves_file = val();
+    else if (a == "--energy-n") {
+      const char *v = val();
+      const char *comma = strchr(v, ',');
+      energy_spec.n_a = atoi(v);
+      energy_spec.n_b = comma ? atoi(comma + 1) : energy_spec.n_a;
+      energy_opts = true;
+    } else if (a == "--energy-perm") {
+      energy_spec.nperm = atoi(val());
+      energy_opts = true;
+    } else if (a == "--energy-seed") {
+      energy_spec.seed = (uint32_t)strtoul(val(), 0, 10);
+      energy_opts = true;
+    } else if (a == "--energy-with-ll") {
+      energy_spec.flags |= MCX_ENERGY_WITH_LL;
+      energy_opts = true;
+    } else if (a == "--energy-raw") {
+      energy_spec.flags |= MCX_ENERGY_RAW;
+      energy_opts = true;
+    }
     else if (a == "--step-probs") {
       step_probs.clear();
       std::stringstream ss(val());
@@ -948,11 +1045,24 @@ int main(int argc, char *argv[])
     return 2;
   }
   const bool want_compare = !compare_file.empty() || !compare_halves_file.empty();
-  if (compare_file.empty() != compare_to_file.empty() || (compare_nc != 0 && compare_file.empty()) || compare_nc < 0 ||
-      (compare_iid && !want_compare)) {
+  const bool want_energy = !energy_file.empty() || !energy_halves_file.empty();
+  if ((compare_file.empty() && energy_file.empty()) != compare_to_file.empty() || (compare_nc != 0 && compare_to_file.empty()) ||
+      compare_nc < 0 || (compare_iid && !want_compare)) {
     if (rank == 0)
-      std::cerr << "--compare FILE and --compare-to OTHER go together; --compare-nc belongs to them, --compare-iid to them or to "
-                   "--compare-halves\n";
+      std::cerr << "--compare FILE (or --energy FILE) and --compare-to OTHER go together; --compare-nc belongs to them, --compare-iid "
+                   "to --compare or to --compare-halves\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (energy_opts && !want_energy) {
+    if (rank == 0) std::cerr << "--energy-n, --energy-perm, --energy-seed, --energy-with-ll and --energy-raw belong to --energy or --energy-halves\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_energy && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--energy and --energy-halves need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
   }
@@ -1130,6 +1240,11 @@ int main(int argc, char *argv[])
   }
   if (want_compare && write_compare(compare_file.empty() ? 0 : compare_file.c_str(), compare_to_file.c_str(), compare_nc ? compare_nc : nc,
                                     compare_iid, compare_halves_file.empty() ? 0 : compare_halves_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_energy && write_energy(energy_file.empty() ? 0 : energy_file.c_str(), compare_to_file.c_str(), compare_nc ? compare_nc : nc,
+                                  energy_spec, energy_halves_file.empty() ? 0 : energy_halves_file.c_str(), rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

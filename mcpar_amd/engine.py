@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, Density2dSpecC,
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, Density2dSpecC,
                    DensitySpecC, Derive, PlanItem, Profile, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
@@ -74,6 +74,11 @@ COMPARE_DTYPE = np.dtype([("ks_plus_num", np.int64), ("ks_minus_num", np.int64),
 assert COMPARE_DTYPE.itemsize == 144
 COMPARE_IID = 1                                   # mcx_compare_spec.flags
 COMPARE_NONFINITE_A, COMPARE_NONFINITE_B = 1, 2   # mcx_col_compare.flags
+ENERGY_COL_DTYPE = np.dtype([("scale", np.float64), ("flags", np.int32)], align=True)  # include/mcx.h mcx_energy_col
+assert ENERGY_COL_DTYPE.itemsize == 16
+ENERGY_WITH_LL, ENERGY_RAW = 1, 2                                        # mcx_energy_spec.flags
+ENERGY_COL_NONFINITE, ENERGY_COL_CONSTANT, ENERGY_COL_UNUSED = 1, 2, 4   # mcx_energy_col.flags
+ENERGY_MAX_SIDE, ENERGY_MAX_PERM = 16384, 4095
 STEP_MAX_PROBS = 8  # include/mcx.h MCX_STEP_MAX_PROBS
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
@@ -616,6 +621,10 @@ class DerivedStore:
         """compare_stores(self, other)"""
         return compare_stores(self, other, iid)
 
+    def energy(self, other, **kw):
+        """energy_stores(self, other)"""
+        return energy_stores(self, other, **kw)
+
 
 def derive_rows(rows, nsteps, nc, spec):
     """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
@@ -941,6 +950,67 @@ def debug_compare_geometry(na, nb, ncol):
     g = CompareGeometry()
     check(load().mcx_debug_compare_geometry(na, nb, ncol, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in CompareGeometry._fields_}
+
+
+# ---- two stores compared jointly (include/mcx.h) ----
+def _energy_spec(n_a=0, n_b=0, nperm=999, seed=0, with_ll=False, raw=False):
+    return EnergySpecC(n_a, n_b, nperm, seed, (ENERGY_WITH_LL if with_ll else 0) | (ENERGY_RAW if raw else 0))
+
+
+def _energy_call(fn, ncol, **kw):
+    """fn(spec, res, cols, perm_e) of one of the four energy entry points -> the dict of mcx_energy_result's fields (e, h,
+    mean_ab, mean_aa, mean_bb, p_value, nge, n_a, n_b, nperm, nused, na_rows, nb_rows), scale and flags [ncol] per column and
+    perm_e [nperm]"""
+    spec, res = _energy_spec(**kw), EnergyResultC()
+    cols = np.zeros(max(int(ncol), 1), ENERGY_COL_DTYPE)
+    perm_e = np.zeros(max(int(spec.nperm), 0))
+    check(fn(C.byref(spec), C.byref(res), cols.ctypes.data_as(C.c_void_p), _dp(perm_e) if len(perm_e) else None))
+    out = {name: getattr(res, name) for name, _ in EnergyResultC._fields_}
+    out.update(scale=cols["scale"].copy(), flags=cols["flags"].copy(), perm_e=perm_e)
+    return out
+
+
+def energy_rows(rows_a, nsteps_a, nc_a, rows_b, nsteps_b, nc_b, **kw):
+    """mcx_rows_energy: do rows_a [nsteps_a * nc_a, np + 1] and rows_b [nsteps_b * nc_b, np + 1] (MCout layout) sample the same
+    joint distribution?  The energy distance between n_a rows of A and n_b of B (> 0: draws with replacement, 0: min(rows, 2048)
+    draws, -1: every row) in the columns scaled by their pooled sd (raw: unscaled; with_ll: log L too), and its law under nperm
+    permutations of the pooled labels: e, h, p_value = (1 + nge) / (1 + nperm).  Exact for exchangeable rows only"""
+    rows_a, rows_b = np.ascontiguousarray(rows_a, np.float32), np.ascontiguousarray(rows_b, np.float32)
+    ncol = rows_a.shape[1]
+    if rows_b.shape[1] != ncol:
+        raise ValueError("rows_a has %d columns and rows_b %d" % (ncol, rows_b.shape[1]))
+    return _energy_call(lambda *a: load().mcx_rows_energy(_fp(rows_a), nsteps_a, nc_a, _fp(rows_b), nsteps_b, nc_b, ncol - 1, *a),
+                        ncol, **kw)
+
+
+def energy_stores(a, b, **kw):
+    """mcx_store_energy: energy_rows' dict for two DerivedStores on one device"""
+    return _energy_call(lambda *args: load().mcx_store_energy(a.h, b.h, *args), a.shape[2], **kw)
+
+
+def debug_energy_sums(rows_a, nsteps_a, nc_a, rows_b, nsteps_b, nc_b, **kw):
+    """mcx_debug_energy_sums: energy_rows' device sums -- (S, S_A [1 + nperm], S_AA [1 + nperm]), label vector 0 first"""
+    rows_a, rows_b = np.ascontiguousarray(rows_a, np.float32), np.ascontiguousarray(rows_b, np.float32)
+    spec = _energy_spec(**kw)
+    sums = np.zeros(3 + 2 * spec.nperm)
+    check(load().mcx_debug_energy_sums(_fp(rows_a), nsteps_a, nc_a, _fp(rows_b), nsteps_b, nc_b, rows_a.shape[1] - 1, C.byref(spec),
+                                       _dp(sums)))
+    return sums[0], sums[1::2].copy(), sums[2::2].copy()
+
+
+def debug_energy_labels(seed, n_a, n_b, p):
+    """mcx_debug_energy_labels (host only): the label vector [n_a + n_b] (uint8, n_a ones) of permutation p"""
+    labels = np.zeros(max(n_a, 0) + max(n_b, 0), np.uint8)
+    check(load().mcx_debug_energy_labels(seed, n_a, n_b, p, labels.ctypes.data_as(C.c_void_p)))
+    return labels
+
+
+def debug_energy_geometry(n_a, n_b, nused, nperm):
+    """mcx_debug_energy_geometry (host only): the launch geometry of n_a against n_b rows of nused columns with nperm
+    permutations, as a dict of include/mcx.h's fields"""
+    g = EnergyGeometry()
+    check(load().mcx_debug_energy_geometry(n_a, n_b, nused, nperm, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in EnergyGeometry._fields_}
 
 
 def debug_store_geometry(np_, nout, nsteps, nc):
@@ -1506,6 +1576,24 @@ class Engine:
         bounds, the sweep of A, the sweep of B, the reducer, the whole call"""
         spec, ms = CompareSpecC(COMPARE_IID if iid else 0), np.zeros(10)
         check(load().mcx_debug_compare_times(self.h, first_a, nsteps_a, first_b, nsteps_b, C.byref(spec), _dp(ms)))
+        return ms
+
+    def energy(self, first_a, nsteps_a, first_b, nsteps_b, **kw):
+        """mcx_samples_energy: energy_rows' dict for kept steps [first_a, first_a + nsteps_a) against [first_b, first_b +
+        nsteps_b) of this engine's store (the ranges may overlap)"""
+        return _energy_call(lambda *a: load().mcx_samples_energy(self.h, first_a, nsteps_a, first_b, nsteps_b, *a), self.np + 1, **kw)
+
+    def energy_store(self, first_step, nsteps, other, **kw):
+        """mcx_samples_energy_store: kept steps [first_step, first_step + nsteps) (nsteps None: to the end) against the
+        DerivedStore other"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _energy_call(lambda *a: load().mcx_samples_energy_store(self.h, first_step, nsteps, other.h, *a), self.np + 1, **kw)
+
+    def energy_times(self, first_a, nsteps_a, first_b, nsteps_b, **kw):
+        """mcx_debug_energy_times: ms[7] of one energy() call -- the gather, scale and flags (host), the label vectors (host), the
+        uploads, k_energy_pairs, the reducer, the whole call (host clock)"""
+        spec, ms = _energy_spec(**kw), np.zeros(7)
+        check(load().mcx_debug_energy_times(self.h, first_a, nsteps_a, first_b, nsteps_b, C.byref(spec), _dp(ms)))
         return ms
 
     def step_table_times(self, first_step=0, nsteps=None, probs=(0.05, 0.5, 0.95)):
