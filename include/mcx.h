@@ -1107,6 +1107,120 @@ int mcx_debug_energy_geometry(int n_a, int n_b, int nused, int nperm, mcx_energy
 int mcx_debug_energy_times(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_energy_spec *spec,
                            double *ms);
 
+/* ---- importance weights on a store ----------------------------------
+ * The rows of a store reweighted to a posterior close to the sampled one, without a rerun.  N = nsteps * nc rows in row order
+ * (step-major, the chain within the step), 1 <= N < 2^31 (MCX_ERR_UNSUPPORTED from 2^31 on); any nsteps >= 1.
+ * The weight source gives a value v_i per row:
+ *   MCX_WEIGHT_HOST   logw[i], a host array of N floats, uploaded once
+ *   MCX_WEIGHT_STORE  column col of store (same nsteps and nc, same device; col = ncol - 1 is its log L column), usually a
+ *                     derived store whose function computes a log-ratio
+ *   MCX_WEIGHT_LL     the view's own log L column (scale = beta - 1: the power posterior L^beta)
+ * lw_i = scale * (double)v_i (scale finite; 0 and negative values are allowed).  lw = -inf is an ordinary zero weight; a NaN or
+ * +inf in any lw_i, or every lw_i at -inf, is MCX_ERR_INVALID, and mcx_last_error names the lowest such row.
+ * Fixed-point weights: lwmax = max lw_i, q_i = (uint32)rint(2^31 exp(lw_i - lwmax)) in fp64, ties to even: 0 <= q_i <= 2^31,
+ * and some row has 2^31.  A row below 2^-32 of the largest weight has q = 0 and takes part in nothing: the mass left out is
+ * below N 2^-32 of the largest weight.  Everything else is integer sums of q or fp64 sums in a fixed order: the same store and
+ * arguments give the same bytes in every entry point.
+ *   n, nzero         rows, and rows with q = 0
+ *   sumq             Q = sum q_i (< 2^62);  sumq2_hi : sumq2_lo = sum q_i^2, exact in 128 bits
+ *   ess_kish         Q^2 / sum q_i^2, Kish's effective size
+ *   log_mean_w       lwmax + log(Q / (2^31 N)): the log of the average weight -- the log-ratio of the two normalising constants
+ *                    when the weights are a ratio of unnormalised densities
+ *   tail_m, khat, tail_sigma   the M = min(floor(N / 5), ceil(3 sqrt(N))) largest q over their cutoff (the (M + 1)-th largest),
+ *                    x = (q - cutoff) / 2^31, fitted by mcx_khat_of_tail: the Pareto tail index of Vehtari et al.  The weights are
+ *                    not smoothed (no PSIS): khat is reported, the raw weights are used
+ *   flags            MCX_REWEIGHT_NO_TAIL (khat and tail_sigma are NaN: M < 5, or ties at the cutoff reach a quarter into the
+ *                    tail, e.g. constant weights), MCX_REWEIGHT_KHAT_HIGH (khat > 0.7: do not trust the estimates)
+ * Per column, over the rows with q > 0 only (a q = 0 row is never multiplied in):
+ *   mean             sum q x / Q;  sd = sqrt(sum q (x - mean)^2 / Q), two passes
+ *   mcse_mean        sqrt(sum q^2 (x - mean)^2) / Q: the delta-method error of the self-normalised estimate.  It ignores the
+ *                    autocorrelation of the rows
+ *   min, max         the smallest and largest value among rows with q > 0, in mcx_samples_summary's key order (NaN last, -0
+ *                    before +0)
+ *   quantiles[col * nprobs + k]   the smallest value x of the column with C(x) >= t, C(x) the q of the rows whose key is at most
+ *                    x's, t = min(Q, max(1, ceil(probs[k] (double)Q))): the weighted inverse ECDF (R type 1), always a float of
+ *                    the column, no interpolation; numpy.quantile(method="inverted_cdf") at equal weights
+ *   flags            MCX_REWEIGHT_NONFINITE: a row with q > 0 holds an inf or NaN in the column; mean, sd and mcse_mean are NaN,
+ *                    min, max and the quantiles stay defined by the order
+ * MCX_ERR_INVALID before anything is allocated: a NULL store, rows, w, res or cols, an unknown kind, a NULL logw or weight
+ * store, a weight store of another shape or device, col outside it, a scale that is not finite, nprobs outside [0,
+ * MCX_REWEIGHT_MAX_PROBS], a probability outside [0, 1], probs or quantiles NULL with nprobs > 0. */
+enum { MCX_WEIGHT_HOST = 1, MCX_WEIGHT_STORE = 2, MCX_WEIGHT_LL = 3 };  /* mcx_weights.kind */
+enum { MCX_REWEIGHT_NO_TAIL = 1, MCX_REWEIGHT_KHAT_HIGH = 2 };          /* mcx_reweight_result.flags */
+enum { MCX_REWEIGHT_NONFINITE = 1 };                                    /* mcx_col_reweight.flags */
+enum { MCX_REWEIGHT_MAX_PROBS = 64 };
+typedef struct mcx_weights {
+  int kind;
+  const float *logw; /* MCX_WEIGHT_HOST */
+  mcx_store *store;  /* MCX_WEIGHT_STORE */
+  int col;
+  double scale;
+} mcx_weights;
+typedef struct mcx_reweight_result {
+  long long n, nzero;
+  double lwmax;
+  long long sumq;
+  unsigned long long sumq2_hi, sumq2_lo;
+  double ess_kish, log_mean_w;
+  long long tail_m;
+  double khat, tail_sigma;
+  int flags, reserved;
+} mcx_reweight_result;
+typedef struct mcx_col_reweight {
+  double mean, sd, mcse_mean;
+  float min, max;
+  int flags, reserved;
+} mcx_col_reweight;
+int mcx_store_reweight(mcx_store *s, const mcx_weights *w, const double *probs, int nprobs, mcx_reweight_result *res,
+                       mcx_col_reweight *cols, double *quantiles);
+/* steps [first_step, first_step + nsteps) of an engine's store, cols[np + 1]; a queued MCX_OPT_ASYNC_RUN run is finished first */
+int mcx_samples_reweight(mcx_engine *e, int first_step, int nsteps, const mcx_weights *w, const double *probs, int nprobs,
+                         mcx_reweight_result *res, mcx_col_reweight *cols, double *quantiles);
+/* host rows in MCout layout (np + 1 columns) */
+int mcx_rows_reweight(const float *rows, int nsteps, int nc, int np, const mcx_weights *w, const double *probs, int nprobs,
+                      mcx_reweight_result *res, mcx_col_reweight *cols, double *quantiles);
+/* Sampling-importance-resampling: K = nsteps_out * nc_out rows drawn with replacement in proportion to q, 1 <= K < 2^31, as a
+ * store of shape (nsteps_out, nc_out, ncol).  Draw k of seed uses mcx_samples_draw's r (Philox key (seed, 5), counter k):
+ * u = (r Q) >> 64, and the row is the smallest j with q_0 + ... + q_j > u, in row order; row k of the new store is a copy of
+ * that row, and index[k] (may be NULL) is j.  A q = 0 row is never drawn; with equal weights index[k] is mcx_store_draw's.
+ * The "chains" of the new store are not chains: its rows are exchangeable draws, so the density, pair density, covariance,
+ * clip and draws mean something on it, and compare / energy in their iid forms; R-hat and the ESS of its summary do not.
+ * MCX_ERR_INVALID as above, and for out NULL or nsteps_out or nc_out < 1. */
+int mcx_store_resample(mcx_store *s, const mcx_weights *w, uint32_t seed, int nsteps_out, int nc_out, mcx_store **out,
+                       int64_t *index);
+int mcx_samples_resample(mcx_engine *e, int first_step, int nsteps, const mcx_weights *w, uint32_t seed, int nsteps_out,
+                         int nc_out, mcx_store **out, int64_t *index);
+int mcx_rows_resample(const float *rows, int nsteps, int nc, int np, const mcx_weights *w, uint32_t seed, int nsteps_out,
+                      int nc_out, mcx_store **out, int64_t *index);
+/* host only: the generalised Pareto fit of a tail.  x[0] <= ... <= x[n - 1] >= 0 are the exceedances over the cutoff.  Zhang and
+ * Stephens' estimator with the weak prior of Vehtari et al., in fp64, every sum in index order: m = 30 + floor(sqrt(n)),
+ * xstar = x[floor(n / 4 + 0.5) - 1]; theta_j = 1 / x[n - 1] + (1 - sqrt(m / (j - 0.5))) / (3 xstar), k_j = mean log1p(-theta_j x),
+ * l_j = n (log(-theta_j / k_j) - k_j - 1) for j = 1 ... m; w_j = 1 / sum_i exp(l_i - l_j); theta = sum theta_j w_j,
+ * k = mean log1p(-theta x), *sigma = -k / theta, *khat = (k n + 5) / (n + 10).  *flags: MCX_REWEIGHT_NO_TAIL with NaN in both
+ * when n < 5, xstar = 0 or x[n - 1] = 0; MCX_REWEIGHT_KHAT_HIGH when khat > 0.7 */
+int mcx_khat_of_tail(const double *x, long long n, double *khat, double *sigma, int *flags);
+/* tests only: the fixed-point weights q[nsteps * nc] and lwmax of the rows of a store (rows == NULL) or of host rows in MCout
+ * layout (s == NULL); exactly one of the two is given */
+int mcx_debug_reweight_q(mcx_store *s, const float *rows, int nsteps, int nc, int np, const mcx_weights *w, uint32_t *q,
+                         double *lwmax);
+/* host only: the launch geometry for N rows of ncol columns, nprobs probabilities and K draws (K = 0: no resample), computed by
+ * the functions the passes call.  k_rw_max and k_rw_q give a workgroup one scan tile of scan_tile_rows rows; the histogram
+ * passes take hist_prefixes target prefixes a launch on parameter tiles hist_tile_cols wide, their 64-bit bins within
+ * hist_lds_budget bytes of LDS (two workgroups and more per compute unit); k_rw_draw gives a lane one draw */
+typedef struct mcx_reweight_geometry {
+  long long block, scan_tile_rows, scan_tiles;
+  long long hist_targets, hist_prefixes, hist_launches, hist_tile_cols, hist_lds_bytes, hist_lds_budget;
+  long long tail_m, sort_tiles;
+  long long draw_workgroups;
+  long long scratch_bytes; /* of a reweight call, or of a resample call when K > 0 */
+} mcx_reweight_geometry;
+int mcx_debug_reweight_geometry(long long N, int ncol, int nprobs, long long K, mcx_reweight_geometry *g);
+/* one mcx_samples_reweight call and, when nsteps_out * nc_out > 0, one mcx_samples_resample call, their results let go.  ms[8],
+ * HIP events: 0 k_rw_max and its reducer, 1 k_rw_q and the scan, 2 the two moment passes, 3 the four histogram passes, 4 the
+ * sort of q, 5 k_rw_draw, 6 the whole reweight call, 7 the whole resample call */
+int mcx_debug_reweight_times(mcx_engine *e, int first_step, int nsteps, const mcx_weights *w, const double *probs, int nprobs,
+                             uint32_t seed, int nsteps_out, int nc_out, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -121,6 +121,25 @@ class EnergyGeometry(C.Structure):
                                             "chunk_blocks", "chunks", "col_chunk", "workgroups", "lds_bytes", "scratch_bytes")]
 
 
+class WeightsC(C.Structure):
+    """include/mcx.h mcx_weights"""
+    _fields_ = [("kind", C.c_int), ("logw", C.POINTER(C.c_float)), ("store", C.c_void_p), ("col", C.c_int), ("scale", C.c_double)]
+
+
+class ReweightResultC(C.Structure):
+    """include/mcx.h mcx_reweight_result"""
+    _fields_ = [("n", C.c_longlong), ("nzero", C.c_longlong), ("lwmax", C.c_double), ("sumq", C.c_longlong),
+                ("sumq2_hi", C.c_ulonglong), ("sumq2_lo", C.c_ulonglong), ("ess_kish", C.c_double), ("log_mean_w", C.c_double),
+                ("tail_m", C.c_longlong), ("khat", C.c_double), ("tail_sigma", C.c_double), ("flags", C.c_int), ("reserved", C.c_int)]
+
+
+class ReweightGeometry(C.Structure):
+    """include/mcx.h mcx_reweight_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "scan_tile_rows", "scan_tiles", "hist_targets", "hist_prefixes", "hist_launches",
+                                            "hist_tile_cols", "hist_lds_bytes", "hist_lds_budget", "tail_m", "sort_tiles",
+                                            "draw_workgroups", "scratch_bytes")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -287,6 +306,18 @@ def load():
         "mcx_debug_energy_sums": [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), dp],
         "mcx_debug_energy_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EnergyGeometry)],
         "mcx_debug_energy_times": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), dp],
+        "mcx_store_reweight": [vp, C.POINTER(WeightsC), dp, C.c_int, C.POINTER(ReweightResultC), vp, dp],
+        "mcx_samples_reweight": [vp, C.c_int, C.c_int, C.POINTER(WeightsC), dp, C.c_int, C.POINTER(ReweightResultC), vp, dp],
+        "mcx_rows_reweight": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(WeightsC), dp, C.c_int, C.POINTER(ReweightResultC), vp, dp],
+        "mcx_store_resample": [vp, C.POINTER(WeightsC), C.c_uint32, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64)],
+        "mcx_samples_resample": [vp, C.c_int, C.c_int, C.POINTER(WeightsC), C.c_uint32, C.c_int, C.c_int, C.POINTER(vp),
+                                 C.POINTER(C.c_int64)],
+        "mcx_rows_resample": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(WeightsC), C.c_uint32, C.c_int, C.c_int, C.POINTER(vp),
+                              C.POINTER(C.c_int64)],
+        "mcx_khat_of_tail": [dp, C.c_longlong, dp, dp, C.POINTER(C.c_int)],
+        "mcx_debug_reweight_q": [vp, fp, C.c_int, C.c_int, C.c_int, C.POINTER(WeightsC), u32p, dp],
+        "mcx_debug_reweight_geometry": [C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.POINTER(ReweightGeometry)],
+        "mcx_debug_reweight_times": [vp, C.c_int, C.c_int, C.POINTER(WeightsC), dp, C.c_int, C.c_uint32, C.c_int, C.c_int, dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

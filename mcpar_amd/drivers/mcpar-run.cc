@@ -15,6 +15,8 @@
 //             [--compare FILE --compare-to OTHER [--compare-nc NC]] [--compare-halves FILE] [--compare-iid]
 //             [--energy FILE --compare-to OTHER [--compare-nc NC]] [--energy-halves FILE] [--energy-n NA[,NB]] [--energy-perm P]
 //             [--energy-seed S] [--energy-with-ll] [--energy-raw]
+//             [--reweight-temper BETA | --reweight-source FILE.hip | --reweight-logw FILE] [--reweight FILE]
+//             [--resampled FILE] [--resampled-density FILE] [--resample-n K] [--resample-seed S]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -75,6 +77,14 @@
 // law under --energy-perm P (default 999) permutations of seed --energy-seed (default 0); --energy-with-ll adds log L to the
 // columns, --energy-raw leaves them unscaled.  FILE: a header and one line of the result's fields, then a header `name scale
 // flags` and one line per column p0 .. LL.  --energy-halves FILE: the first floor(nsamp / 2) kept steps against the rest.
+// --reweight FILE: the kept rows under importance weights, on the GPU (mcx_rows_reweight).  The weight
+// source is one of --reweight-temper BETA (log-weight (BETA - 1) log L: the power posterior L^BETA), --reweight-source FILE.hip
+// (a derive text with one output, the log-weight of a row; --derive-par is its `par`) and --reweight-logw FILE (one number per
+// row, in row order).  FILE: the first line is the global result -- n nzero lwmax sumq sumq2_hi sumq2_lo ess_kish log_mean_w
+// tail_m khat tail_sigma flags --, then one line per column p0 .. LL: name mean sd mcse_mean min max q05 q50 q95 flags.
+// --resampled FILE --resample-n K [--resample-seed S]: K rows drawn with replacement in proportion to the weights
+// (mcx_rows_resample, seed S, default 8675309) as the text of the sample output; --resampled-density FILE: the file of
+// --density for them.  All under the conditions of --summary.
 // --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
 // the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
 // one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
@@ -641,6 +651,134 @@ static int write_energy(const char *path, const char *other, int other_nc, const
   return 0;
 }
 
+// --reweight-temper / --reweight-source / --reweight-logw: the weight source of --reweight, --resampled and --resampled-density
+struct ReweightSource {
+  bool temper = false;
+  double beta = 1.0;
+  std::string source_file, logw_file;
+  bool given() const { return temper || !source_file.empty() || !logw_file.empty(); }
+};
+
+// --reweight FILE: the rows of MCout under importance weights -- the first line is the global result (n
+// nzero lwmax sumq sumq2_hi sumq2_lo ess_kish log_mean_w tail_m khat tail_sigma flags), then one row per column (name mean sd
+// mcse_mean min max, the quantiles at 0.05, 0.5 and 0.95, flags); --resampled FILE: K weighted draws as sample text;
+// --resampled-density FILE: their densities
+static int write_reweight(const ReweightSource &src, const std::vector<float> &par, const char *path, const char *resampled_path,
+                          const char *density_path, long long K, unsigned seed, const mcx_density_spec &dspec, MCout &rows, int nsamp,
+                          int nc, int np)
+{
+  static const double probs[3] = {0.05, 0.5, 0.95};
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--reweight: " << rows.size() << " rows stored, importance weights need nsamp * nc of them\n";
+    return 1;
+  }
+  const size_t N = (size_t)nsamp * nc, ncol = (size_t)np + 1;
+  mcx_weights w = {MCX_WEIGHT_LL, 0, 0, 0, src.beta - 1.0};
+  std::vector<float> logw;
+  mcx_store *ws = 0;
+  if (!src.logw_file.empty()) {
+    FILE *f = fopen(src.logw_file.c_str(), "r");
+    if (!f) {
+      std::cerr << "--reweight-logw: cannot read " << src.logw_file << "\n";
+      return 1;
+    }
+    double t;
+    while (fscanf(f, "%lf", &t) == 1) logw.push_back((float)t);
+    const bool clean = feof(f) != 0;
+    fclose(f);
+    if (!clean || logw.size() != N) {
+      std::cerr << "--reweight-logw: " << src.logw_file << " holds " << logw.size() << " numbers" << (clean ? "" : " before something that is not one")
+                << ", one per row = " << N << " are needed\n";
+      return 1;
+    }
+    w = mcx_weights{MCX_WEIGHT_HOST, logw.data(), 0, 0, 1.0};
+  } else if (!src.source_file.empty()) {
+    FILE *f = fopen(src.source_file.c_str(), "rb");
+    if (!f) {
+      std::cerr << "--reweight-source: cannot read " << src.source_file << "\n";
+      return 1;
+    }
+    std::string text;
+    char buf[4096];
+    for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, k);
+    fclose(f);
+    const mcx_derive spec = {MCX_DERIVE_SOURCE, 1, (int)par.size(), par.empty() ? 0 : par.data(), text.c_str()};
+    if (mcx_rows_derive(rows.getpset(0), nsamp, nc, np, &spec, &ws) != MCX_OK) {
+      std::cerr << "--reweight-source: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    w = mcx_weights{MCX_WEIGHT_STORE, 0, ws, 0, 1.0};
+  }
+  int rc = 0;
+  if (path) {
+    mcx_reweight_result r;
+    std::vector<mcx_col_reweight> cols(ncol);
+    std::vector<double> q(ncol * 3);
+    if (mcx_rows_reweight(rows.getpset(0), nsamp, nc, np, &w, probs, 3, &r, cols.data(), q.data()) != MCX_OK) {
+      std::cerr << "--reweight: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else {
+      FILE *f = fopen(path, "w");
+      if (!f) {
+        std::cerr << "cannot open " << path << "\n";
+        rc = 1;
+      } else {
+        fprintf(f, "%lld %lld %.17g %lld %llu %llu %.17g %.17g %lld %.17g %.17g %d\n", r.n, r.nzero, r.lwmax, r.sumq, r.sumq2_hi, r.sumq2_lo,
+                r.ess_kish, r.log_mean_w, r.tail_m, r.khat, r.tail_sigma, r.flags);
+        for (size_t c = 0; c < ncol; ++c)
+          fprintf(f, "%s %.17g %.17g %.17g %.9g %.9g %.17g %.17g %.17g %d\n", colname('p', (int)c, np).c_str(), cols[c].mean, cols[c].sd,
+                  cols[c].mcse_mean, (double)cols[c].min, (double)cols[c].max, q[c * 3], q[c * 3 + 1], q[c * 3 + 2], cols[c].flags);
+        if (fclose(f) != 0) rc = 1;
+      }
+    }
+  }
+  if (rc == 0 && (resampled_path || density_path)) {
+    // a store of K rows: as many "chains" as the largest divisor of K up to 1024 (its rows are draws, not chains)
+    int nc_out = 1;
+    for (int d = 1; d <= 1024 && d <= K; ++d)
+      if (K % d == 0) nc_out = d;
+    mcx_store *st = 0;
+    if (K < 1 || K / nc_out > 2147483647LL ||
+        mcx_rows_resample(rows.getpset(0), nsamp, nc, np, &w, seed, (int)(K / nc_out), nc_out, &st, 0) != MCX_OK) {
+      std::cerr << "--resampled: " << (K < 1 ? "--resample-n gives the number of draws, at least 1" : mcx_last_error()) << "\n";
+      rc = 1;
+    }
+    if (rc == 0 && resampled_path) {
+      std::vector<float> drawn((size_t)K * ncol);
+      size_t nb = 0;
+      std::vector<char> text;
+      if (mcx_store_copy(st, 0, (int)(K / nc_out), drawn.data()) != MCX_OK || mcx_format_rows(drawn.data(), (size_t)K, (int)ncol, 0, 0, &nb) != MCX_OK) rc = 1;
+      if (rc == 0) {
+        text.resize(nb);
+        if (mcx_format_rows(drawn.data(), (size_t)K, (int)ncol, text.data(), nb, &nb) != MCX_OK) rc = 1;
+      }
+      if (rc != 0) std::cerr << "--resampled: " << mcx_last_error() << "\n";
+      else {
+        FILE *f = fopen(resampled_path, "w");
+        if (!f) {
+          std::cerr << "cannot open " << resampled_path << "\n";
+          rc = 1;
+        } else {
+          if (nb && fwrite(text.data(), 1, nb, f) != nb) rc = 1;
+          if (fclose(f) != 0) rc = 1;
+        }
+      }
+    }
+    if (rc == 0 && density_path) {
+      const size_t n = (size_t)(dspec.n > 0 ? dspec.n : 1);
+      std::vector<mcx_col_density> cols(ncol);
+      std::vector<double> x(ncol * n), y(ncol * n);
+      if (mcx_store_density(st, &dspec, cols.data(), x.data(), y.data()) != MCX_OK) {
+        std::cerr << "--resampled-density: " << mcx_last_error() << "\n";
+        rc = 1;
+      } else rc = print_density(density_path, x, y, np, dspec.n, 'p');
+    }
+    mcx_store_destroy(st);
+  }
+  mcx_store_destroy(ws);
+  return rc;
+}
+
 // --derived-*: the files for the K derived columns of MCout's rows, through one derived store on the device
 static int write_derived(const mcx_derive &spec, const char *sum_path, const char *rank_path, const char *cov_path, const char *dens_path,
                          const mcx_density_spec &dspec, const char *dens2d_path, const mcx_density2d_spec &d2spec, MCout &rows, int nsamp,
@@ -815,6 +953,10 @@ int main(int argc, char *argv[])
   std::string energy_file, energy_halves_file;
   mcx_energy_spec energy_spec = {0, 0, 999, 0u, 0u};
   bool energy_opts = false;
+  ReweightSource reweight_source;
+  std::string reweight_file, resampled_file, resampled_density_file;
+  long long resample_n = 0;
+  unsigned resample_seed = 8675309u;
   std::vector<double> step_probs = {0.05, 0.5, 0.95};
   mcx_step_rule step_rule = {0.1, 0.1, 0.5, 0};
   bool settle = false;
@@ -940,6 +1082,14 @@ int main(int argc, char *argv[])
       energy_spec.flags |= MCX_ENERGY_RAW;
       energy_opts = true;
     }
+    else if (a == "--reweight") reweight_file = val();
+    else if (a == "--reweight-temper") { reweight_source.temper = true; reweight_source.beta = atof(val()); }
+    else if (a == "--reweight-source") reweight_source.source_file = val();
+    else if (a == "--reweight-logw") reweight_source.logw_file = val();
+    else if (a == "--resampled") resampled_file = val();
+    else if (a == "--resampled-density") resampled_density_file = val();
+    else if (a == "--resample-n") resample_n = atoll(val());
+    else if (a == "--resample-seed") resample_seed = (unsigned)strtoul(val(), 0, 10);
     else if (a == "--step-probs") {
       step_probs.clear();
       std::stringstream ss(val());
@@ -1069,6 +1219,23 @@ int main(int argc, char *argv[])
   if (want_compare && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--compare and --compare-halves need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  const bool want_resampled = !resampled_file.empty() || !resampled_density_file.empty();
+  const bool want_reweight = !reweight_file.empty() || want_resampled;
+  const int reweight_sources = (reweight_source.temper ? 1 : 0) + (reweight_source.source_file.empty() ? 0 : 1) + (reweight_source.logw_file.empty() ? 0 : 1);
+  if (want_reweight != (reweight_sources == 1) || reweight_sources > 1 || want_resampled != (resample_n > 0)) {
+    if (rank == 0)
+      std::cerr << "--reweight, --resampled and --resampled-density need exactly one of --reweight-temper BETA, --reweight-source FILE and "
+                   "--reweight-logw FILE, and the other way round; --resample-n K (K >= 1) goes with the two --resampled files\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (want_reweight && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--reweight and --resampled need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -1279,6 +1446,13 @@ int main(int argc, char *argv[])
       MPI_Finalize();
       return 2;
     }
+  }
+  if (want_reweight && write_reweight(reweight_source, derive_par, reweight_file.empty() ? 0 : reweight_file.c_str(),
+                                      resampled_file.empty() ? 0 : resampled_file.c_str(),
+                                      resampled_density_file.empty() ? 0 : resampled_density_file.c_str(), resample_n, resample_seed,
+                                      density_spec, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
   }
   if (!draws_file.empty() && write_draws(draws_file.c_str(), rslts, np, ndraw, draw_seed) != 0) {
     MPI_Finalize();

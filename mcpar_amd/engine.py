@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, Density2dSpecC,
-                   DensitySpecC, Derive, PlanItem, Profile, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, check, load)
+                   DensitySpecC, Derive, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -79,6 +79,14 @@ assert ENERGY_COL_DTYPE.itemsize == 16
 ENERGY_WITH_LL, ENERGY_RAW = 1, 2                                        # mcx_energy_spec.flags
 ENERGY_COL_NONFINITE, ENERGY_COL_CONSTANT, ENERGY_COL_UNUSED = 1, 2, 4   # mcx_energy_col.flags
 ENERGY_MAX_SIDE, ENERGY_MAX_PERM = 16384, 4095
+# include/mcx.h mcx_col_reweight
+REWEIGHT_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("mcse_mean", np.float64), ("min", np.float32), ("max", np.float32),
+                           ("flags", np.int32), ("reserved", np.int32)], align=True)
+assert REWEIGHT_DTYPE.itemsize == 40
+WEIGHT_HOST, WEIGHT_STORE, WEIGHT_LL = 1, 2, 3   # mcx_weights.kind
+REWEIGHT_NO_TAIL, REWEIGHT_KHAT_HIGH = 1, 2      # mcx_reweight_result.flags
+REWEIGHT_NONFINITE = 1                           # mcx_col_reweight.flags
+REWEIGHT_MAX_PROBS = 64
 STEP_MAX_PROBS = 8  # include/mcx.h MCX_STEP_MAX_PROBS
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
@@ -617,6 +625,14 @@ class DerivedStore:
         t, _, ncol = self.shape
         return _step_table_call(lambda *a: load().mcx_store_step_table(self.h, *a), t, ncol, probs)
 
+    def reweight(self, weights, probs=(0.05, 0.5, 0.95)):
+        """mcx_store_reweight: reweight_rows' dict for the rows of this store"""
+        return _reweight_call(lambda *a: load().mcx_store_reweight(self.h, *a), weights, self.shape[2], probs)
+
+    def resample(self, weights, nsteps_out, nc_out, seed, with_index=False):
+        """mcx_store_resample: resample_rows' DerivedStore of nsteps_out * nc_out weighted draws of this store's rows"""
+        return _resample_call(lambda *a: load().mcx_store_resample(self.h, *a), weights, nsteps_out, nc_out, seed, with_index)
+
     def compare(self, other, iid=False):
         """compare_stores(self, other)"""
         return compare_stores(self, other, iid)
@@ -1011,6 +1027,107 @@ def debug_energy_geometry(n_a, n_b, nused, nperm):
     g = EnergyGeometry()
     check(load().mcx_debug_energy_geometry(n_a, n_b, nused, nperm, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in EnergyGeometry._fields_}
+
+
+# ---- importance weights on a store (include/mcx.h) ----
+class Weights:
+    """an mcx_weights and what it points to"""
+
+    def __init__(self, kind, logw=None, store=None, col=0, scale=1.0):
+        self.logw = None if logw is None else np.ascontiguousarray(np.asarray(logw, np.float32).reshape(-1))
+        self.store = store
+        self.c = WeightsC(kind, None if self.logw is None else _fp(self.logw), None if store is None else store.h, col, scale)
+
+
+def weights_host(logw):
+    """MCX_WEIGHT_HOST: one log-weight per row, in row order (step-major, the chain within the step)"""
+    return Weights(WEIGHT_HOST, logw=logw)
+
+
+def weights_column(store, col, scale=1.0):
+    """MCX_WEIGHT_STORE: scale times column col of a DerivedStore of the same steps and chains (col = ncol - 1: its log L)"""
+    return Weights(WEIGHT_STORE, store=store, col=col, scale=scale)
+
+
+def weights_loglike(scale):
+    """MCX_WEIGHT_LL: scale times the rows' own log L column (scale = beta - 1: the power posterior L^beta)"""
+    return Weights(WEIGHT_LL, scale=scale)
+
+
+def _reweight_call(fn, weights, ncol, probs):
+    """fn(w, probs, nprobs, res, cols, quantiles) of one of the three reweight entry points -> the dict of
+    mcx_reweight_result's fields (n, nzero, lwmax, sumq, sumq2_hi, sumq2_lo, sumq2 as a Python integer, ess_kish, log_mean_w,
+    tail_m, khat, tail_sigma, flags), cols (arrays [ncol]: mean, sd, mcse_mean, min, max, flags) and quantiles [ncol, nprobs]"""
+    p, pp = _probs(probs)
+    res = ReweightResultC()
+    cols = np.zeros(max(int(ncol), 1), REWEIGHT_DTYPE)
+    q = np.zeros((max(int(ncol), 1), len(p)), np.float64)
+    check(fn(None if weights is None else C.byref(weights.c), pp if len(p) else None, len(p), C.byref(res),
+             cols.ctypes.data_as(C.c_void_p), _dp(q) if len(p) else None))
+    out = {name: getattr(res, name) for name, _ in ReweightResultC._fields_ if name != "reserved"}
+    out["sumq2"] = (int(res.sumq2_hi) << 64) | int(res.sumq2_lo)
+    out["cols"] = {name: cols[name].copy() for name in REWEIGHT_DTYPE.names if name != "reserved"}
+    out["quantiles"] = q
+    return out
+
+
+def reweight_rows(rows, nsteps, nc, weights, probs=(0.05, 0.5, 0.95)):
+    """mcx_rows_reweight: rows [nsteps * nc, np + 1] (MCout layout) under importance weights -- Kish's effective size, the
+    log of the mean weight, the Pareto tail index k-hat of the largest weights, and per column the weighted mean, sd, error
+    of the mean, min, max and exact weighted quantiles (no interpolation)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    return _reweight_call(lambda *a: load().mcx_rows_reweight(_fp(rows), nsteps, nc, ncol - 1, *a), weights, ncol, probs)
+
+
+def _resample_call(fn, weights, nsteps_out, nc_out, seed, with_index):
+    """fn(w, seed, nsteps_out, nc_out, out, index) of one of the three resample entry points -> the DerivedStore, or
+    (DerivedStore, index [nsteps_out * nc_out] int64) with with_index"""
+    h = C.c_void_p()
+    index = np.empty(max(int(nsteps_out) * int(nc_out), 0), np.int64) if with_index else None
+    check(fn(None if weights is None else C.byref(weights.c), seed, nsteps_out, nc_out, C.byref(h),
+             index.ctypes.data_as(C.POINTER(C.c_int64)) if with_index else None))
+    st = DerivedStore(h)
+    return (st, index) if with_index else st
+
+
+def resample_rows(rows, nsteps, nc, weights, nsteps_out, nc_out, seed, with_index=False):
+    """mcx_rows_resample: nsteps_out * nc_out rows of rows [nsteps * nc, np + 1] drawn with replacement in proportion to their
+    weights, as a DerivedStore of shape (nsteps_out, nc_out, np + 1) whose rows are exchangeable draws, not chains"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    return _resample_call(lambda *a: load().mcx_rows_resample(_fp(rows), nsteps, nc, rows.shape[1] - 1, *a), weights, nsteps_out,
+                          nc_out, seed, with_index)
+
+
+def khat_of_tail(x):
+    """mcx_khat_of_tail (host only): (khat, sigma, flags) of the rising exceedances x of a tail over its cutoff"""
+    x = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1))
+    k, s, f = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    check(load().mcx_khat_of_tail(_dp(x), len(x), C.byref(k), C.byref(s), C.byref(f)))
+    return k.value, s.value, f.value
+
+
+def debug_reweight_q(weights, rows=None, nsteps=0, nc=0, store=None):
+    """mcx_debug_reweight_q: (q [N] uint32, lwmax) -- the fixed-point weights of host rows (rows, nsteps, nc) or of a
+    DerivedStore (store)"""
+    if store is not None:
+        t, c, _ = store.shape
+        q, mx = np.zeros(t * c, np.uint32), C.c_double(0.0)
+        check(load().mcx_debug_reweight_q(store.h, None, 0, 0, 0, C.byref(weights.c), q.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(mx)))
+        return q, mx.value
+    rows = np.ascontiguousarray(rows, np.float32)
+    q, mx = np.zeros(max(nsteps * nc, 1), np.uint32), C.c_double(0.0)
+    check(load().mcx_debug_reweight_q(None, _fp(rows), nsteps, nc, rows.shape[1] - 1, C.byref(weights.c),
+                                      q.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(mx)))
+    return q[:nsteps * nc], mx.value
+
+
+def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
+    """mcx_debug_reweight_geometry (host only): the launch geometry of a reweight of N rows of ncol columns with nprobs
+    probabilities and of a resample of K draws, as a dict of include/mcx.h's fields"""
+    g = ReweightGeometry()
+    check(load().mcx_debug_reweight_geometry(N, ncol, nprobs, K, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in ReweightGeometry._fields_}
 
 
 def debug_store_geometry(np_, nout, nsteps, nc):
@@ -1594,6 +1711,27 @@ class Engine:
         uploads, k_energy_pairs, the reducer, the whole call (host clock)"""
         spec, ms = _energy_spec(**kw), np.zeros(7)
         check(load().mcx_debug_energy_times(self.h, first_a, nsteps_a, first_b, nsteps_b, C.byref(spec), _dp(ms)))
+        return ms
+
+    def reweight(self, weights, probs=(0.05, 0.5, 0.95), first_step=0, nsteps=None):
+        """mcx_samples_reweight: reweight_rows' dict for kept steps [first_step, first_step + nsteps)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _reweight_call(lambda *a: load().mcx_samples_reweight(self.h, first_step, nsteps, *a), weights, self.np + 1, probs)
+
+    def resample(self, weights, nsteps_out, nc_out, seed, with_index=False, first_step=0, nsteps=None):
+        """mcx_samples_resample: resample_rows' DerivedStore of weighted draws of kept steps [first_step, first_step + nsteps)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _resample_call(lambda *a: load().mcx_samples_resample(self.h, first_step, nsteps, *a), weights, nsteps_out, nc_out,
+                              seed, with_index)
+
+    def reweight_times(self, weights, probs=(0.05, 0.5, 0.95), nsteps_out=0, nc_out=0, seed=0, first_step=0, nsteps=None):
+        """mcx_debug_reweight_times: ms[8] of one reweight() and, with nsteps_out * nc_out > 0, one resample() call -- the
+        maximum, q and the scan, the moment passes, the histogram passes, the sort of q, the draw, the whole reweight, the whole
+        resample"""
+        p, pp = _probs(probs)
+        ms = np.zeros(8)
+        self._on_store(load().mcx_debug_reweight_times, first_step, nsteps, C.byref(weights.c), pp if len(p) else None, len(p), seed,
+                       nsteps_out, nc_out, _dp(ms))
         return ms
 
     def step_table_times(self, first_step=0, nsteps=None, probs=(0.05, 0.5, 0.95)):
