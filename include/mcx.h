@@ -1221,6 +1221,87 @@ int mcx_debug_reweight_geometry(long long N, int ncol, int nprobs, long long K, 
 int mcx_debug_reweight_times(mcx_engine *e, int first_step, int nsteps, const mcx_weights *w, const double *probs, int nprobs,
                              uint32_t seed, int nsteps_out, int nc_out, double *ms);
 
+/* ---- interval estimates of the sample store, on the device ----------
+ * What the table of posterior::summarise_draws / arviz.summary holds beyond mcx_samples_summary.  Columns as there (the np
+ * parameters, then log L), N = nsteps * nc values per column, nsteps >= 4.  s(0) <= ... <= s(N - 1) are the column's floats in
+ * the key order of the rank summary: -0 and +0 are one value (reported as +0), every NaN sorts last.
+ *   HDI of mass p, 0 < p < 1 (arviz's hdi): span m = min(floor(p N), N - 1); w(i) = double(s(i + m)) - double(s(i)) for 0 <= i <
+ *              N - m; index = the smallest i with the smallest w; lo = s(index), hi = s(index + m), width = w(index)
+ *   ess_sd, mcse_sd (posterior's): c2 = float((double(x) - mean)^2), ess_sd and ess_sd_lag the ess and ess_lag of the store of
+ *              c2 as mcx_samples_summary defines them; mcse_sd = sqrt((N - 1) / N sd_c2^2 / ess_sd / mean_c2 / 4)
+ *   ess_q, mcse_q of a probability p (posterior's ess_quantile, mcse_quantile): q = mcx_samples_summary's type-7 quantile, bit
+ *              for bit; ess_q and ess_q_lag those of the store of the indicators double(x) <= q (1.0f / 0.0f); u_lo, u_hi = the
+ *              quantiles of 0.1586553 and 0.8413447 of the beta law (ess_q p + 1, ess_q (1 - p) + 1), by mcx_beta_quantile;
+ *              k_lo = max(floor(u_lo N), 1) - 1, k_hi = min(ceil(u_hi N), N) - 1; s_lo = s(k_lo), s_hi = s(k_hi);
+ *              mcse_q = (double(s_hi) - double(s_lo)) / 2
+ * A column holding an inf or NaN has MCX_SUMMARY_NONFINITE, NaN in every double and float and -1 in index, k_lo and k_hi (span
+ * stays m).  A transformed column that is constant within every half-chain gives NaN ess and mcse, NaN u and s and -1 ranks for
+ * what is built on it.  A constant column's HDI is lo = hi, width 0, index 0. */
+enum { MCX_INTERVAL_MAX_MASSES = 8, MCX_INTERVAL_MAX_PROBS = 8, MCX_INTERVAL_TIMES = 12 };
+typedef struct mcx_interval_spec {
+  int nmass;           /* 0 to MCX_INTERVAL_MAX_MASSES */
+  int nprobs;          /* 0 to MCX_INTERVAL_MAX_PROBS */
+  const double *mass;  /* nmass masses in (0, 1) */
+  const double *probs; /* nprobs probabilities in [0, 1] */
+} mcx_interval_spec;
+typedef struct mcx_col_intervals {
+  double mean, sd;         /* mcx_samples_summary's */
+  double ess_sd, mcse_sd;
+  int ess_sd_lag, flags;   /* MCX_SUMMARY_* */
+} mcx_col_intervals;
+typedef struct mcx_col_hdi {
+  double width;
+  long long index, span;
+  float lo, hi;
+} mcx_col_hdi;
+typedef struct mcx_col_quantile_se {
+  double q, ess_q, u_lo, u_hi, mcse_q;
+  long long k_lo, k_hi;
+  float s_lo, s_hi;
+  int ess_q_lag, reserved;
+} mcx_col_quantile_se;
+/* Steps [first_step, first_step + nsteps) of the store.  cols[np + 1]; hdi[(np + 1) * nmass] and qse[(np + 1) * nprobs], row =
+ * column (each may be NULL when its count is 0).  MCX_ERR_INVALID, before a device is touched, for nsteps < 4, a mass outside
+ * (0, 1), a probability outside [0, 1], a count outside its range and a NULL output, and in the cases mcx_samples_summary
+ * refuses; MCX_ERR_UNSUPPORTED for N >= 2^31; MCX_ERR_ALLOC, with the bytes needed in mcx_last_error, when the scratch (4 N (np +
+ * 1) bytes of transformed store, then 8 N bytes of keys per column sorted at a time) does not fit even one column at a time.
+ * The same store and arguments give the same bytes. */
+int mcx_samples_intervals(mcx_engine *e, int first_step, int nsteps, const mcx_interval_spec *spec, mcx_col_intervals *cols,
+                          mcx_col_hdi *hdi, mcx_col_quantile_se *qse);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows) */
+int mcx_rows_intervals(const float *rows, int nsteps, int nc, int np, const mcx_interval_spec *spec, mcx_col_intervals *cols,
+                       mcx_col_hdi *hdi, mcx_col_quantile_se *qse);
+/* and for the whole of a derived store */
+int mcx_store_intervals(mcx_store *s, const mcx_interval_spec *spec, mcx_col_intervals *cols, mcx_col_hdi *hdi,
+                        mcx_col_quantile_se *qse);
+/* host only: *x = the quantile of probability p of the beta law (a, b), the inverse of the regularised incomplete beta function
+ * in fp64, for 0 <= p <= 1 and finite a >= 1, b >= 1 (MCX_ERR_INVALID and NaN otherwise) */
+int mcx_beta_quantile(double p, double a, double b, double *x);
+/* host only: u_lo, u_hi, k_lo, k_hi of the definition above for N values, a probability and an effective size; an ess that is
+ * not a positive finite number gives NaN and -1 */
+int mcx_intervals_quantile_ranks(long long N, double prob, double ess, double *u_lo, double *u_hi, long long *k_lo, long long *k_hi);
+/* tests only, host only: the launch geometry of an intervals call, from the function the launches use */
+typedef struct mcx_intervals_geometry {
+  long long block;                 /* threads per workgroup */
+  long long window_tile;           /* window starts per workgroup of k_hdi_windows */
+  long long window_tiles;          /* its grid.x, ceil(N / window_tile); grid.y = the columns of a group */
+  long long slab_entries;          /* (w, i) pairs per column between k_hdi_windows and k_hdi_reduce: nmass * window_tiles */
+  long long slab_bytes;            /* 16 bytes each */
+  long long reduce_workgroups;     /* of k_hdi_reduce per column: nmass */
+  long long pick_ranks;            /* ranks per column read by k_iv_pick: 2 nprobs */
+  long long transforms;            /* k_iv_transform sweeps, each followed by the summary's mixing passes: 1 + nprobs */
+  long long sort_tiles;            /* sort tiles of 8192 keys per column */
+  long long step_chunk, grid_y;    /* steps per workgroup of the transform and key sweeps, and their grid.y */
+  long long group_cols, groups;    /* columns sorted at a time at most (MCX_RANK_GROUP_COLS caps it), and the groups that makes */
+  long long store_scratch_bytes;   /* the transformed store */
+  long long scratch_bytes_per_col; /* keys, counts, slab and outputs of one column of a group */
+} mcx_intervals_geometry;
+int mcx_debug_intervals_geometry(int nsteps, int nc, int np, int nmass, int nprobs, mcx_intervals_geometry *g);
+/* mcx_samples_intervals with HIP events around its stages, for tools/intervals_bench.py.  ms[MCX_INTERVAL_TIMES]: 0 the
+ * summary's spread passes, 1 the k_iv_transform sweeps, 2 the mixing passes behind them, 3 k_iv_keys, 4 .. 7 the sort passes,
+ * 8 k_hdi_windows, 9 k_hdi_reduce, 10 k_iv_pick, 11 the whole call */
+int mcx_debug_intervals_times(mcx_engine *e, int first_step, int nsteps, const mcx_interval_spec *spec, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

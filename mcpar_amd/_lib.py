@@ -140,6 +140,18 @@ class ReweightGeometry(C.Structure):
                                             "draw_workgroups", "scratch_bytes")]
 
 
+class IntervalSpecC(C.Structure):
+    """include/mcx.h mcx_interval_spec"""
+    _fields_ = [("nmass", C.c_int), ("nprobs", C.c_int), ("mass", C.POINTER(C.c_double)), ("probs", C.POINTER(C.c_double))]
+
+
+class IntervalsGeometry(C.Structure):
+    """include/mcx.h mcx_intervals_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "window_tile", "window_tiles", "slab_entries", "slab_bytes", "reduce_workgroups",
+                                            "pick_ranks", "transforms", "sort_tiles", "step_chunk", "grid_y", "group_cols", "groups",
+                                            "store_scratch_bytes", "scratch_bytes_per_col")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -318,6 +330,13 @@ def load():
         "mcx_debug_reweight_q": [vp, fp, C.c_int, C.c_int, C.c_int, C.POINTER(WeightsC), u32p, dp],
         "mcx_debug_reweight_geometry": [C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.POINTER(ReweightGeometry)],
         "mcx_debug_reweight_times": [vp, C.c_int, C.c_int, C.POINTER(WeightsC), dp, C.c_int, C.c_uint32, C.c_int, C.c_int, dp],
+        "mcx_samples_intervals": [vp, C.c_int, C.c_int, C.POINTER(IntervalSpecC), vp, vp, vp],
+        "mcx_rows_intervals": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(IntervalSpecC), vp, vp, vp],
+        "mcx_store_intervals": [vp, C.POINTER(IntervalSpecC), vp, vp, vp],
+        "mcx_beta_quantile": [C.c_double, C.c_double, C.c_double, dp],
+        "mcx_intervals_quantile_ranks": [C.c_longlong, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+        "mcx_debug_intervals_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(IntervalsGeometry)],
+        "mcx_debug_intervals_times": [vp, C.c_int, C.c_int, C.POINTER(IntervalSpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

@@ -17,6 +17,7 @@
 //             [--energy-seed S] [--energy-with-ll] [--energy-raw]
 //             [--reweight-temper BETA | --reweight-source FILE.hip | --reweight-logw FILE] [--reweight FILE]
 //             [--resampled FILE] [--resampled-density FILE] [--resample-n K] [--resample-seed S]
+//             [--intervals FILE [--hdi P1,P2,...] [--interval-probs p1,p2,...]]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -85,6 +86,10 @@
 // --resampled FILE --resample-n K [--resample-seed S]: K rows drawn with replacement in proportion to the weights
 // (mcx_rows_resample, seed S, default 8675309) as the text of the sample output; --resampled-density FILE: the file of
 // --density for them.  All under the conditions of --summary.
+// --intervals FILE: the interval estimates of the kept rows on the GPU (mcx_rows_intervals), one line per
+// column p0 .. LL under a header: name mean sd mcse_sd ess_sd, then hdi<P>_lo hdi<P>_hi for every mass P of --hdi (default 0.9; up
+// to 8), then q<p> mcse_q<p> ess_q<p> for every probability p of --interval-probs (default 0.05,0.5,0.95; up to 8), then flags.
+// Under the conditions of --summary.
 // --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
 // the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
 // one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
@@ -174,6 +179,42 @@ static int write_rank_summary(const char *path, MCout &rows, int nsamp, int nc, 
     return 1;
   }
   return print_rank_summary(path, cols, np, 'p');
+}
+
+// --intervals: the highest-density intervals and the Monte-Carlo errors of the sd and the quantiles of MCout's rows
+static int write_intervals(const char *path, const std::vector<double> &mass, const std::vector<double> &probs, MCout &rows, int nsamp,
+                           int nc, int np)
+{
+  const size_t ncol = (size_t)np + 1, nm = mass.size(), nq = probs.size();
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 4) {
+    std::cerr << "--intervals: " << rows.size() << " rows stored, the intervals need nsamp * nc of them and nsamp >= 4\n";
+    return 1;
+  }
+  const mcx_interval_spec spec = {(int)nm, (int)nq, mass.data(), probs.data()};
+  std::vector<mcx_col_intervals> cols(ncol);
+  std::vector<mcx_col_hdi> hdi(ncol * nm + 1);
+  std::vector<mcx_col_quantile_se> qse(ncol * nq + 1);
+  if (mcx_rows_intervals(rows.getpset(0), nsamp, nc, np, &spec, cols.data(), hdi.data(), qse.data()) != MCX_OK) {
+    std::cerr << "--intervals: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "name mean sd mcse_sd ess_sd");
+  for (double m : mass) fprintf(f, " hdi%g_lo hdi%g_hi", m, m);
+  for (double p : probs) fprintf(f, " q%g mcse_q%g ess_q%g", p, p, p);
+  fprintf(f, " flags\n");
+  for (size_t c = 0; c < ncol; ++c) {
+    const mcx_col_intervals &s = cols[c];
+    fprintf(f, "%s %.17g %.17g %.17g %.17g", colname('p', (int)c, np).c_str(), s.mean, s.sd, s.mcse_sd, s.ess_sd);
+    for (size_t j = 0; j < nm; ++j) fprintf(f, " %.9g %.9g", hdi[c * nm + j].lo, hdi[c * nm + j].hi);
+    for (size_t k = 0; k < nq; ++k) fprintf(f, " %.17g %.17g %.17g", qse[c * nq + k].q, qse[c * nq + k].mcse_q, qse[c * nq + k].ess_q);
+    fprintf(f, " %d\n", s.flags);
+  }
+  return fclose(f) == 0 ? 0 : 1;
 }
 
 static int print_covariance(const char *path, const std::vector<double> &mean, const std::vector<double> &cov, int np, char prefix)
@@ -946,7 +987,8 @@ int main(int argc, char *argv[])
   int clip_nc = 1024;
   std::string chain_table_file, kept_chains_file, kept_summary_file;
   mcx_chain_rule chain_rule = {5.0, 1, 0, 0};
-  std::string step_table_file;
+  std::string step_table_file, intervals_file;
+  std::vector<double> hdi_mass = {0.9}, interval_probs = {0.05, 0.5, 0.95};
   std::string compare_file, compare_to_file, compare_halves_file;
   int compare_nc = 0;
   bool compare_iid = false;
@@ -1090,6 +1132,13 @@ int main(int argc, char *argv[])
     else if (a == "--resampled-density") resampled_density_file = val();
     else if (a == "--resample-n") resample_n = atoll(val());
     else if (a == "--resample-seed") resample_seed = (unsigned)strtoul(val(), 0, 10);
+    else if (a == "--intervals") intervals_file = val();
+    else if (a == "--hdi" || a == "--interval-probs") {
+      std::vector<double> &list = a == "--hdi" ? hdi_mass : interval_probs;
+      list.clear();
+      std::stringstream ss(val());
+      for (std::string tok; std::getline(ss, tok, ',');) list.push_back(atof(tok.c_str()));
+    }
     else if (a == "--step-probs") {
       step_probs.clear();
       std::stringstream ss(val());
@@ -1178,6 +1227,13 @@ int main(int argc, char *argv[])
   if (want_chains && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--chain-table, --kept-chains and --kept-summary need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!intervals_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--intervals needs the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -1398,6 +1454,10 @@ int main(int argc, char *argv[])
   if (want_chains && write_chains(chain_rule, chain_table_file.empty() ? 0 : chain_table_file.c_str(),
                                   kept_chains_file.empty() ? 0 : kept_chains_file.c_str(),
                                   kept_summary_file.empty() ? 0 : kept_summary_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (!intervals_file.empty() && write_intervals(intervals_file.c_str(), hdi_mass, interval_probs, rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, Density2dSpecC,
-                   DensitySpecC, Derive, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
+                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -88,6 +88,15 @@ REWEIGHT_NO_TAIL, REWEIGHT_KHAT_HIGH = 1, 2      # mcx_reweight_result.flags
 REWEIGHT_NONFINITE = 1                           # mcx_col_reweight.flags
 REWEIGHT_MAX_PROBS = 64
 STEP_MAX_PROBS = 8  # include/mcx.h MCX_STEP_MAX_PROBS
+# include/mcx.h mcx_col_intervals, mcx_col_hdi, mcx_col_quantile_se
+INTERVALS_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("ess_sd", np.float64), ("mcse_sd", np.float64),
+                            ("ess_sd_lag", np.int32), ("flags", np.int32)], align=True)
+HDI_DTYPE = np.dtype([("width", np.float64), ("index", np.int64), ("span", np.int64), ("lo", np.float32), ("hi", np.float32)], align=True)
+QUANTILE_SE_DTYPE = np.dtype([("q", np.float64), ("ess_q", np.float64), ("u_lo", np.float64), ("u_hi", np.float64), ("mcse_q", np.float64),
+                              ("k_lo", np.int64), ("k_hi", np.int64), ("s_lo", np.float32), ("s_hi", np.float32),
+                              ("ess_q_lag", np.int32), ("reserved", np.int32)], align=True)
+assert INTERVALS_DTYPE.itemsize == 40 and HDI_DTYPE.itemsize == 32 and QUANTILE_SE_DTYPE.itemsize == 72
+INTERVAL_MAX_MASSES, INTERVAL_MAX_PROBS, INTERVAL_TIMES = 8, 8, 12
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
@@ -633,6 +642,10 @@ class DerivedStore:
         """mcx_store_resample: resample_rows' DerivedStore of nsteps_out * nc_out weighted draws of this store's rows"""
         return _resample_call(lambda *a: load().mcx_store_resample(self.h, *a), weights, nsteps_out, nc_out, seed, with_index)
 
+    def intervals(self, hdi=(0.9,), probs=(0.05, 0.5, 0.95)):
+        """mcx_store_intervals: Engine.intervals' dict for the columns of this store"""
+        return _intervals_call(lambda *a: load().mcx_store_intervals(self.h, *a), self.shape[2], hdi, probs)
+
     def compare(self, other, iid=False):
         """compare_stores(self, other)"""
         return compare_stores(self, other, iid)
@@ -1120,6 +1133,62 @@ def debug_reweight_q(weights, rows=None, nsteps=0, nc=0, store=None):
     check(load().mcx_debug_reweight_q(None, _fp(rows), nsteps, nc, rows.shape[1] - 1, C.byref(weights.c),
                                       q.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(mx)))
     return q[:nsteps * nc], mx.value
+
+
+class IntervalSpec:
+    """mcx_interval_spec: the masses of the highest-density intervals and the probabilities of the quantiles with an error"""
+
+    def __init__(self, hdi=(0.9,), probs=(0.05, 0.5, 0.95)):
+        self.mass, mp = _probs(hdi)
+        self.probs, pp = _probs(probs)
+        self.c = IntervalSpecC(len(self.mass), len(self.probs), mp if len(self.mass) else None, pp if len(self.probs) else None)
+
+
+def _intervals_call(fn, ncol, hdi, probs):
+    """fn(spec, cols, hdi, qse) of one of the three intervals entry points -> a dict of arrays [ncol]: mean, sd, ess_sd,
+    mcse_sd, ess_sd_lag, flags; hdi: a dict of arrays [ncol, nmass] (width, index, span, lo, hi); quantiles: a dict of arrays
+    [ncol, nprobs] (q, ess_q, u_lo, u_hi, mcse_q, k_lo, k_hi, s_lo, s_hi, ess_q_lag)"""
+    spec = IntervalSpec(hdi, probs)
+    ncol = max(int(ncol), 1)
+    cols = np.zeros(ncol, INTERVALS_DTYPE)
+    h = np.zeros((ncol, len(spec.mass)), HDI_DTYPE)
+    q = np.zeros((ncol, len(spec.probs)), QUANTILE_SE_DTYPE)
+    check(fn(C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p) if h.size else None,
+             q.ctypes.data_as(C.c_void_p) if q.size else None))
+    out = {name: cols[name].copy() for name in INTERVALS_DTYPE.names}
+    out["hdi"] = {name: h[name].copy() for name in HDI_DTYPE.names}
+    out["quantiles"] = {name: q[name].copy() for name in QUANTILE_SE_DTYPE.names if name != "reserved"}
+    return out
+
+
+def rows_intervals(rows, nsteps, nc, hdi=(0.9,), probs=(0.05, 0.5, 0.95)):
+    """mcx_rows_intervals: Engine.intervals' dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    return _intervals_call(lambda *a: load().mcx_rows_intervals(_fp(rows), nsteps, nc, ncol - 1, *a), ncol, hdi, probs)
+
+
+def beta_quantile(p, a, b):
+    """mcx_beta_quantile (host only): the quantile of probability p of the beta law (a, b), a >= 1 and b >= 1, float64"""
+    x = C.c_double()
+    check(load().mcx_beta_quantile(p, a, b, C.byref(x)))
+    return x.value
+
+
+def intervals_quantile_ranks(N, prob, ess):
+    """mcx_intervals_quantile_ranks (host only): (u_lo, u_hi, k_lo, k_hi) around the quantile of probability prob of N sorted
+    values whose indicator has the effective size ess"""
+    ul, uh, kl, kh = C.c_double(), C.c_double(), C.c_longlong(), C.c_longlong()
+    check(load().mcx_intervals_quantile_ranks(N, prob, ess, C.byref(ul), C.byref(uh), C.byref(kl), C.byref(kh)))
+    return ul.value, uh.value, kl.value, kh.value
+
+
+def debug_intervals_geometry(nsteps, nc, np_, nmass=1, nprobs=3):
+    """mcx_debug_intervals_geometry (host only): the launch geometry of an intervals call on nsteps steps of nc chains of np_
+    parameters with nmass masses and nprobs probabilities, as a dict of include/mcx.h's fields"""
+    g = IntervalsGeometry()
+    check(load().mcx_debug_intervals_geometry(nsteps, nc, np_, nmass, nprobs, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in IntervalsGeometry._fields_}
 
 
 def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
@@ -1723,6 +1792,20 @@ class Engine:
         nsteps = self._nsteps(first_step, nsteps)
         return _resample_call(lambda *a: load().mcx_samples_resample(self.h, first_step, nsteps, *a), weights, nsteps_out, nc_out,
                               seed, with_index)
+
+    def intervals(self, hdi=(0.9,), probs=(0.05, 0.5, 0.95), first_step=0, nsteps=None):
+        """mcx_samples_intervals: per column (the parameters, then log L) of kept steps [first_step, first_step + nsteps) the
+        highest-density interval of every mass in hdi and the Monte-Carlo errors of the sd and of the quantiles of probs, with
+        the effective sizes behind them (_intervals_call lists the fields)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _intervals_call(lambda *a: load().mcx_samples_intervals(self.h, first_step, nsteps, *a), self.np + 1, hdi, probs)
+
+    def intervals_times(self, hdi=(0.9,), probs=(0.05, 0.5, 0.95), first_step=0, nsteps=None):
+        """mcx_debug_intervals_times: the 12 stage times of one intervals() call in ms (include/mcx.h lists them)"""
+        spec = IntervalSpec(hdi, probs)
+        ms = np.zeros(INTERVAL_TIMES)
+        self._on_store(load().mcx_debug_intervals_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
+        return ms
 
     def reweight_times(self, weights, probs=(0.05, 0.5, 0.95), nsteps_out=0, nc_out=0, seed=0, first_step=0, nsteps=None):
         """mcx_debug_reweight_times: ms[8] of one reweight() and, with nsteps_out * nc_out > 0, one resample() call -- the
