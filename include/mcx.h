@@ -1302,6 +1302,83 @@ int mcx_debug_intervals_geometry(int nsteps, int nc, int np, int nmass, int npro
  * 8 k_hdi_windows, 9 k_hdi_reduce, 10 k_iv_pick, 11 the whole call */
 int mcx_debug_intervals_times(mcx_engine *e, int first_step, int nsteps, const mcx_interval_spec *spec, double *ms);
 
+/* ---- lagged covariance of the sample store and the multivariate ESS, on the device ----------
+ * Columns as in mcx_samples_summary (the np parameters, then log L; ncol = np + 1), T = nsteps kept steps of nc chains, N = T nc
+ * rows, m the column means (mcx_samples_summary's bits).  For 0 <= t <= T - 1
+ *   G(t)[i][j] = (1 / N) sum over chains c and steps s <= T - 1 - t of (x[c, s, i] - m_i) (x[c, s + t, j] - m_j)
+ * in fp64, two passes: the globally centred, biased estimator for replicated chains.  G(t)[j][i] is the lag -t entry; G(0) is
+ * symmetric in its bits, and G(0) N / (N - 1) is mcx_samples_covariance's matrix within its bound.
+ * On the chosen columns -- the finite, non-constant parameters, and log L when with_ll is set -- with S(t) = (G(t) + G(t)^T) / 2,
+ * P(k) = S(2k) + S(2k + 1), Sigma_k = -S(0) + 2 sum_{i <= k} P(i) and K = floor((min(T - 1, max_lag) - 1) / 2):
+ *   s       the smallest k <= K at which Sigma_k is positive definite (every pivot of a double Cholesky factorisation > 0);
+ *           none: MCX_MESS_NOT_PD, k_used = s = -1, Sigma, mess, ess and mcse NaN
+ *   k_used  the last k of s, s + 1, ... <= K at which Sigma_k is still positive definite and log det Sigma_k > log det Sigma_{k-1};
+ *           Sigma = Sigma_k_used, lags_used = 2 k_used + 2; MCX_MESS_TRUNCATED when k reached K with no test failed
+ *   mess = N exp((log det Lambda - log det Sigma) / p), Lambda = G(0) N / (N - 1) on the p chosen columns (not positive definite:
+ *           MCX_MESS_LAMBDA_SINGULAR and a NaN mess); ess_j = N Lambda_jj / Sigma_jj; mcse_j = sqrt(Sigma_jj / N); Sigma / N is
+ *           the covariance of the Monte-Carlo error of the mean vector
+ * A column holding an inf or NaN has MCX_SUMMARY_NONFINITE, a NaN mean, and NaN in its row and column of every G(t); every other
+ * entry is what it would be without that column.  A constant column (G(0)_jj = 0) has MCX_LAGCOV_CONSTANT.  Both are left out of
+ * Sigma and the determinants (their rows and columns of sigma, their ess and mcse are NaN).  Lags are computed a window at a
+ * time, only as far as the walk (and nlags_out) needs them: lags_computed says how many.  Every lag computed is kept on the host
+ * until the call returns, 8 ncol^2 bytes each: on a long unmixed range, where the walk runs to the end, max_lag is the cap. */
+enum { MCX_LAGCOV_CONSTANT = 2 }; /* mcx_col_lagcov.flags, beside MCX_SUMMARY_NONFINITE */
+enum { MCX_MESS_NOT_PD = 1, MCX_MESS_TRUNCATED = 2, MCX_MESS_LAMBDA_SINGULAR = 4, MCX_LAGCOV_TIMES = 5 };
+typedef struct mcx_lagcov_spec {
+  int max_lag;   /* >= 1; lags beyond T - 1 do not exist: pass nsteps - 1 for all */
+  int nlags_out; /* G(0) .. G(nlags_out - 1) are returned in gamma, 0 <= nlags_out <= nsteps: also beyond max_lag, which bounds
+                    the walk alone */
+  int with_ll;   /* log L among the chosen columns */
+} mcx_lagcov_spec;
+typedef struct mcx_lagcov_result {
+  long long N;
+  int p, s, k_used, lags_used, lags_computed, flags; /* flags: MCX_MESS_* */
+  double mess, logdet_lambda, logdet_sigma;
+} mcx_lagcov_result;
+typedef struct mcx_col_lagcov {
+  double mean, ess, mcse;
+  int flags, reserved;
+} mcx_col_lagcov;
+/* Steps [first_step, first_step + nsteps) of the store.  cols[ncol]; sigma[ncol][ncol], NaN outside the chosen columns;
+ * gamma[nlags_out][ncol][ncol] (may be NULL when nlags_out is 0).  MCX_ERR_INVALID, before a device is touched and with nothing
+ * allocated, for nsteps < 4, N < 2, a NULL spec or output, max_lag < 1 and nlags_out outside [0, nsteps], and in the cases
+ * mcx_samples_summary refuses.  The same store and arguments give the same bytes. */
+int mcx_samples_lagcov(mcx_engine *e, int first_step, int nsteps, const mcx_lagcov_spec *spec, mcx_lagcov_result *res,
+                       mcx_col_lagcov *cols, double *sigma, double *gamma);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows) */
+int mcx_rows_lagcov(const float *rows, int nsteps, int nc, int np, const mcx_lagcov_spec *spec, mcx_lagcov_result *res,
+                    mcx_col_lagcov *cols, double *sigma, double *gamma);
+/* and for the whole of a derived store */
+int mcx_store_lagcov(mcx_store *s, const mcx_lagcov_spec *spec, mcx_lagcov_result *res, mcx_col_lagcov *cols, double *sigma,
+                     double *gamma);
+/* host only: the walk and the numbers made of Sigma on given matrices gamma[nlags][ncol][ncol] = G(0) .. G(nlags - 1) of N rows
+ * (so K = floor((nlags - 2) / 2)); use[ncol]: the chosen columns (NULL: all).  cols[c].mean is NaN (the matrices do not hold it),
+ * a NaN G(0)_cc gives MCX_SUMMARY_NONFINITE; lags_computed = nlags.  MCX_ERR_INVALID for nlags < 2, N < 2, ncol outside
+ * [1, 257] and a NULL pointer other than use. */
+int mcx_mess_finish(int ncol, int nlags, long long N, const double *gamma, const unsigned char *use, mcx_lagcov_result *res,
+                    mcx_col_lagcov *cols, double *sigma);
+/* tests only, host only: the launch geometry of a lagcov call that computes lags 0 .. nlags - 1 of nsteps steps */
+typedef struct mcx_lagcov_geometry {
+  long long block;              /* threads per workgroup */
+  long long window_lags;        /* W: lags per sweep beyond lag 0 */
+  long long rows_per_iteration; /* rows of a unit: what a workgroup loads before it multiplies */
+  long long units;              /* ceil(N / rows_per_iteration) */
+  long long workgroups;         /* grid.x = min(units, max(32, 512 / tiles^2)): workgroup g takes units g, g + workgroups, ...; a
+                                   function of N and np */
+  long long tiles;              /* 16-column tiles of the parameters */
+  long long pairs_lag0;         /* tile pairs swept at lag 0: tiles (tiles + 1) / 2 */
+  long long pairs;              /* at every other lag: tiles^2 */
+  long long slab_rows;          /* partial sums per lag and workgroup */
+  long long windows;            /* sweeps of W lags: ceil((nlags - 1) / W) */
+  long long launches;           /* sweeps in all: 1 + windows */
+  long long lags_computed;      /* min(nsteps, 1 + windows W) */
+  long long scratch_bytes;
+} mcx_lagcov_geometry;
+int mcx_debug_lagcov_geometry(int nsteps, int nc, int np, int nlags, mcx_lagcov_geometry *g);
+/* mcx_samples_lagcov with HIP events around its stages, for tools/lagcov_bench.py (sigma, the columns and gamma are dropped).
+ * ms[MCX_LAGCOV_TIMES]: 0 the column-sum sweep, 1 the sweep of lag 0, 2 the window sweeps, 3 the reducers, 4 the whole call */
+int mcx_debug_lagcov_times(mcx_engine *e, int first_step, int nsteps, const mcx_lagcov_spec *spec, mcx_lagcov_result *res, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -152,6 +152,23 @@ class IntervalsGeometry(C.Structure):
                                             "store_scratch_bytes", "scratch_bytes_per_col")]
 
 
+class LagcovSpecC(C.Structure):
+    """include/mcx.h mcx_lagcov_spec"""
+    _fields_ = [("max_lag", C.c_int), ("nlags_out", C.c_int), ("with_ll", C.c_int)]
+
+
+class LagcovResultC(C.Structure):
+    """include/mcx.h mcx_lagcov_result"""
+    _fields_ = [("N", C.c_longlong)] + [(n, C.c_int) for n in ("p", "s", "k_used", "lags_used", "lags_computed", "flags")] + \
+               [(n, C.c_double) for n in ("mess", "logdet_lambda", "logdet_sigma")]
+
+
+class LagcovGeometry(C.Structure):
+    """include/mcx.h mcx_lagcov_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "window_lags", "rows_per_iteration", "units", "workgroups", "tiles",
+                                            "pairs_lag0", "pairs", "slab_rows", "windows", "launches", "lags_computed", "scratch_bytes")]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("naccept_burn", "naccept_main", "nsteps_burn", "nsteps_main",
                                           "remote_steps", "remote_passes", "exchanges", "kernel_launches",
@@ -337,6 +354,12 @@ def load():
         "mcx_intervals_quantile_ranks": [C.c_longlong, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
         "mcx_debug_intervals_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(IntervalsGeometry)],
         "mcx_debug_intervals_times": [vp, C.c_int, C.c_int, C.POINTER(IntervalSpecC), dp],
+        "mcx_samples_lagcov": [vp, C.c_int, C.c_int, C.POINTER(LagcovSpecC), C.POINTER(LagcovResultC), vp, dp, dp],
+        "mcx_rows_lagcov": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(LagcovSpecC), C.POINTER(LagcovResultC), vp, dp, dp],
+        "mcx_store_lagcov": [vp, C.POINTER(LagcovSpecC), C.POINTER(LagcovResultC), vp, dp, dp],
+        "mcx_mess_finish": [C.c_int, C.c_int, C.c_longlong, dp, C.POINTER(C.c_ubyte), C.POINTER(LagcovResultC), vp, dp],
+        "mcx_debug_lagcov_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LagcovGeometry)],
+        "mcx_debug_lagcov_times": [vp, C.c_int, C.c_int, C.POINTER(LagcovSpecC), C.POINTER(LagcovResultC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

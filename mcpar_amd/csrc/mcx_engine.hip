@@ -62,6 +62,8 @@ extern "C" int mcx_device_info(char *name, size_t namelen, int *cu_count, size_t
 // Cholesky factor, lower, row-major, strict upper triangle zeroed: the role of spotrf('U') on the
 // column-major view in MCPar::covar_setup (src/mcpar.cc:470-480).  Host side, np <= 32, once per run.  Returns 0, or
 // 1 + the index of the pivot that is not > 0 (mcx_proposal_from_cov asks the same function for its verdict).
+// mcx_lagcov_host.hpp has this function operation by operation in double (a log-determinant to nine digits, DESIGN.md section
+// 24): a change to the loops or to the pivot test here belongs there too.
 int cholesky_lower(int d, float *a)
 {
   for (int i = 0; i < d; ++i) {

@@ -18,6 +18,7 @@
 //             [--reweight-temper BETA | --reweight-source FILE.hip | --reweight-logw FILE] [--reweight FILE]
 //             [--resampled FILE] [--resampled-density FILE] [--resample-n K] [--resample-seed S]
 //             [--intervals FILE [--hdi P1,P2,...] [--interval-probs p1,p2,...]]
+//             [--mess FILE [--mess-max-lag L] [--mess-with-ll]] [--ccf FILE --ccf-lags L]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -90,6 +91,12 @@
 // column p0 .. LL under a header: name mean sd mcse_sd ess_sd, then hdi<P>_lo hdi<P>_hi for every mass P of --hdi (default 0.9; up
 // to 8), then q<p> mcse_q<p> ess_q<p> for every probability p of --interval-probs (default 0.05,0.5,0.95; up to 8), then flags.
 // Under the conditions of --summary.
+// --mess FILE: the multivariate effective sample size of the kept rows on the GPU (mcx_rows_lagcov): under a
+// header one line per column p0 .. LL, name mean ess mcse flags; then one line "name value" for each of N p s k_used lags_used
+// lags_computed flags mess logdet_lambda logdet_sigma; then "sigma" and the matrix, one row per line.  --mess-max-lag L: the walk
+// sees lags up to L (default: all); --mess-with-ll: log L among the columns.  --ccf FILE --ccf-lags L: the cross-correlations of
+// lags 0 .. L - 1, one line "lag name_i name_j ccf gamma" per (lag, i, j): column i leads column j by lag steps.  Under the
+// conditions of --summary.
 // --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
 // the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
 // one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
@@ -215,6 +222,58 @@ static int write_intervals(const char *path, const std::vector<double> &mass, co
     fprintf(f, " %d\n", s.flags);
   }
   return fclose(f) == 0 ? 0 : 1;
+}
+
+// --mess, --ccf: the lagged covariance of MCout's rows, the walk over it and the cross-correlations (either path may be NULL)
+static int write_lagcov(const char *mess_path, const char *ccf_path, int max_lag, bool with_ll, int ccf_lags, MCout &rows, int nsamp, int nc,
+                        int np)
+{
+  const size_t ncol = (size_t)np + 1, nn = ncol * ncol;
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 4) {
+    std::cerr << "--mess / --ccf: " << rows.size() << " rows stored, the lagged covariance needs nsamp * nc of them and nsamp >= 4\n";
+    return 1;
+  }
+  const mcx_lagcov_spec spec = {max_lag > 0 ? max_lag : nsamp - 1, ccf_path ? ccf_lags : 0, with_ll ? 1 : 0};
+  mcx_lagcov_result r;
+  std::vector<mcx_col_lagcov> cols(ncol);
+  std::vector<double> sigma(nn), gamma(nn * (size_t)(spec.nlags_out > 0 ? spec.nlags_out : 0) + 1);
+  if (mcx_rows_lagcov(rows.getpset(0), nsamp, nc, np, &spec, &r, cols.data(), sigma.data(), gamma.data()) != MCX_OK) {
+    std::cerr << "--mess / --ccf: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  if (mess_path) {
+    FILE *f = fopen(mess_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << mess_path << "\n";
+      return 1;
+    }
+    fprintf(f, "name mean ess mcse flags\n");
+    for (size_t c = 0; c < ncol; ++c)
+      fprintf(f, "%s %.17g %.17g %.17g %d\n", colname('p', (int)c, np).c_str(), cols[c].mean, cols[c].ess, cols[c].mcse, cols[c].flags);
+    fprintf(f, "N %lld\np %d\ns %d\nk_used %d\nlags_used %d\nlags_computed %d\nflags %d\n", r.N, r.p, r.s, r.k_used, r.lags_used,
+            r.lags_computed, r.flags);
+    fprintf(f, "mess %.17g\nlogdet_lambda %.17g\nlogdet_sigma %.17g\nsigma\n", r.mess, r.logdet_lambda, r.logdet_sigma);
+    for (size_t i = 0; i < ncol; ++i)
+      for (size_t j = 0; j < ncol; ++j) fprintf(f, "%.17g%c", sigma[i * ncol + j], j + 1 < ncol ? ' ' : '\n');
+    if (fclose(f) != 0) return 1;
+  }
+  if (ccf_path) {
+    FILE *f = fopen(ccf_path, "w");
+    if (!f) {
+      std::cerr << "cannot open " << ccf_path << "\n";
+      return 1;
+    }
+    fprintf(f, "lag i j ccf gamma\n");
+    for (int t = 0; t < spec.nlags_out; ++t)
+      for (size_t i = 0; i < ncol; ++i)
+        for (size_t j = 0; j < ncol; ++j) {
+          const double vi = gamma[i * ncol + i], vj = gamma[j * ncol + j], g = gamma[(size_t)t * nn + i * ncol + j];
+          const double c = !(vi > 0.0) || !(vj > 0.0) ? NAN : t == 0 && i == j ? 1.0 : g / (std::sqrt(vi) * std::sqrt(vj));
+          fprintf(f, "%d %s %s %.17g %.17g\n", t, colname('p', (int)i, np).c_str(), colname('p', (int)j, np).c_str(), c, g);
+        }
+    if (fclose(f) != 0) return 1;
+  }
+  return 0;
 }
 
 static int print_covariance(const char *path, const std::vector<double> &mean, const std::vector<double> &cov, int np, char prefix)
@@ -987,7 +1046,9 @@ int main(int argc, char *argv[])
   int clip_nc = 1024;
   std::string chain_table_file, kept_chains_file, kept_summary_file;
   mcx_chain_rule chain_rule = {5.0, 1, 0, 0};
-  std::string step_table_file, intervals_file;
+  std::string step_table_file, intervals_file, mess_file, ccf_file;
+  int mess_max_lag = 0, ccf_lags = 0;
+  bool mess_with_ll = false;
   std::vector<double> hdi_mass = {0.9}, interval_probs = {0.05, 0.5, 0.95};
   std::string compare_file, compare_to_file, compare_halves_file;
   int compare_nc = 0;
@@ -1133,6 +1194,11 @@ int main(int argc, char *argv[])
     else if (a == "--resample-n") resample_n = atoll(val());
     else if (a == "--resample-seed") resample_seed = (unsigned)strtoul(val(), 0, 10);
     else if (a == "--intervals") intervals_file = val();
+    else if (a == "--mess") mess_file = val();
+    else if (a == "--mess-max-lag") mess_max_lag = atoi(val());
+    else if (a == "--mess-with-ll") mess_with_ll = true;
+    else if (a == "--ccf") ccf_file = val();
+    else if (a == "--ccf-lags") ccf_lags = atoi(val());
     else if (a == "--hdi" || a == "--interval-probs") {
       std::vector<double> &list = a == "--hdi" ? hdi_mass : interval_probs;
       list.clear();
@@ -1235,6 +1301,18 @@ int main(int argc, char *argv[])
     if (rank == 0)
       std::cerr << "--intervals needs the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if ((!mess_file.empty() || !ccf_file.empty()) && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--mess and --ccf need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!ccf_file.empty() && ccf_lags < 1) {
+    if (rank == 0) std::cerr << "--ccf needs --ccf-lags L with L >= 1\n";
     MPI_Finalize();
     return 2;
   }
@@ -1458,6 +1536,12 @@ int main(int argc, char *argv[])
     return 2;
   }
   if (!intervals_file.empty() && write_intervals(intervals_file.c_str(), hdi_mass, interval_probs, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if ((!mess_file.empty() || !ccf_file.empty()) &&
+      write_lagcov(mess_file.empty() ? 0 : mess_file.c_str(), ccf_file.empty() ? 0 : ccf_file.c_str(), mess_max_lag, mess_with_ll, ccf_lags,
+                   rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

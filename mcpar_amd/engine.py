@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, Density2dSpecC,
-                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
+                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -97,6 +97,12 @@ QUANTILE_SE_DTYPE = np.dtype([("q", np.float64), ("ess_q", np.float64), ("u_lo",
                               ("ess_q_lag", np.int32), ("reserved", np.int32)], align=True)
 assert INTERVALS_DTYPE.itemsize == 40 and HDI_DTYPE.itemsize == 32 and QUANTILE_SE_DTYPE.itemsize == 72
 INTERVAL_MAX_MASSES, INTERVAL_MAX_PROBS, INTERVAL_TIMES = 8, 8, 12
+# include/mcx.h mcx_col_lagcov, its flags beside SUMMARY_NONFINITE, and mcx_lagcov_result.flags
+LAGCOV_DTYPE = np.dtype([("mean", np.float64), ("ess", np.float64), ("mcse", np.float64), ("flags", np.int32), ("reserved", np.int32)], align=True)
+assert LAGCOV_DTYPE.itemsize == 32
+LAGCOV_CONSTANT = 2
+MESS_NOT_PD, MESS_TRUNCATED, MESS_LAMBDA_SINGULAR = 1, 2, 4
+LAGCOV_TIMES = 5
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
@@ -646,6 +652,10 @@ class DerivedStore:
         """mcx_store_intervals: Engine.intervals' dict for the columns of this store"""
         return _intervals_call(lambda *a: load().mcx_store_intervals(self.h, *a), self.shape[2], hdi, probs)
 
+    def lagcov(self, max_lag=None, nlags=0, with_ll=False):
+        """mcx_store_lagcov: Engine.lagcov's dict for the columns of this store"""
+        return _lagcov_call(lambda *a: load().mcx_store_lagcov(self.h, *a), self.shape[0], self.shape[2], max_lag, nlags, with_ll)
+
     def compare(self, other, iid=False):
         """compare_stores(self, other)"""
         return compare_stores(self, other, iid)
@@ -1189,6 +1199,64 @@ def debug_intervals_geometry(nsteps, nc, np_, nmass=1, nprobs=3):
     g = IntervalsGeometry()
     check(load().mcx_debug_intervals_geometry(nsteps, nc, np_, nmass, nprobs, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in IntervalsGeometry._fields_}
+
+
+def _lagcov_dict(res, cols, sigma, gamma):
+    """the fields of mcx_lagcov_result; mean, ess, mcse, col_flags [ncol]; sigma and mcse_cov = sigma / N [ncol, ncol]; gamma
+    [nlags, ncol, ncol] and ccf = G(t)_ij / sqrt(G(0)_ii G(0)_jj): NaN where a variance is 0 or NaN, else exactly 1 on the diagonal
+    of lag 0"""
+    out = {name: getattr(res, name) for name, _ in LagcovResultC._fields_}
+    out.update(mean=cols["mean"].copy(), ess=cols["ess"].copy(), mcse=cols["mcse"].copy(), col_flags=cols["flags"].copy(),
+               sigma=sigma, mcse_cov=sigma / res.N, gamma=gamma)
+    ccf = gamma.copy()
+    if gamma.shape[0]:
+        v = np.diag(gamma[0]).copy()
+        v[~(v > 0)] = np.nan
+        sd = np.sqrt(v)
+        with np.errstate(invalid="ignore"):
+            ccf = gamma / np.outer(sd, sd)
+        k = np.flatnonzero(~np.isnan(v))
+        ccf[0, k, k] = 1.0
+    out["ccf"] = ccf
+    return out
+
+
+def _lagcov_call(fn, nsteps, ncol, max_lag, nlags, with_ll):
+    """fn(spec, res, cols, sigma, gamma) of one of the three lagcov entry points -> _lagcov_dict.  max_lag None: every lag of the
+    range"""
+    spec = LagcovSpecC(max(int(nsteps) - 1, 1) if max_lag is None else int(max_lag), int(nlags), 1 if with_ll else 0)
+    ncol = max(int(ncol), 1)
+    res, cols, sigma = LagcovResultC(), np.zeros(ncol, LAGCOV_DTYPE), np.zeros((ncol, ncol))
+    gamma = np.zeros((max(int(nlags), 0), ncol, ncol))
+    check(fn(C.byref(spec), C.byref(res), cols.ctypes.data_as(C.c_void_p), _dp(sigma), _dp(gamma) if gamma.size else None))
+    return _lagcov_dict(res, cols, sigma, gamma)
+
+
+def rows_lagcov(rows, nsteps, nc, max_lag=None, nlags=0, with_ll=False):
+    """mcx_rows_lagcov: Engine.lagcov's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    return _lagcov_call(lambda *a: load().mcx_rows_lagcov(_fp(rows), nsteps, nc, ncol - 1, *a), nsteps, ncol, max_lag, nlags, with_ll)
+
+
+def mess_finish(gamma, N, use=None):
+    """mcx_mess_finish (host only): the walk of DESIGN.md section 24 on given matrices gamma [nlags, ncol, ncol] of N rows, use
+    [ncol] the chosen columns (None: all) -> _lagcov_dict (mean is NaN; gamma and ccf are those given)"""
+    gamma = np.ascontiguousarray(gamma, np.float64)
+    nlags, ncol = gamma.shape[0], gamma.shape[1] if gamma.ndim == 3 else 0
+    res, cols, sigma = LagcovResultC(), np.zeros(max(ncol, 1), LAGCOV_DTYPE), np.zeros((max(ncol, 1),) * 2)
+    u = None if use is None else np.ascontiguousarray(np.asarray(use, bool), np.uint8)
+    check(load().mcx_mess_finish(ncol, nlags, int(N), _dp(gamma), None if u is None else u.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                 C.byref(res), cols.ctypes.data_as(C.c_void_p), _dp(sigma)))
+    return _lagcov_dict(res, cols, sigma, gamma)
+
+
+def debug_lagcov_geometry(nsteps, nc, np_, nlags=1):
+    """mcx_debug_lagcov_geometry (host only): the launch geometry of a lagcov call on nsteps steps of nc chains of np_ parameters
+    that computes lags 0 .. nlags - 1, as a dict of include/mcx.h's fields"""
+    g = LagcovGeometry()
+    check(load().mcx_debug_lagcov_geometry(nsteps, nc, np_, nlags, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in LagcovGeometry._fields_}
 
 
 def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
@@ -1806,6 +1874,23 @@ class Engine:
         ms = np.zeros(INTERVAL_TIMES)
         self._on_store(load().mcx_debug_intervals_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
         return ms
+
+    def lagcov(self, max_lag=None, nlags=0, with_ll=False, first_step=0, nsteps=None):
+        """mcx_samples_lagcov of kept steps [first_step, first_step + nsteps): the lagged covariance matrices G(0) .. G(nlags - 1) of
+        the columns (the parameters, then log L) and their cross-correlations, the multivariate initial sequence estimator sigma of
+        the chosen columns (the parameters, and log L with with_ll) walked over the lags up to max_lag, the multivariate effective
+        sample size mess and the ess and mcse per column made of sigma (_lagcov_dict lists the fields)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _lagcov_call(lambda *a: load().mcx_samples_lagcov(self.h, first_step, nsteps, *a), nsteps, self.np + 1, max_lag, nlags,
+                            with_ll)
+
+    def lagcov_times(self, max_lag=None, nlags=0, with_ll=False, first_step=0, nsteps=None):
+        """mcx_debug_lagcov_times: (the 5 stage times of one lagcov() call in ms -- include/mcx.h lists them --, lags_computed)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        spec = LagcovSpecC(max(nsteps - 1, 1) if max_lag is None else int(max_lag), int(nlags), 1 if with_ll else 0)
+        res, ms = LagcovResultC(), np.zeros(LAGCOV_TIMES)
+        check(load().mcx_debug_lagcov_times(self.h, first_step, nsteps, C.byref(spec), C.byref(res), _dp(ms)))
+        return ms, res.lags_computed
 
     def reweight_times(self, weights, probs=(0.05, 0.5, 0.95), nsteps_out=0, nc_out=0, seed=0, first_step=0, nsteps=None):
         """mcx_debug_reweight_times: ms[8] of one reweight() and, with nsteps_out * nc_out > 0, one resample() call -- the
