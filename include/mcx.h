@@ -1379,6 +1379,132 @@ int mcx_debug_lagcov_geometry(int nsteps, int nc, int np, int nlags, mcx_lagcov_
  * ms[MCX_LAGCOV_TIMES]: 0 the column-sum sweep, 1 the sweep of lag 0, 2 the window sweeps, 3 the reducers, 4 the whole call */
 int mcx_debug_lagcov_times(mcx_engine *e, int first_step, int nsteps, const mcx_lagcov_spec *spec, mcx_lagcov_result *res, double *ms);
 
+/* ---- modes of the sample store: k-means on the device, the mode table, chain hops ----------
+ * The N = T nc rows of a range are partitioned into K clusters by Lloyd's k-means on the p = np parameters; log L takes no
+ * part in a distance.
+ *   scale     s_j = 1 / sd_j of mcx_samples_summary's sd of the range (spec->scale != 0), else 1; a column whose sd is 0 or
+ *             not finite has s_j = 0 and takes no part
+ *   distance  u_ij = (double)x_ij s_j; d2(i, k): over j = 0 .. p - 1 in that order e = u_ij - c_kj, acc = acc + e e, every
+ *             subtraction, product and sum rounded on its own (no fused multiply-add); columns with s_j = 0 are skipped.
+ *             Centres are held scaled, in fp64
+ *   label     the lowest k that attains the least d2; a row with an inf or NaN parameter gets MCX_MODE_NONE, is counted in
+ *             n_nonfinite and enters no sum.  Given centres, the labels are a function of the definition alone
+ *   a pass    labels, n_changed (rows whose label differs from the pass before; before the first pass every label is
+ *             MCX_MODE_NONE), n_k and S_kj = sum of u_ij over the members of k in fp64; then c_k <- S_k / n_k on the host.  A
+ *             cluster with n_k = 0 keeps its centre and sets MCX_MODES_EMPTY
+ *   stopping  n_changed == 0: MCX_MODES_CONVERGED; after max_iter passes: MCX_MODES_NOT_CONVERGED.  The centres returned are
+ *             those the returned labels are the argmin of
+ *   seeding   spec->centres ([k][np], unscaled) when given; else mcx_modes_seed on M = min(N, seed_rows) rows: every row when
+ *             N <= seed_rows, else draws 0 .. M - 1 of (spec->seed, the range) as mcx_samples_draw makes them
+ *   table     one more sweep with the final centres and labels: per mode n, weight = n / (N - n_nonfinite), per column the
+ *             mean of its members (= the centre at convergence) and the within-mode sd sqrt(sum (u - mean)^2 / (n - 1)) / s_j,
+ *             inertia = sum d2, ll_mean in fp64 (NaN when a member's log L is not finite), ll_max in float order with the
+ *             first source row that holds it (NaN and -1 when a member's log L is NaN; an empty mode: NaN everywhere, -1)
+ * No float atomics: float sums go through one-writer accumulators, per-workgroup slabs and a fixed-order reducer, counts are
+ * integers.  The same source and arguments give the same bytes. */
+enum { MCX_MODES_MAX_K = 32, MCX_MODE_NONE = 255 };
+enum { MCX_MODES_CONVERGED = 1, MCX_MODES_NOT_CONVERGED = 2, MCX_MODES_EMPTY = 4, MCX_MODES_TIMES = 8 };
+typedef struct mcx_modes_spec {
+  int k;                 /* 1 .. MCX_MODES_MAX_K */
+  int max_iter;          /* >= 1 (the wrappers' default: 50) */
+  int scale;             /* non-zero: s_j = 1 / sd_j; 0: s_j = 1 */
+  int seed_rows;         /* >= 1 (the wrappers' default: 16 384) */
+  uint32_t seed;
+  const double *centres; /* NULL, or [k][np] unscaled, all finite: replaces the seeding */
+} mcx_modes_spec;
+typedef struct mcx_modes_result {
+  int k, iters, flags; /* flags: MCX_MODES_* */
+  int reserved;        /* 0 */
+  long long n, n_nonfinite, n_changed; /* rows of the range; rows labelled MCX_MODE_NONE; of the last pass */
+  double inertia;      /* the sum of the modes' */
+} mcx_modes_result;
+typedef struct mcx_mode_row {
+  long long n, ll_max_row;
+  double weight, inertia, ll_mean;
+  float ll_max;
+  int flags; /* MCX_MODES_EMPTY for a mode without rows */
+} mcx_mode_row;
+typedef struct mcx_mode_chain {
+  long long hops;           /* steps t >= 1 at which l_t and l_{t-1} are both valid and differ */
+  long long dominant_steps; /* visits of the dominant mode */
+  int dominant;             /* the mode the chain visits most, the lowest on ties; MCX_MODE_NONE when no label is valid */
+  int first_label, last_label; /* at steps 0 and T - 1 */
+  int reserved;             /* 0 */
+} mcx_mode_chain;
+/* The labels of a call: it owns a byte per row on the device and a stream, and remembers (T, nc, ncol, k) of its source but
+ * not the rows.  It depends neither on the engine nor on the store it came from.  One thread at a time per handle. */
+typedef struct mcx_modes mcx_modes;
+/* Steps [first_step, first_step + nsteps) of the engine's store (a queued asynchronous run is finished first), nsteps >= 1,
+ * N >= 2 when spec->scale is set.  table[k]; centres_scaled, centres, means, sds [k][np] (centres, means and sds unscaled; NaN
+ * in a column that takes no part, and for an empty mode's means and sds); scale[np].  out may be NULL (the labels are let go).
+ * MCX_ERR_INVALID, before a device is touched and with nothing allocated, for a NULL pointer other than out and
+ * spec->centres, k outside [1, MCX_MODES_MAX_K] or greater than N, max_iter < 1, seed_rows < 1, np outside [1, 256], N < 2 with
+ * spec->scale set and a centre that is not finite (the entry is named); after the seed sample is fetched, for k greater than its rows with finite parameters; and in the
+ * cases mcx_samples_summary refuses (the store does not hold the range).  MCX_ERR_ALLOC names the bytes. */
+int mcx_samples_modes(mcx_engine *e, int first_step, int nsteps, const mcx_modes_spec *spec, mcx_modes_result *res,
+                      mcx_mode_row *table, double *centres_scaled, double *centres, double *means, double *sds, double *scale,
+                      mcx_modes **out);
+/* the same for host rows in MCout layout (np + 1 columns, step-major then chain, nsteps * nc rows) */
+int mcx_rows_modes(const float *rows, int nsteps, int nc, int np, const mcx_modes_spec *spec, mcx_modes_result *res,
+                   mcx_mode_row *table, double *centres_scaled, double *centres, double *means, double *sds, double *scale,
+                   mcx_modes **out);
+/* and for the whole of a derived store */
+int mcx_store_modes(mcx_store *s, const mcx_modes_spec *spec, mcx_modes_result *res, mcx_mode_row *table, double *centres_scaled,
+                    double *centres, double *means, double *sds, double *scale, mcx_modes **out);
+int mcx_modes_destroy(mcx_modes *m); /* NULL is fine */
+/* any of the four may be NULL */
+int mcx_modes_shape(const mcx_modes *m, int *nsteps, int *nc, int *ncol, int *k);
+/* labels[nrows] of source rows [first_row, first_row + nrows), row = step * nc + chain */
+int mcx_modes_labels(mcx_modes *m, long long first_row, long long nrows, unsigned char *labels);
+/* Integers from the labels alone; any output may be NULL.  chains[nc]; visits[nc][k]: the steps chain c spends in mode k;
+ * trans[k][k]: the pairs (l_{t-1}, l_t) with both valid over all chains and steps t >= 1, a = b included; occupancy[T][k]: the
+ * chains in mode k at step t.  One lane walks a chain's T labels: many steps of few chains are slow, as in section 16. */
+int mcx_modes_chain_table(mcx_modes *m, mcx_mode_chain *chains, long long *visits, long long *trans, long long *occupancy);
+/* A store of T steps of nc chains with k columns, column j = 1.0f where the row's label is j and 0.0f elsewhere (a row
+ * labelled MCX_MODE_NONE is all zero), and log L = 0 (the handle does not hold the source's): mcx_store_summary of it gives
+ * every mode's weight as the mean, with its MCSE, R-hat and ESS. */
+int mcx_modes_indicator_store(mcx_modes *m, mcx_store **out);
+/* The rows of mode k of the source the handle was made from (or of any source of the same shape), in source order, as a
+ * row set (section 14).  MCX_ERR_INVALID for a source whose (nsteps, nc, np + 1) is not the handle's and k outside [0, m's k). */
+int mcx_samples_mode_rows(mcx_engine *e, int first_step, int nsteps, mcx_modes *m, int k, mcx_rowset **out);
+int mcx_rows_mode_rows(const float *rows, int nsteps, int nc, int np, mcx_modes *m, int k, mcx_rowset **out);
+int mcx_store_mode_rows(mcx_store *s, mcx_modes *m, int k, mcx_rowset **out);
+/* host only: k-means++ on rows[nrows][np + 1] (MCout layout) with the scale s[np] -> index[k], the seed rows.
+ *   centre 0  the row of the largest log L, first on ties (a NaN log L counts as -inf), among the rows with finite parameters
+ *   centre j  D_i = the least d2 of row i from centres 0 .. j - 1 (0 for a row that is not finite), cum_i their running sum
+ *             in index order in fp64; the first i with cum_i > u cum_{nrows-1}, u = the top 53 bits of words x : y of Philox
+ *             block (j, 0, 0, 0) under key (seed, 7) times 2^-53 (stream 7 is this unit's alone).  When every row sits on a
+ *             centre: the first finite row not yet taken
+ * MCX_ERR_INVALID for NULL pointers, np outside [1, 256], k outside [1, MCX_MODES_MAX_K] and fewer than k finite rows. */
+int mcx_modes_seed(const float *rows, long long nrows, int np, int k, uint32_t seed, const double *s, long long *index);
+/* tests only: one pass over host rows with given scaled centres[k][np] and scale s[np] (a column with s = 0 takes no part,
+ * whatever the centres hold there) -> labels[N], d2[N] of the winner (NaN for MCX_MODE_NONE), n[k], S[k][np]; any output may be
+ * NULL */
+int mcx_debug_modes_assign(const float *rows, int nsteps, int nc, int np, int k, const double *centres_scaled, const double *s,
+                           unsigned char *labels, double *d2, long long *n, double *S);
+/* tests only, host only: the launch geometry of a modes call */
+typedef struct mcx_modes_geometry {
+  long long block;           /* threads per workgroup */
+  long long rows_per_tile;   /* R = clip_rows of section 14: a workgroup stages R consecutive rows of all np columns */
+  long long tiles;           /* ceil(N / R) */
+  long long workgroups;      /* min(tiles, 1024): workgroup g takes tiles g, g + workgroups, ... */
+  long long lane_groups;     /* 256 / R: a row's centre blocks are dealt among this many lanes */
+  long long centre_blocks;   /* ceil(k / 8): eight running distances per lane at a time */
+  long long uniform_centres; /* 1 when R >= 64: a wavefront's centres are one scalar load */
+  long long sum_subgroups;   /* of the assign pass: the lane groups that share the tile's rows, min(256 / np, 2048 / (k np)), 1 at least */
+  long long table_columns;   /* of the table pass: np + 2 (the squares, d2, log L) */
+  long long table_subgroups; /* min(256 / min(np + 2, 256), 2048 / (k (np + 2))), 1 at least */
+  long long assign_lds_bytes, table_lds_bytes;
+  long long mark_workgroups, mark_mask_words; /* of mode_rows: section 14's geometry */
+  long long chains_workgroups, steps_workgroups;
+  long long scratch_bytes;   /* of the call's three scratch buffers */
+} mcx_modes_geometry;
+int mcx_debug_modes_geometry(int np, int nsteps, int nc, int k, mcx_modes_geometry *g);
+/* mcx_samples_modes with HIP events around its stages, for tools/modes_bench.py (the tables and labels are let go).
+ * ms[MCX_MODES_TIMES]: 0 the scale (summary passes), 1 the seed sample and seeding (wall clock), 2 the assign passes in all,
+ * 3 their reducers, 4 the table pass and its reducer (2 to 4: HIP events), 5 and 6 reserved (0), 7 the whole call (wall clock) */
+int mcx_debug_modes_times(mcx_engine *e, int first_step, int nsteps, const mcx_modes_spec *spec, mcx_modes_result *res, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -185,6 +185,26 @@ class PlanItem(C.Structure):
     _fields_ = [("kind", C.c_int), ("first", C.c_int), ("nsteps", C.c_int), ("aux", C.c_int)]
 
 
+class ModesSpecC(C.Structure):
+    """include/mcx.h mcx_modes_spec"""
+    _fields_ = [("k", C.c_int), ("max_iter", C.c_int), ("scale", C.c_int), ("seed_rows", C.c_int), ("seed", C.c_uint32),
+                ("centres", C.POINTER(C.c_double))]
+
+
+class ModesResultC(C.Structure):
+    """include/mcx.h mcx_modes_result"""
+    _fields_ = [("k", C.c_int), ("iters", C.c_int), ("flags", C.c_int), ("reserved", C.c_int), ("n", C.c_longlong),
+                ("n_nonfinite", C.c_longlong), ("n_changed", C.c_longlong), ("inertia", C.c_double)]
+
+
+class ModesGeometry(C.Structure):
+    """include/mcx.h mcx_modes_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "rows_per_tile", "tiles", "workgroups", "lane_groups", "centre_blocks",
+                                            "uniform_centres", "sum_subgroups", "table_columns", "table_subgroups",
+                                            "assign_lds_bytes", "table_lds_bytes", "mark_workgroups", "mark_mask_words",
+                                            "chains_workgroups", "steps_workgroups", "scratch_bytes")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 12), ("launches", C.c_uint64 * 12), ("chain_steps", C.c_uint64 * 12)]
 
@@ -360,6 +380,23 @@ def load():
         "mcx_mess_finish": [C.c_int, C.c_int, C.c_longlong, dp, C.POINTER(C.c_ubyte), C.POINTER(LagcovResultC), vp, dp],
         "mcx_debug_lagcov_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LagcovGeometry)],
         "mcx_debug_lagcov_times": [vp, C.c_int, C.c_int, C.POINTER(LagcovSpecC), C.POINTER(LagcovResultC), dp],
+        "mcx_samples_modes": [vp, C.c_int, C.c_int, C.POINTER(ModesSpecC), C.POINTER(ModesResultC), vp, dp, dp, dp, dp, dp, C.POINTER(vp)],
+        "mcx_rows_modes": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(ModesSpecC), C.POINTER(ModesResultC), vp, dp, dp, dp, dp, dp,
+                           C.POINTER(vp)],
+        "mcx_store_modes": [vp, C.POINTER(ModesSpecC), C.POINTER(ModesResultC), vp, dp, dp, dp, dp, dp, C.POINTER(vp)],
+        "mcx_modes_destroy": [vp],
+        "mcx_modes_shape": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+        "mcx_modes_labels": [vp, C.c_longlong, C.c_longlong, C.POINTER(C.c_ubyte)],
+        "mcx_modes_chain_table": [vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+        "mcx_modes_indicator_store": [vp, C.POINTER(vp)],
+        "mcx_samples_mode_rows": [vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp)],
+        "mcx_rows_mode_rows": [fp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp)],
+        "mcx_store_mode_rows": [vp, vp, C.c_int, C.POINTER(vp)],
+        "mcx_modes_seed": [fp, C.c_longlong, C.c_int, C.c_int, C.c_uint32, dp, C.POINTER(C.c_longlong)],
+        "mcx_debug_modes_assign": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_ubyte), dp,
+                                   C.POINTER(C.c_longlong), dp],
+        "mcx_debug_modes_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ModesGeometry)],
+        "mcx_debug_modes_times": [vp, C.c_int, C.c_int, C.POINTER(ModesSpecC), C.POINTER(ModesResultC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

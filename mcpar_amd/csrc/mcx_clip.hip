@@ -256,6 +256,7 @@ int clip_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_clip_spec *s
   unsigned long long *H = B.h->p;
   a.thr = B.d->p; a.counts = H; a.mask = H + o_mask; a.cnt = B.u->p; a.offs = H + o_offs;
   const size_t lds = geo.lds_bytes;
+  const RowMask rm{a.mask, a.cnt, H + o_offs};  // (offs | bsum | boff: rowset_scan's order)
   std::vector<unsigned long long> counts((size_t)ncol * 2);
   unsigned long long total = 0;
   auto run = [&]() -> int {
@@ -266,15 +267,7 @@ int clip_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_clip_spec *s
       HIPCHK(hipGetLastError());
       return MCX_OK;
     }));
-    MCXCHK(tm.run(2, [&]() -> int {
-      hipLaunchKernelGGL(k_clip_scan<0>, dim3((unsigned)nb), dim3(DERIVE_BLOCK), 0, st, a.cnt, nwg, nb, H + o_bsum, H + o_boff, H + o_offs);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(k_clip_scan<1>, dim3(1), dim3(DERIVE_BLOCK), 0, st, a.cnt, nwg, nb, H + o_bsum, H + o_boff, H + o_offs);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(k_clip_scan<2>, dim3((unsigned)nb), dim3(DERIVE_BLOCK), 0, st, a.cnt, nwg, nb, H + o_bsum, H + o_boff, H + o_offs);
-      HIPCHK(hipGetLastError());
-      return MCX_OK;
-    }));
+    MCXCHK(tm.run(2, [&]() -> int { return rowset_scan(st, rm, geo); }));
     HIPCHK(hipMemcpyAsync(counts.data(), H, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&total, H + o_boff + nb, sizeof total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -295,20 +288,9 @@ int clip_span(hipStream_t st, Bufs B, const StoreSpan &s, const mcx_clip_spec *s
   // ---- 5. the row set
   std::unique_ptr<mcx_rowset> o;
   if (out) {
-    o.reset(new mcx_rowset);
-    HIPCHK(hipGetDevice(&o->device));
-    o->np = np; o->K = (long long)total; o->N = (long long)N;
-    MCXCHK(o->st.ensure(hipStreamNonBlocking));
-    MCXCHK(o->x.alloc((size_t)total * np));
-    MCXCHK(o->ly.alloc((size_t)total));
-    MCXCHK(o->idx.alloc((size_t)total));
-    a.xo = o->x.p; a.lyo = o->ly.p; a.idx = o->idx.p;
+    MCXCHK(rowset_new(np, total, N, o));
     if (total > 0) {
-      rc = tm.run(3, [&]() -> int {
-        hipLaunchKernelGGL(k_clip_scatter, dim3((unsigned)nwg), dim3(DERIVE_BLOCK), lds, st, a);
-        HIPCHK(hipGetLastError());
-        return MCX_OK;
-      });
+      rc = tm.run(3, [&]() -> int { return rowset_scatter(st, s, rm, geo, *o); });
       const hipError_t es = hipStreamSynchronize(st);  // (before the new row set may go)
       MCXCHK(rc);
       HIPCHK(es);
@@ -348,6 +330,66 @@ ClipGeometry clip_geometry(int np, uint64_t N)
   g.nwg = sweep_tiles(N, g.R);
   g.nb = (g.nwg + CLIP_FAN - 1) / CLIP_FAN;
   return g;
+}
+
+int rowset_scan(hipStream_t st, const RowMask &m, const ClipGeometry &g)
+{
+  const uint64_t nwg = g.nwg, nb = g.nb;
+  unsigned long long *offs = m.scan, *bsum = offs + nwg, *boff = bsum + nb;
+  hipLaunchKernelGGL(k_clip_scan<0>, dim3((unsigned)nb), dim3(DERIVE_BLOCK), 0, st, m.cnt, nwg, nb, bsum, boff, offs);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_clip_scan<1>, dim3(1), dim3(DERIVE_BLOCK), 0, st, m.cnt, nwg, nb, bsum, boff, offs);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_clip_scan<2>, dim3((unsigned)nb), dim3(DERIVE_BLOCK), 0, st, m.cnt, nwg, nb, bsum, boff, offs);
+  HIPCHK(hipGetLastError());
+  return MCX_OK;
+}
+
+int rowset_new(int np, unsigned long long total, uint64_t N, std::unique_ptr<mcx_rowset> &o)
+{
+  o.reset(new mcx_rowset);
+  HIPCHK(hipGetDevice(&o->device));
+  o->np = np; o->K = (long long)total; o->N = (long long)N;
+  MCXCHK(o->st.ensure(hipStreamNonBlocking));
+  MCXCHK(o->x.alloc((size_t)total * np));
+  MCXCHK(o->ly.alloc((size_t)total));
+  MCXCHK(o->idx.alloc((size_t)total));
+  return MCX_OK;
+}
+
+int rowset_scatter(hipStream_t st, const StoreSpan &s, const RowMask &m, const ClipGeometry &g, mcx_rowset &o)
+{
+  ClipArgs a{};
+  a.x = s.x; a.ly = s.ly; a.N = (uint64_t)s.T * (uint64_t)s.nc; a.np = s.np; a.R = g.R; a.wpw = g.wpw;
+  a.mask = const_cast<unsigned long long *>(m.mask); a.cnt = const_cast<uint32_t *>(m.cnt); a.offs = m.scan;
+  a.xo = o.x.p; a.lyo = o.ly.p; a.idx = o.idx.p;
+  hipLaunchKernelGGL(k_clip_scatter, dim3((unsigned)g.nwg), dim3(DERIVE_BLOCK), g.lds_bytes, st, a);
+  HIPCHK(hipGetLastError());
+  return MCX_OK;
+}
+
+int rowset_from_mask(hipStream_t st, const StoreSpan &s, const RowMask &m, const ClipGeometry &g, mcx_rowset **out)
+{
+  unsigned long long total = 0;
+  auto scan = [&]() -> int {
+    MCXCHK(rowset_scan(st, m, g));
+    HIPCHK(hipMemcpyAsync(&total, m.scan + g.nwg + 2 * g.nb, sizeof total, hipMemcpyDeviceToHost, st));
+    return MCX_OK;
+  };
+  int rc = scan();
+  const hipError_t e0 = hipStreamSynchronize(st);  // (total is the copy's until here)
+  MCXCHK(rc);
+  HIPCHK(e0);
+  std::unique_ptr<mcx_rowset> o;
+  MCXCHK(rowset_new(s.np, total, (uint64_t)s.T * (uint64_t)s.nc, o));
+  if (total > 0) {
+    rc = rowset_scatter(st, s, m, g, *o);
+    const hipError_t es = hipStreamSynchronize(st);  // (before the new row set may go)
+    MCXCHK(rc);
+    HIPCHK(es);
+  }
+  *out = o.release();
+  return MCX_OK;
 }
 
 extern "C" int mcx_samples_clip(mcx_engine *e, int first_step, int nsteps, const mcx_clip_spec *spec, mcx_col_clip *cols,

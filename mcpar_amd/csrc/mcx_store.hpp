@@ -37,3 +37,21 @@ struct ClipGeometry {
   uint64_t nwg, nb;  // workgroups of the mark and scatter sweeps; scan blocks
 };
 MCXI ClipGeometry clip_geometry(int np, uint64_t N);
+
+// Section 14's scan and scatter for any unit that has a keep mask in the clip's geometry g = clip_geometry(s.np, N) (mcx_clip.hip
+// has them; section 25's rows of a mode come through here): mask[g.nwg][g.wpw], bit l of word w = row w * 64 + l of the
+// workgroup is kept; cnt[g.nwg] the kept rows of each; scan[rowset_scan_words(g)] u64 words of scratch, all on the device
+struct RowMask {
+  const unsigned long long *mask;
+  const uint32_t *cnt;
+  unsigned long long *scan;  // offs[nwg] | bsum[nb] | boff[nb + 1]: boff[nb] is the total
+};
+inline size_t rowset_scan_words(const ClipGeometry &g) { return (size_t)g.nwg + 2 * (size_t)g.nb + 1; }
+// the three scan launches: nothing is waited for
+MCXI int rowset_scan(hipStream_t st, const RowMask &m, const ClipGeometry &g);
+// a new row set of total rows of np parameters out of N, allocated with a stream of its own; then the one launch that scatters
+// the rows the mask keeps (total as rowset_scan left it in boff[nb], read by the caller) into it: nothing is waited for
+MCXI int rowset_new(int np, unsigned long long total, uint64_t N, std::unique_ptr<mcx_rowset> &o);
+MCXI int rowset_scatter(hipStream_t st, const StoreSpan &s, const RowMask &m, const ClipGeometry &g, mcx_rowset &o);
+// scan, the total, a new row set, scatter; waited for
+MCXI int rowset_from_mask(hipStream_t st, const StoreSpan &s, const RowMask &m, const ClipGeometry &g, mcx_rowset **out);

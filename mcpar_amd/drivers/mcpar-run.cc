@@ -19,6 +19,8 @@
 //             [--resampled FILE] [--resampled-density FILE] [--resample-n K] [--resample-seed S]
 //             [--intervals FILE [--hdi P1,P2,...] [--interval-probs p1,p2,...]]
 //             [--mess FILE [--mess-max-lag L] [--mess-with-ll]] [--ccf FILE --ccf-lags L]
+//             [--modes FILE --modes-k K [--modes-seed S] [--modes-iter M] [--modes-raw] [--modes-centres FILE]]
+//             [--mode-weights FILE] [--mode-chains FILE] [--mode-occupancy FILE] [--mode-rows K,FILE] [--mode-summary K,FILE]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
 // the engine's fused step kernels at run time; mcpar_amd/examples/ has three), --par its parameter block.
@@ -97,6 +99,17 @@
 // sees lags up to L (default: all); --mess-with-ll: log L among the columns.  --ccf FILE --ccf-lags L: the cross-correlations of
 // lags 0 .. L - 1, one line "lag name_i name_j ccf gamma" per (lag, i, j): column i leads column j by lag steps.  Under the
 // conditions of --summary.
+// --modes FILE --modes-k K: the kept rows partitioned into K modes by k-means on the GPU (mcx_rows_modes):
+// one line "name value" for each of k iters flags n n_nonfinite n_changed inertia; under a header one line per mode, mode n weight
+// inertia ll_mean ll_max ll_max_row flags; then "scale" and its line, then "centres", "means" and "sds" with one line per mode.
+// --modes-seed S (default 0) seeds the k-means++ start, --modes-iter M bounds the passes (default 50), --modes-raw leaves the
+// columns unscaled, --modes-centres FILE: K * np numbers, the centres to start from in place of the seeding.  --mode-weights FILE:
+// under a header one line per mode, mode weight sd mcse_mean rhat ess (the summary of the indicator store; nsamp >= 4).
+// --mode-chains FILE: under a header one line per chain, chain hops dominant dominant_steps first_label last_label and its visits
+// of every mode; then "trans" and the K x K matrix.  --mode-occupancy FILE: one line per step, the step and the chains in every
+// mode.  --mode-rows K,FILE: the rows of mode K as the text of the sample output.  --mode-summary K,FILE: the file of --summary for
+// the rows of mode K as one sequence.  Each of them needs --modes-k (--modes FILE itself is not needed).  Under the conditions of
+// --summary.
 // --read FILE: no run; FILE -- sample text as --out, mcx_samples_text or the reference's drivers write it -- is parsed on
 // the GPU (mcx_file_store, the reference's read.mc.data) and its rows fill the MCout the analysis files are made from: every
 // one of them works on a file as on a run.  --nc NC: the chains of the run that wrote it (rows are step-major, then chain);
@@ -107,6 +120,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <sstream>
 #include <string>
@@ -488,6 +502,183 @@ static int write_clip(const mcx_clip_spec &spec, const char *report_path, const 
     }
   }
   mcx_rowset_destroy(rs);
+  return rc;
+}
+
+// --modes and its companions: one modes call on MCout's rows (mcx_rows_modes), the files made of its tables and labels
+struct ModesFiles {
+  std::string modes, weights, chains, occupancy, rows, summary, centres;  // (centres: read, not written)
+  int rows_k = -1, summary_k = -1;
+  bool any() const { return !modes.empty() || !weights.empty() || !chains.empty() || !occupancy.empty() || !rows.empty() || !summary.empty(); }
+};
+
+static int write_rowset_text(const char *what, const char *path, mcx_rowset *rs, long long K, size_t ncol)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  int rc = 0;
+  const long long chunk = 65536;
+  std::vector<float> part;
+  std::vector<char> text;
+  for (long long done = 0; rc == 0 && done < K; done += chunk) {
+    const long long k = K - done < chunk ? K - done : chunk;
+    size_t nb = 0;
+    part.resize((size_t)k * ncol);
+    if (mcx_rowset_copy(rs, done, k, part.data()) != MCX_OK || mcx_format_rows(part.data(), (size_t)k, (int)ncol, 0, 0, &nb) != MCX_OK) {
+      std::cerr << what << ": " << mcx_last_error() << "\n";
+      rc = 1;
+      break;
+    }
+    text.resize(nb);
+    if (mcx_format_rows(part.data(), (size_t)k, (int)ncol, text.data(), nb, &nb) != MCX_OK) {
+      std::cerr << what << ": " << mcx_last_error() << "\n";
+      rc = 1;
+    } else if (fwrite(text.data(), 1, nb, f) != nb) rc = 1;
+  }
+  if (fclose(f) != 0) rc = 1;
+  return rc;
+}
+
+static int write_modes(const ModesFiles &mf, mcx_modes_spec spec, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--modes: " << rows.size() << " rows stored, the modes need nsamp * nc of them\n";
+    return 1;
+  }
+  const int K = spec.k;
+  std::vector<double> given;
+  if (!mf.centres.empty()) {
+    std::ifstream in(mf.centres.c_str());
+    double v;
+    while (in >> v) given.push_back(v);
+    if (K < 1 || given.size() != (size_t)K * np) {
+      std::cerr << "--modes-centres " << mf.centres << ": " << given.size() << " numbers, --modes-k * np = " << (long long)K * np << " are needed\n";
+      return 1;
+    }
+    spec.centres = given.data();
+  }
+  const size_t kk = (size_t)(K > 0 ? K : 1), knp = kk * np;
+  mcx_modes_result res;
+  std::vector<mcx_mode_row> table(kk);
+  std::vector<double> cs(knp), c(knp), means(knp), sds(knp), scale((size_t)np);
+  mcx_modes *m = 0;
+  if (mcx_rows_modes(rows.getpset(0), nsamp, nc, np, &spec, &res, table.data(), cs.data(), c.data(), means.data(), sds.data(), scale.data(),
+                     &m) != MCX_OK) {
+    std::cerr << "--modes: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  int rc = 0;
+  auto open_w = [&](const std::string &path) -> FILE * {
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) {
+      std::cerr << "cannot open " << path << "\n";
+      rc = 1;
+    }
+    return f;
+  };
+  auto matrix = [&](FILE *f, const char *name, const std::vector<double> &v) {
+    fprintf(f, "%s\n", name);
+    for (int k = 0; k < K; ++k) {
+      for (int j = 0; j < np; ++j) fprintf(f, "%s%.17g", j ? " " : "", v[(size_t)k * np + j]);
+      fprintf(f, "\n");
+    }
+  };
+  if (!mf.modes.empty()) {
+    if (FILE *f = open_w(mf.modes)) {
+      fprintf(f, "k %d\niters %d\nflags %d\nn %lld\nn_nonfinite %lld\nn_changed %lld\ninertia %.17g\n", res.k, res.iters, res.flags, res.n,
+              res.n_nonfinite, res.n_changed, res.inertia);
+      fprintf(f, "mode n weight inertia ll_mean ll_max ll_max_row flags\n");
+      for (int k = 0; k < K; ++k)
+        fprintf(f, "%d %lld %.17g %.17g %.17g %.9g %lld %d\n", k, table[k].n, table[k].weight, table[k].inertia, table[k].ll_mean,
+                (double)table[k].ll_max, table[k].ll_max_row, table[k].flags);
+      fprintf(f, "scale\n");
+      for (int j = 0; j < np; ++j) fprintf(f, "%s%.17g", j ? " " : "", scale[j]);
+      fprintf(f, "\n");
+      matrix(f, "centres", c);
+      matrix(f, "means", means);
+      matrix(f, "sds", sds);
+      if (fclose(f) != 0) rc = 1;
+    }
+  }
+  if (rc == 0 && !mf.weights.empty()) {
+    mcx_store *st = 0;
+    std::vector<mcx_col_summary> sc(kk + 1);
+    if (mcx_modes_indicator_store(m, &st) != MCX_OK || mcx_store_summary(st, 0, 0, sc.data(), 0) != MCX_OK) {
+      std::cerr << "--mode-weights: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else if (FILE *f = open_w(mf.weights)) {
+      fprintf(f, "mode weight sd mcse_mean rhat ess\n");
+      for (int k = 0; k < K; ++k)
+        fprintf(f, "%d %.17g %.17g %.17g %.17g %.17g\n", k, sc[k].mean, sc[k].sd, sc[k].mcse_mean, sc[k].rhat, sc[k].ess);
+      if (fclose(f) != 0) rc = 1;
+    }
+    mcx_store_destroy(st);
+  }
+  if (rc == 0 && (!mf.chains.empty() || !mf.occupancy.empty())) {
+    std::vector<mcx_mode_chain> ch((size_t)nc);
+    std::vector<long long> visits((size_t)nc * kk), trans(kk * kk), occ((size_t)nsamp * kk);
+    if (mcx_modes_chain_table(m, ch.data(), visits.data(), trans.data(), occ.data()) != MCX_OK) {
+      std::cerr << "--mode-chains: " << mcx_last_error() << "\n";
+      rc = 1;
+    }
+    if (rc == 0 && !mf.chains.empty())
+      if (FILE *f = open_w(mf.chains)) {
+        fprintf(f, "chain hops dominant dominant_steps first_label last_label visits\n");
+        for (int i = 0; i < nc; ++i) {
+          fprintf(f, "%d %lld %d %lld %d %d", i, ch[i].hops, ch[i].dominant, ch[i].dominant_steps, ch[i].first_label, ch[i].last_label);
+          for (int k = 0; k < K; ++k) fprintf(f, " %lld", visits[(size_t)i * K + k]);
+          fprintf(f, "\n");
+        }
+        fprintf(f, "trans\n");
+        for (int a = 0; a < K; ++a) {
+          for (int b = 0; b < K; ++b) fprintf(f, "%s%lld", b ? " " : "", trans[(size_t)a * K + b]);
+          fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) rc = 1;
+      }
+    if (rc == 0 && !mf.occupancy.empty())
+      if (FILE *f = open_w(mf.occupancy)) {
+        for (int t = 0; t < nsamp; ++t) {
+          fprintf(f, "%d", t);
+          for (int k = 0; k < K; ++k) fprintf(f, " %lld", occ[(size_t)t * K + k]);
+          fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) rc = 1;
+      }
+  }
+  if (rc == 0 && !mf.rows.empty()) {
+    mcx_rowset *rs = 0;
+    long long n = 0;
+    if (mcx_rows_mode_rows(rows.getpset(0), nsamp, nc, np, m, mf.rows_k, &rs) != MCX_OK || mcx_rowset_shape(rs, &n, 0, 0) != MCX_OK) {
+      std::cerr << "--mode-rows: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = write_rowset_text("--mode-rows", mf.rows.c_str(), rs, n, (size_t)np + 1);
+    mcx_rowset_destroy(rs);
+  }
+  if (rc == 0 && !mf.summary.empty()) {
+    // the rows of the mode as one pseudo-chain: the file of --summary for them (its R-hat and ESS are of that one sequence)
+    mcx_rowset *rs = 0;
+    mcx_store *st = 0;
+    long long n = 0;
+    std::vector<mcx_col_summary> sc((size_t)np + 1);
+    std::vector<double> q(((size_t)np + 1) * 3);
+    if (mcx_rows_mode_rows(rows.getpset(0), nsamp, nc, np, m, mf.summary_k, &rs) != MCX_OK || mcx_rowset_shape(rs, &n, 0, 0) != MCX_OK) {
+      std::cerr << "--mode-summary: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else if (n < 4 || n > 2000000000LL) {
+      std::cerr << "--mode-summary: mode " << mf.summary_k << " has " << n << " rows, a summary needs at least 4\n";
+      rc = 1;
+    } else if (mcx_rowset_store(rs, 0, (int)n, 1, &st) != MCX_OK || mcx_store_summary(st, SUMMARY_PROBS, 3, sc.data(), q.data()) != MCX_OK) {
+      std::cerr << "--mode-summary: " << mcx_last_error() << "\n";
+      rc = 1;
+    } else rc = print_summary(mf.summary.c_str(), sc, q, np, 'p');
+    mcx_store_destroy(st);
+    mcx_rowset_destroy(rs);
+  }
+  mcx_modes_destroy(m);
   return rc;
 }
 
@@ -1048,6 +1239,8 @@ int main(int argc, char *argv[])
   mcx_chain_rule chain_rule = {5.0, 1, 0, 0};
   std::string step_table_file, intervals_file, mess_file, ccf_file;
   int mess_max_lag = 0, ccf_lags = 0;
+  ModesFiles modes_files;
+  mcx_modes_spec modes_spec = {0, 50, 1, 16384, 0u, 0};
   bool mess_with_ll = false;
   std::vector<double> hdi_mass = {0.9}, interval_probs = {0.05, 0.5, 0.95};
   std::string compare_file, compare_to_file, compare_halves_file;
@@ -1194,6 +1387,24 @@ int main(int argc, char *argv[])
     else if (a == "--resample-n") resample_n = atoll(val());
     else if (a == "--resample-seed") resample_seed = (unsigned)strtoul(val(), 0, 10);
     else if (a == "--intervals") intervals_file = val();
+    else if (a == "--modes") modes_files.modes = val();
+    else if (a == "--modes-k") modes_spec.k = atoi(val());
+    else if (a == "--modes-seed") modes_spec.seed = (uint32_t)strtoul(val(), 0, 10);
+    else if (a == "--modes-iter") modes_spec.max_iter = atoi(val());
+    else if (a == "--modes-raw") modes_spec.scale = 0;
+    else if (a == "--modes-centres") modes_files.centres = val();
+    else if (a == "--mode-weights") modes_files.weights = val();
+    else if (a == "--mode-chains") modes_files.chains = val();
+    else if (a == "--mode-occupancy") modes_files.occupancy = val();
+    else if (a == "--mode-rows" || a == "--mode-summary") {
+      const char *v = val(), *comma = strchr(v, ',');
+      if (!comma || comma == v || !comma[1]) {
+        std::cerr << a << " takes K,FILE\n";
+        return 2;
+      }
+      (a == "--mode-rows" ? modes_files.rows_k : modes_files.summary_k) = atoi(v);
+      (a == "--mode-rows" ? modes_files.rows : modes_files.summary) = comma + 1;
+    }
     else if (a == "--mess") mess_file = val();
     else if (a == "--mess-max-lag") mess_max_lag = atoi(val());
     else if (a == "--mess-with-ll") mess_with_ll = true;
@@ -1308,6 +1519,18 @@ int main(int argc, char *argv[])
     if (rank == 0)
       std::cerr << "--mess and --ccf need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (modes_files.any() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--modes and the --mode-* files need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (modes_files.any() && modes_spec.k < 1) {
+    if (rank == 0) std::cerr << "--modes and the --mode-* files need --modes-k K with K >= 1\n";
     MPI_Finalize();
     return 2;
   }
@@ -1542,6 +1765,10 @@ int main(int argc, char *argv[])
   if ((!mess_file.empty() || !ccf_file.empty()) &&
       write_lagcov(mess_file.empty() ? 0 : mess_file.c_str(), ccf_file.empty() ? 0 : ccf_file.c_str(), mess_max_lag, mess_with_ll, ccf_lags,
                    rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (modes_files.any() && write_modes(modes_files, modes_spec, rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, Density2dSpecC,
-                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
+                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, ModesGeometry, ModesResultC, ModesSpecC, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -656,6 +656,12 @@ class DerivedStore:
         """mcx_store_lagcov: Engine.lagcov's dict for the columns of this store"""
         return _lagcov_call(lambda *a: load().mcx_store_lagcov(self.h, *a), self.shape[0], self.shape[2], max_lag, nlags, with_ll)
 
+    def modes(self, k, **spec):
+        """mcx_store_modes: Engine.modes' Modes for the rows of this store (which must outlive the Modes' rows() calls)"""
+        t, nc, ncol = self.shape
+        return _modes_call(lambda *a: load().mcx_store_modes(self.h, *a), _modes_spec(k, ncol - 1, **spec), ncol - 1, (t, nc, ncol),
+                           lambda *a: load().mcx_store_mode_rows(self.h, *a))
+
     def compare(self, other, iid=False):
         """compare_stores(self, other)"""
         return compare_stores(self, other, iid)
@@ -1257,6 +1263,156 @@ def debug_lagcov_geometry(nsteps, nc, np_, nlags=1):
     g = LagcovGeometry()
     check(load().mcx_debug_lagcov_geometry(nsteps, nc, np_, nlags, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in LagcovGeometry._fields_}
+
+
+# ---- modes of a store (include/mcx.h) ----
+MODES_MAX_K, MODE_NONE, MODES_TIMES = 32, 255, 8  # include/mcx.h MCX_MODES_MAX_K, MCX_MODE_NONE, MCX_MODES_TIMES
+MODES_CONVERGED, MODES_NOT_CONVERGED, MODES_EMPTY = 1, 2, 4
+MODE_ROW_DTYPE = np.dtype([("n", np.int64), ("ll_max_row", np.int64), ("weight", np.float64), ("inertia", np.float64),
+                           ("ll_mean", np.float64), ("ll_max", np.float32), ("flags", np.int32)], align=True)
+MODE_CHAIN_DTYPE = np.dtype([("hops", np.int64), ("dominant_steps", np.int64), ("dominant", np.int32), ("first_label", np.int32),
+                             ("last_label", np.int32), ("reserved", np.int32)], align=True)
+assert MODE_ROW_DTYPE.itemsize == 48 and MODE_CHAIN_DTYPE.itemsize == 32
+
+
+def _modes_spec(k, np_, max_iter=50, scale=True, seed_rows=16384, seed=0, centres=None):
+    """(mcx_modes_spec, the array it points to)"""
+    c = None
+    if centres is not None:
+        c = np.ascontiguousarray(np.asarray(centres, np.float64).reshape(-1))
+        if c.size != int(k) * np_:
+            raise ValueError("centres takes [k, np] = [%d, %d] values" % (k, np_))
+    return ModesSpecC(int(k), int(max_iter), 1 if scale else 0, int(seed_rows), int(seed) & 0xffffffff, None if c is None else _dp(c)), c
+
+
+class Modes:
+    """an mcx_modes with the tables of its call: the labels of every row of the source stay on the device, owned by this object.
+    result: dict of mcx_modes_result's fields; table: dict of arrays [k] (n, weight, inertia, ll_mean, ll_max, ll_max_row, flags)
+    and [k, np] (mean, sd, unscaled); centres, centres_scaled [k, np]; scale [np].  source: how to reach the rows again
+    (rows() needs them: the handle does not own them)."""
+
+    def __init__(self, handle, result, table, centres, centres_scaled, scale, shape, source):
+        self.h, self.result, self.table, self.centres, self.centres_scaled, self.scale = handle, result, table, centres, centres_scaled, scale
+        self.nsteps, self.nc, self.ncol = shape
+        self.k = result["k"]
+        self._source = source
+
+    def close(self):
+        if self.h:
+            load().mcx_modes_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def labels(self, first=0, n=None):
+        """uint8 labels of source rows [first, first + n), row = step * nc + chain; MODE_NONE for a row that is not finite"""
+        n = max(self.nsteps * self.nc - first, 0) if n is None else n
+        out = np.empty(max(n, 0), np.uint8)
+        check(load().mcx_modes_labels(self.h, first, n, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
+
+    def chain_table(self):
+        """mcx_modes_chain_table: dict of hops, dominant, dominant_steps, first_label, last_label [nc]; visits [nc, k]; trans [k, k];
+        occupancy [nsteps, k], all integers"""
+        chains = np.zeros(self.nc, MODE_CHAIN_DTYPE)
+        visits, trans, occ = (np.zeros(s, np.int64) for s in ((self.nc, self.k), (self.k, self.k), (self.nsteps, self.k)))
+        llp = lambda a: a.ctypes.data_as(C.POINTER(C.c_longlong))  # noqa: E731
+        check(load().mcx_modes_chain_table(self.h, chains.ctypes.data_as(C.c_void_p), llp(visits), llp(trans), llp(occ)))
+        out = {name: chains[name].copy() for name in MODE_CHAIN_DTYPE.names if name != "reserved"}
+        out.update(visits=visits, trans=trans, occupancy=occ)
+        return out
+
+    def rows(self, k):
+        """the rows of mode k in source order as a RowSet (its report is empty: nothing was clipped)"""
+        h = C.c_void_p()
+        check(self._source(self.h, int(k), C.byref(h)))
+        nrows = C.c_longlong(0)
+        check(load().mcx_rowset_shape(h, C.byref(nrows), None, None))
+        rs = RowSet(h, np.zeros(self.ncol, CLIP_DTYPE), nrows.value, self.nsteps * self.nc)
+        return rs
+
+    def indicators(self):
+        """mcx_modes_indicator_store: the DerivedStore of k columns of 1.0 / 0.0, log L = 0"""
+        h = C.c_void_p()
+        check(load().mcx_modes_indicator_store(self.h, C.byref(h)))
+        return DerivedStore(h)
+
+    def weights(self):
+        """section 9's summary of the indicators, per mode: dict of mean (= the weight when every row is finite), sd, mcse_mean,
+        rhat, ess [k]"""
+        st = self.indicators()
+        try:
+            s = st.summary(probs=())
+        finally:
+            st.close()
+        return {name: np.asarray(s[name])[:self.k].copy() for name in ("mean", "sd", "mcse_mean", "rhat", "ess")}
+
+
+def _modes_call(fn, spec_and_centres, np_, shape, source):
+    """fn(spec, res, table, cs, c, means, sds, scale, out) of one of the three modes entry points -> Modes"""
+    spec, _keep = spec_and_centres
+    k = min(max(int(spec.k), 1), MODES_MAX_K)  # (what the tables are sized for; a k outside is refused by the call)
+    res, table, h = ModesResultC(), np.zeros(k, MODE_ROW_DTYPE), C.c_void_p()
+    cs, c, means, sds = (np.zeros((k, np_)) for _ in range(4))
+    scale = np.zeros(np_)
+    check(fn(C.byref(spec), C.byref(res), table.ctypes.data_as(C.c_void_p), _dp(cs), _dp(c), _dp(means), _dp(sds), _dp(scale), C.byref(h)))
+    result = {name: getattr(res, name) for name in ("k", "iters", "flags", "n", "n_nonfinite", "n_changed", "inertia")}
+    tab = {name: table[name].copy() for name in MODE_ROW_DTYPE.names}
+    tab.update(mean=means, sd=sds)
+    return Modes(h, result, tab, c, cs, scale, shape, source)
+
+
+def rows_modes(rows, nsteps, nc, k, **spec):
+    """mcx_rows_modes: Engine.modes' Modes for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    np_ = rows.shape[1] - 1
+    return _modes_call(lambda *a: load().mcx_rows_modes(_fp(rows), nsteps, nc, np_, *a), _modes_spec(k, np_, **spec), np_,
+                       (nsteps, nc, np_ + 1), lambda *a: load().mcx_rows_mode_rows(_fp(rows), nsteps, nc, np_, *a))
+
+
+def seed_modes(rows, k, seed=0, scale=None):
+    """mcx_modes_seed (host only): the int64 indices of the k k-means++ seed rows of rows [M, np + 1]; scale: s [np], None = ones"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    np_ = rows.shape[1] - 1
+    s = np.ones(np_) if scale is None else np.ascontiguousarray(np.asarray(scale, np.float64).reshape(-1))
+    if s.size != np_:
+        raise ValueError("scale takes one entry per parameter (%d)" % np_)
+    idx = np.zeros(max(int(k), 1), np.int64)
+    check(load().mcx_modes_seed(_fp(rows), rows.shape[0], np_, int(k), int(seed) & 0xffffffff, _dp(s),
+                                idx.ctypes.data_as(C.POINTER(C.c_longlong))))
+    return idx
+
+
+def debug_modes_assign(rows, nsteps, nc, centres_scaled, scale):
+    """mcx_debug_modes_assign: one pass -> (labels [N] uint8, d2 [N], n [k] int64, S [k, np])"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    np_ = rows.shape[1] - 1
+    c = np.ascontiguousarray(np.asarray(centres_scaled, np.float64).reshape(-1, np_))
+    s = np.ascontiguousarray(np.asarray(scale, np.float64).reshape(-1))
+    if s.size != np_:
+        raise ValueError("scale takes one entry per parameter (%d)" % np_)
+    k, N = c.shape[0], nsteps * nc
+    labels, d2, n, S = np.zeros(N, np.uint8), np.zeros(N), np.zeros(max(k, 1), np.int64), np.zeros((max(k, 1), np_))
+    check(load().mcx_debug_modes_assign(_fp(rows), nsteps, nc, np_, k, _dp(c), _dp(s), labels.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                        _dp(d2), n.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(S)))
+    return labels, d2, n[:k], S[:k]
+
+
+def debug_modes_geometry(np_, nsteps, nc, k):
+    """mcx_debug_modes_geometry (host only): the launch geometry of a modes call as a dict of include/mcx.h's fields"""
+    g = ModesGeometry()
+    check(load().mcx_debug_modes_geometry(np_, nsteps, nc, k, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in ModesGeometry._fields_}
 
 
 def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
@@ -1883,6 +2039,24 @@ class Engine:
         nsteps = self._nsteps(first_step, nsteps)
         return _lagcov_call(lambda *a: load().mcx_samples_lagcov(self.h, first_step, nsteps, *a), nsteps, self.np + 1, max_lag, nlags,
                             with_ll)
+
+    def modes(self, k, first_step=0, nsteps=None, **spec):
+        """mcx_samples_modes of kept steps [first_step, first_step + nsteps): the rows partitioned into k modes by k-means on the
+        device -> Modes (the mode table, the centres, the labels on the device, and from them the chains' hops, the rows of one
+        mode and the indicator store).  spec: max_iter=50, scale=True (1 / sd per column), seed_rows=16384, seed=0, centres=None
+        or [k, np] unscaled starting centres in place of the k-means++ seeding"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _modes_call(lambda *a: load().mcx_samples_modes(self.h, first_step, nsteps, *a), _modes_spec(k, self.np, **spec), self.np,
+                           (nsteps, self.nc, self.np + 1),
+                           lambda *a: load().mcx_samples_mode_rows(self.h, first_step, nsteps, *a))
+
+    def modes_times(self, k, first_step=0, nsteps=None, **spec):
+        """mcx_debug_modes_times: (ms[MODES_TIMES] of one modes() call -- include/mcx.h lists them --, the result dict)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        sp, _keep = _modes_spec(k, self.np, **spec)
+        res, ms = ModesResultC(), np.zeros(MODES_TIMES)
+        check(load().mcx_debug_modes_times(self.h, first_step, nsteps, C.byref(sp), C.byref(res), _dp(ms)))
+        return ms, {name: getattr(res, name) for name in ("k", "iters", "flags", "n", "n_nonfinite", "n_changed", "inertia")}
 
     def lagcov_times(self, max_lag=None, nlags=0, with_ll=False, first_step=0, nsteps=None):
         """mcx_debug_lagcov_times: (the 5 stage times of one lagcov() call in ms -- include/mcx.h lists them --, lags_computed)"""

@@ -121,6 +121,24 @@ __global__ void k_pk2(unsigned *out, unsigned seed)
   unsigned fin = __float_as_uint(a0.x + a1.x + a2.x + a3.x + a4.y + a5.y + a6.y + a7.y + b0.x + b7.y);
   out[blockIdx.x * blockDim.x + threadIdx.x] = fin;
 }
+// fp64 on the vector unit, one rounding an instruction (what the distance of the modes of a store issues):
+//   add_f64, mul_f64 alone, and dist_f64: v_add_f64 e = u - c ; v_mul_f64 e = e e ; v_add_f64 d = d + e, counted per instruction
+#define DD(k) double a##k = seed * 1e-9 + k + threadIdx.x, b##k = a##k + 0.5;
+#define FIND unsigned fin = __float_as_uint((float)(a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + b0 + b1 + b2 + b3 + b4 + b5 + b6 + b7))
+#define OP_ADD64(k) asm volatile("v_add_f64 %0, %0, %1" : "+v"(a##k) : "v"(sd));
+#define OP_MUL64(k) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(a##k) : "v"(sd));
+#define OP_DIST64(k) asm volatile("v_add_f64 %1, %2, -%3\n\tv_mul_f64 %1, %1, %1\n\tv_add_f64 %0, %0, %1" : "+v"(a##k), "+v"(b##k) : "v"(sd), "s"(sc));
+KERNEL(k_add_f64, double sd = seed * 1e-9; R8(DD), R8(OP_ADD64), FIND)
+KERNEL(k_mul_f64, double sd = 1.0 + seed * 1e-12; R8(DD), R8(OP_MUL64), FIND)
+__global__ void k_dist_f64(unsigned *out, unsigned seed)
+{
+  const double sd = seed * 1e-9 + threadIdx.x;
+  const double sc = __longlong_as_double(((long long)__builtin_amdgcn_readfirstlane(0x3ff00000) << 32) | __builtin_amdgcn_readfirstlane(seed));
+  R8(DD)
+  for (int i = 0; i < ITER / 3; ++i) { R8(OP_DIST64) }
+  for (int i = 0; i < ITER % 3; ++i) { R8(OP_ADD64) }  // (ITER instructions a chain, as main counts them)
+  FIND; out[blockIdx.x * blockDim.x + threadIdx.x] = fin;
+}
 KERNEL(k_fma, R8(DF), R8(OP_FMA), FINF)
 KERNEL(k_xor, R8(DU), R8(OP_XOR), FINU)
 KERNEL(k_mul_lo_u32, R8(DU), R8(OP_MULLO), FINU)
@@ -161,7 +179,7 @@ typedef void (*kfn)(unsigned *, unsigned);
 struct K { const char *name; kfn f; };
 int main()
 {
-  K ks[] = {{"fma", k_fma},{"xor", k_xor},{"mul_lo_u32", k_mul_lo_u32},{"mul_hi_u32", k_mul_hi_u32},{"mad_u64_u32", k_mad_u64_u32},{"mul_u32_u24", k_mul_u32_u24},{"sqrt", k_sqrt},{"rcp", k_rcp},{"cvt_f32_u32", k_cvt_f32_u32},{"cndmask", k_cndmask},{"cndmask sgpr", k_cndmask_s},{"cmp+cndmask", k_cmp_cnd},{"med3_f32", k_med3},{"max_f32", k_max_f32},{"addc_co_u32", k_addc},{"cmp+addc", k_cmp_addc},{"add_u32", k_add_u32},{"add_f32_dpp", k_add_f32_dpp},{"bitop3_b32", k_bitop3},{"bitop3 v,v,s", k_bitop3_s},{"frexp_mant_f32", k_frexp_mant},{"ldexp_f32", k_ldexp},{"and_or_b32", k_and_or},{"pk_fma", k_pk_fma},{"pk_mul", k_pk_mul},{"sweep mov3", k_mov3},{"sweep fma2", k_fma2},{"mov_b64 s->v", k_mov64},{"fmac_f32_dpp", k_fmac_dpp},{"8fma+lds_b128", k_fma_lds},{"sweep pk2", k_pk2}};
+  K ks[] = {{"fma", k_fma},{"xor", k_xor},{"mul_lo_u32", k_mul_lo_u32},{"mul_hi_u32", k_mul_hi_u32},{"mad_u64_u32", k_mad_u64_u32},{"mul_u32_u24", k_mul_u32_u24},{"sqrt", k_sqrt},{"rcp", k_rcp},{"cvt_f32_u32", k_cvt_f32_u32},{"cndmask", k_cndmask},{"cndmask sgpr", k_cndmask_s},{"cmp+cndmask", k_cmp_cnd},{"med3_f32", k_med3},{"max_f32", k_max_f32},{"addc_co_u32", k_addc},{"cmp+addc", k_cmp_addc},{"add_u32", k_add_u32},{"add_f32_dpp", k_add_f32_dpp},{"bitop3_b32", k_bitop3},{"bitop3 v,v,s", k_bitop3_s},{"frexp_mant_f32", k_frexp_mant},{"ldexp_f32", k_ldexp},{"and_or_b32", k_and_or},{"pk_fma", k_pk_fma},{"pk_mul", k_pk_mul},{"sweep mov3", k_mov3},{"sweep fma2", k_fma2},{"mov_b64 s->v", k_mov64},{"fmac_f32_dpp", k_fmac_dpp},{"8fma+lds_b128", k_fma_lds},{"sweep pk2", k_pk2},{"add_f64", k_add_f64},{"mul_f64", k_mul_f64},{"dist_f64", k_dist_f64}};
   hipDeviceProp_t p; CHK(hipGetDeviceProperties(&p, 0));
   const int cus = p.multiProcessorCount;
   unsigned *out; CHK(hipMalloc(&out, (size_t)cus * 8 * 256 * 4 * 4));
