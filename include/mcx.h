@@ -1505,6 +1505,111 @@ int mcx_debug_modes_geometry(int np, int nsteps, int nc, int k, mcx_modes_geomet
  * 3 their reducers, 4 the table pass and its reducer (2 to 4: HIP events), 5 and 6 reserved (0), 7 the whole call (wall clock) */
 int mcx_debug_modes_times(mcx_engine *e, int first_step, int nsteps, const mcx_modes_spec *spec, mcx_modes_result *res, double *ms);
 
+/* ---- evidence of a run: log Z by bridge sampling, with its error -------------------------------------
+ * log Z = log of the integral of the sampled function L, from the rows of a view (their log L is in the store) and draws from
+ * a proposal g, a mixture of 1 <= k <= MCX_EVIDENCE_MAX_K Gaussians with full covariances, by the iterative bridge estimator of
+ * Meng & Wong with the relative error of Fruehwirth-Schnatter.  All of it is fp64 on the device through slabs and a
+ * fixed-order reducer: the same arguments give the same bytes.
+ *   proposal   mcx_evidence_mixture: weights[k] > 0, centres[k][np], covs[k][np][np] (row-major, the lower triangle is read),
+ *              scale > 0 multiplies every component's standard deviations.  NULL: k = 1, centre and covariance are section 10's
+ *              mean and covariance of the parameters over the first fit_steps steps of the view (default nsteps / 2), which are
+ *              then left out of the bridge; spec->scale scales it.  With a caller's proposal fit_steps defaults to 0.
+ *   log g(x)   u = (double)x - c_k, z = W_k u with W_k the inverse of the lower Cholesky factor C_k of scale^2 covs[k],
+ *              t_k = lc_k - sum z_i^2 / 2, lc_k = log(w_k / sum w) - sum log diag C_k - (np / 2) log 2 pi, log-sum-exp over k;
+ *              NaN for a row with a non-finite parameter
+ *   rows       N1 = (nsteps - fit_steps) * nc, l1_i = log L_i - log g(x_i); a non-finite l1 is MCX_ERR_INVALID naming the lowest
+ *              such row
+ *   draws      N2 = spec->ndraw (0: min(N1, 2^20)), Philox stream 8: the component of draw j from the uniform of block
+ *              (j, 0, 1, 0), its normals z[4b .. 4b+3] those of mcx_debug_normals(seed, 8, j, b, 0, 0), x~_i = (float)(c_i + sum_{l
+ *              <= i} C_il (double)z_l), l ascending, no fused multiply-add; log L of the draws by L's device code (the callback
+ *              for MCX_VL_HOST); l2_j = log L - log g(x~_j); log L = -inf or NaN counts as L = 0 (ndraw_zero), +inf is
+ *              MCX_ERR_INVALID, and so are draws that all have L = 0
+ *   bridge     neff = the lower median over the parameters of mcx_samples_summary's ess on the N1 rows, at most N1 (N1 itself
+ *              with use_neff = 0, or with MCX_EVIDENCE_NO_ESS when fewer than 4 steps remain or an ess is NaN); s1 = neff / (neff
+ *              + N2), s2 = N2 / (neff + N2); l* = mean l1; r <- (mean over draws of num) / (mean over rows of den) from r = 1 until
+ *              |delta log r| <= tol or max_iter passes (MCX_EVIDENCE_NOT_CONVERGED); log_z = log r + l*
+ *   error      f1 = p / (s1 p + s2) over the draws, f2 = 1 / (s1 p + s2) over the rows, p = e^(l - log_z); re2_draws = Var f1 /
+ *              (mean(f1)^2 N2), re2_rows = Var f2 / (mean(f2)^2 ess_f2) (variances with divisor n - 1), ess_f2 = the summary's ess
+ *              of the series f2 as a one-column store of floats (N1 when that is NaN or the range too short); se = sqrt of their sum
+ *   log_z_is   log mean e^(l2), importance sampling from g alone; log_z_ris = -log mean e^(-l1), the reciprocal estimator
+ * L: the sampled function (L->d = np); NULL for mcx_samples_evidence = the last run's.  mcx_store_evidence is for stores whose
+ * columns are the parameters (a text read back, chosen chains, a row set's store).
+ * MCX_ERR_INVALID before a device is touched: a NULL argument, k outside 1 .. 8, a weight <= 0, a scale that is not finite and
+ * positive, fit_steps outside [0, nsteps) (-1 = the default), a fitted proposal with fit_steps = 0, L->d != np, tol < 0 or NaN,
+ * max_iter < 0, ndraw < 0, a covariance that is not positive definite (the message names the component and the pivot).
+ * MCX_ERR_UNSUPPORTED: N1 or N2 >= 2^31. */
+enum { MCX_EVIDENCE_MAX_K = 8 };
+enum { MCX_EVIDENCE_NOT_CONVERGED = 1, MCX_EVIDENCE_NO_ESS = 2 };
+typedef struct mcx_evidence_mixture {
+  int k;                 /* 1 .. MCX_EVIDENCE_MAX_K */
+  int reserved;          /* 0 */
+  const double *weights; /* [k] */
+  const double *centres; /* [k][np] */
+  const double *covs;    /* [k][np][np] */
+  double scale;          /* > 0 */
+} mcx_evidence_mixture;
+typedef struct mcx_evidence_spec {
+  long long ndraw; /* 0: min(N1, 2^20) */
+  uint32_t seed;
+  int fit_steps;   /* -1: nsteps / 2 for a fitted proposal, 0 for a caller's */
+  int use_neff;    /* 0: neff = N1 */
+  int max_iter;    /* 0: 1000 */
+  double tol;      /* >= 0; 1e-10 is what the drivers use */
+  double scale;    /* of the fitted proposal, > 0 */
+} mcx_evidence_spec;
+typedef struct mcx_evidence_result {
+  long long n1, n2;
+  int k, fit_steps;
+  double neff, lstar, log_z, se, re2_draws, re2_rows, ess_f2, log_z_is, log_z_ris;
+  long long ndraw_zero;
+  int iters, flags; /* MCX_EVIDENCE_* */
+} mcx_evidence_result;
+int mcx_samples_evidence(mcx_engine *e, int first_step, int nsteps, const mcx_vlfunc *L, const mcx_evidence_spec *spec,
+                         const mcx_evidence_mixture *proposal, mcx_evidence_result *res);
+int mcx_rows_evidence(const float *rows, int nsteps, int nc, int np, const mcx_vlfunc *L, const mcx_evidence_spec *spec,
+                      const mcx_evidence_mixture *proposal, mcx_evidence_result *res);
+int mcx_store_evidence(mcx_store *s, const mcx_vlfunc *L, const mcx_evidence_spec *spec, const mcx_evidence_mixture *proposal,
+                       mcx_evidence_result *res);
+/* host only, no device: the factors of a proposal.  C[k][np][np] the lower Cholesky factors of scale^2 covs (may be NULL),
+ * W[k][np][np] their inverses (may be NULL), lc[k] */
+int mcx_evidence_proposal(int np, const mcx_evidence_mixture *m, double *C, double *W, double *lc);
+/* host only, no device: the estimator on host arrays l1[n1] and l2[n2] (an l2 of -inf is a draw with L = 0), by the update and
+ * finish functions of the device path with sums in index order.  The host has no spectral estimate: ess_f2 = n1.  Fills lstar,
+ * log_z, se, re2_draws, re2_rows, ess_f2, log_z_is, log_z_ris, ndraw_zero, iters, flags, n1, n2, neff of res (k = fit_steps = 0). */
+int mcx_evidence_iterate(const double *l1, long long n1, const double *l2, long long n2, double neff, double tol, int max_iter,
+                         mcx_evidence_result *res);
+/* tests only: log g of n host rows x[n][np] (parameters alone) under a proposal -> lg[n], by the sweep kernel of the calls */
+int mcx_debug_evidence_logg(const float *x, long long n, int np, const mcx_evidence_mixture *m, double *lg);
+/* tests only: the first ndraw draws of (seed, proposal): x[ndraw][np], comp[ndraw], lg[ndraw] = log g of the rounded rows, and with
+ * L not NULL ll[ndraw] = their log L as the calls evaluate it (any of the four may be NULL) */
+int mcx_debug_evidence_draws(int np, const mcx_evidence_mixture *m, const mcx_vlfunc *L, uint32_t seed, long long ndraw, float *x,
+                             int *comp, double *lg, float *ll);
+/* tests only: mcx_rows_evidence that also returns l1[N1] and l2[N2] as the bridge passes read them */
+int mcx_debug_evidence_l(const float *rows, int nsteps, int nc, int np, const mcx_vlfunc *L, const mcx_evidence_spec *spec,
+                         const mcx_evidence_mixture *proposal, mcx_evidence_result *res, double *l1, double *l2);
+/* host only, no device: the launch geometry of a call on n1 rows and n2 draws of np parameters */
+typedef struct mcx_evidence_geometry {
+  long long block;          /* threads per workgroup: 256 */
+  long long tile_rows;      /* R: rows per tile of the sweep, 64 up to np = 128 and 32 above */
+  long long slices;         /* 256 / R lanes per row, lane s taking the outputs i = s, s + slices, ... */
+  long long sweep_tiles, sweep_workgroups; /* tiles of n1 rows; workgroups, at most sweep_max_workgroups (each takes tiles in turn) */
+  long long sweep_max_workgroups;
+  long long sweep_lds_bytes;
+  long long use_mfma;       /* 0: the product runs on the vector unit at every np */
+  long long w_chunk_rows;   /* rows of W_k staged in LDS at a time: np when 2048 / np >= np, else 2048 / np rounded down to slices */
+  long long draw_rows;      /* draws per workgroup of the draw kernel: max(16, 256 / np) */
+  long long draw_workgroups, draw_lds_bytes;
+  long long terms_workgroups_rows, terms_workgroups_draws; /* of a bridge pass: ceil(n / 1024), at most 1024 each */
+  long long scratch_bytes;  /* of the call's own device buffers, without the likelihood's and the summary's */
+} mcx_evidence_geometry;
+int mcx_debug_evidence_geometry(int np, long long n1, long long n2, int k, mcx_evidence_geometry *g);
+/* mcx_samples_evidence with HIP events around its stages, for tools/evidence_bench.py.  ms[MCX_EVIDENCE_TIMES]: 0 the fit
+ * (section 10), 1 the draws, 2 the likelihood of the draws, 3 the sweep of the rows (k_ev_logg), 4 the sweep of the draws, 5 neff and
+ * ess_f2 (the summary passes), 6 all bridge passes with their reducers, 7 the whole call (wall clock) */
+enum { MCX_EVIDENCE_TIMES = 8 };
+int mcx_debug_evidence_times(mcx_engine *e, int first_step, int nsteps, const mcx_vlfunc *L, const mcx_evidence_spec *spec,
+                             const mcx_evidence_mixture *proposal, mcx_evidence_result *res, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -205,6 +205,32 @@ class ModesGeometry(C.Structure):
                                             "chains_workgroups", "steps_workgroups", "scratch_bytes")]
 
 
+class EvidenceMixtureC(C.Structure):
+    """include/mcx.h mcx_evidence_mixture"""
+    _fields_ = [("k", C.c_int), ("reserved", C.c_int), ("weights", C.POINTER(C.c_double)), ("centres", C.POINTER(C.c_double)),
+                ("covs", C.POINTER(C.c_double)), ("scale", C.c_double)]
+
+
+class EvidenceSpecC(C.Structure):
+    """include/mcx.h mcx_evidence_spec"""
+    _fields_ = [("ndraw", C.c_longlong), ("seed", C.c_uint32), ("fit_steps", C.c_int), ("use_neff", C.c_int), ("max_iter", C.c_int),
+                ("tol", C.c_double), ("scale", C.c_double)]
+
+
+class EvidenceResultC(C.Structure):
+    """include/mcx.h mcx_evidence_result"""
+    _fields_ = [("n1", C.c_longlong), ("n2", C.c_longlong), ("k", C.c_int), ("fit_steps", C.c_int)] + \
+               [(n, C.c_double) for n in ("neff", "lstar", "log_z", "se", "re2_draws", "re2_rows", "ess_f2", "log_z_is", "log_z_ris")] + \
+               [("ndraw_zero", C.c_longlong), ("iters", C.c_int), ("flags", C.c_int)]
+
+
+class EvidenceGeometry(C.Structure):
+    """include/mcx.h mcx_evidence_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "tile_rows", "slices", "sweep_tiles", "sweep_workgroups", "sweep_max_workgroups",
+                                            "sweep_lds_bytes", "use_mfma", "w_chunk_rows", "draw_rows", "draw_workgroups", "draw_lds_bytes",
+                                            "terms_workgroups_rows", "terms_workgroups_draws", "scratch_bytes")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 12), ("launches", C.c_uint64 * 12), ("chain_steps", C.c_uint64 * 12)]
 
@@ -397,6 +423,21 @@ def load():
                                    C.POINTER(C.c_longlong), dp],
         "mcx_debug_modes_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ModesGeometry)],
         "mcx_debug_modes_times": [vp, C.c_int, C.c_int, C.POINTER(ModesSpecC), C.POINTER(ModesResultC), dp],
+        "mcx_samples_evidence": [vp, C.c_int, C.c_int, C.POINTER(VLFunc), C.POINTER(EvidenceSpecC), C.POINTER(EvidenceMixtureC),
+                                 C.POINTER(EvidenceResultC)],
+        "mcx_rows_evidence": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(VLFunc), C.POINTER(EvidenceSpecC), C.POINTER(EvidenceMixtureC),
+                              C.POINTER(EvidenceResultC)],
+        "mcx_store_evidence": [vp, C.POINTER(VLFunc), C.POINTER(EvidenceSpecC), C.POINTER(EvidenceMixtureC), C.POINTER(EvidenceResultC)],
+        "mcx_evidence_proposal": [C.c_int, C.POINTER(EvidenceMixtureC), dp, dp, dp],
+        "mcx_evidence_iterate": [dp, C.c_longlong, dp, C.c_longlong, C.c_double, C.c_double, C.c_int, C.POINTER(EvidenceResultC)],
+        "mcx_debug_evidence_logg": [fp, C.c_longlong, C.c_int, C.POINTER(EvidenceMixtureC), dp],
+        "mcx_debug_evidence_draws": [C.c_int, C.POINTER(EvidenceMixtureC), C.POINTER(VLFunc), C.c_uint32, C.c_longlong, fp,
+                                     C.POINTER(C.c_int), dp, fp],
+        "mcx_debug_evidence_l": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(VLFunc), C.POINTER(EvidenceSpecC), C.POINTER(EvidenceMixtureC),
+                                 C.POINTER(EvidenceResultC), dp, dp],
+        "mcx_debug_evidence_geometry": [C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.POINTER(EvidenceGeometry)],
+        "mcx_debug_evidence_times": [vp, C.c_int, C.c_int, C.POINTER(VLFunc), C.POINTER(EvidenceSpecC), C.POINTER(EvidenceMixtureC),
+                                     C.POINTER(EvidenceResultC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

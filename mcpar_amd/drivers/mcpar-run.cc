@@ -20,6 +20,7 @@
 //             [--intervals FILE [--hdi P1,P2,...] [--interval-probs p1,p2,...]]
 //             [--mess FILE [--mess-max-lag L] [--mess-with-ll]] [--ccf FILE --ccf-lags L]
 //             [--modes FILE --modes-k K [--modes-seed S] [--modes-iter M] [--modes-raw] [--modes-centres FILE]]
+//             [--evidence FILE [--evidence-draws N] [--evidence-seed S] [--evidence-fit-steps F] [--evidence-modes K] [--evidence-scale S]]
 //             [--mode-weights FILE] [--mode-chains FILE] [--mode-occupancy FILE] [--mode-rows K,FILE] [--mode-summary K,FILE]
 //   mcpar-run --read FILE --nc NC [--np NP] [--read-skip K] [--read-rows N] [--quiet] [the analysis files above]
 // --func-source: the user's own likelihood as HIP source of device functions (SourceVLFunc, MCX_VL_SOURCE: compiled into
@@ -503,6 +504,95 @@ static int write_clip(const mcx_clip_spec &spec, const char *report_path, const 
   }
   mcx_rowset_destroy(rs);
   return rc;
+}
+
+// --evidence FILE: log Z of the sampled function by bridge sampling on the GPU (mcx_rows_evidence), after a
+// run on its rows and its likelihood, or after --read on the file's rows and the likelihood the likelihood flags name (--func,
+// --func-source, --par, --ncomp: with --evidence they do not start a run).  FILE holds the fields of mcx_evidence_result, one
+// `name value` per line, doubles with 17 significant digits.  The proposal is one Gaussian fitted on the first F steps
+// (--evidence-fit-steps, default nsamp / 2), which are then left out; with --evidence-modes K it is K Gaussians, the modes of those
+// first F steps (section 25, seed 0) with their weights, means and section 10's covariance of each mode's rows.  --evidence-draws N
+// (default min(rows, 2^20)), --evidence-seed S (default 0), --evidence-scale S (default 1) scales the proposal's standard deviations.
+struct EvidenceOpts {
+  std::string file;
+  long long ndraw = 0;
+  unsigned seed = 0;
+  int fit_steps = -1, modes_k = 0;
+  double scale = 1.0;
+  bool any_option = false;
+};
+
+static int evidence_host_fn(void *ctx, int npset, const float *x, float *y) { return (*static_cast<VLFunc *>(ctx))(npset, x, y); }
+
+static int write_evidence(const EvidenceOpts &eo, VLFunc *L, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--evidence: " << rows.size() << " rows stored, the evidence needs nsamp * nc of them\n";
+    return 1;
+  }
+  mcx_vlfunc f;
+  if (!L->device_descriptor(np, &f)) f = mcx_vlfunc{MCX_VL_HOST, np, 0, 0, evidence_host_fn, L};
+  const int fit = eo.fit_steps >= 0 ? eo.fit_steps : nsamp / 2;
+  mcx_evidence_spec spec = {eo.ndraw, eo.seed, fit, 1, 1000, 1e-10, eo.scale};
+  mcx_evidence_mixture mix = {eo.modes_k, 0, 0, 0, 0, eo.scale};
+  std::vector<double> wts, means, covs;
+  if (eo.modes_k > 0) {  // the proposal from the modes of the fitting steps
+    const int K = eo.modes_k;
+    if (K > MCX_EVIDENCE_MAX_K || fit < 1) {
+      std::cerr << "--evidence-modes " << K << ": 1 to " << MCX_EVIDENCE_MAX_K << " modes, fitted on at least one step\n";
+      return 1;
+    }
+    const size_t knp = (size_t)K * np, ncol = (size_t)np + 1;
+    mcx_modes_spec ms = {K, 50, 1, 16384, 0u, 0};
+    mcx_modes_result mr;
+    std::vector<mcx_mode_row> table((size_t)K);
+    std::vector<double> cs(knp), c(knp), sds(knp), scale((size_t)np), mean(ncol), cov(ncol * ncol);
+    means.resize(knp);
+    wts.resize((size_t)K);
+    covs.resize(knp * np);
+    mcx_modes *m = 0;
+    if (mcx_rows_modes(rows.getpset(0), fit, nc, np, &ms, &mr, table.data(), cs.data(), c.data(), means.data(), sds.data(), scale.data(), &m) !=
+        MCX_OK) {
+      std::cerr << "--evidence-modes: " << mcx_last_error() << "\n";
+      return 1;
+    }
+    int rc = 0;
+    for (int k = 0; rc == 0 && k < K; ++k) {
+      mcx_rowset *rs = 0;
+      mcx_store *st = 0;
+      long long n = 0;
+      wts[k] = table[k].weight;
+      if (mcx_rows_mode_rows(rows.getpset(0), fit, nc, np, m, k, &rs) != MCX_OK || mcx_rowset_shape(rs, &n, 0, 0) != MCX_OK ||
+          n >= (1ll << 31) || mcx_rowset_store(rs, 0, (int)n, 1, &st) != MCX_OK || mcx_store_covariance(st, mean.data(), cov.data(), 0) != MCX_OK) {
+        std::cerr << "--evidence-modes: mode " << k << ": " << mcx_last_error() << "\n";
+        rc = 1;
+      }
+      for (int i = 0; rc == 0 && i < np; ++i)
+        for (int j = 0; j < np; ++j) covs[((size_t)k * np + i) * np + j] = cov[(size_t)i * ncol + j];
+      mcx_store_destroy(st);
+      mcx_rowset_destroy(rs);
+    }
+    mcx_modes_destroy(m);
+    if (rc != 0) return rc;
+    mix.weights = wts.data();
+    mix.centres = means.data();
+    mix.covs = covs.data();
+  }
+  mcx_evidence_result r;
+  if (mcx_rows_evidence(rows.getpset(0), nsamp, nc, np, &f, &spec, eo.modes_k > 0 ? &mix : 0, &r) != MCX_OK) {
+    std::cerr << "--evidence: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *o = fopen(eo.file.c_str(), "w");
+  if (!o) {
+    std::cerr << "cannot open " << eo.file << "\n";
+    return 1;
+  }
+  fprintf(o, "n1 %lld\nn2 %lld\nk %d\nfit_steps %d\nneff %.17g\nlstar %.17g\nlog_z %.17g\nse %.17g\nre2_draws %.17g\nre2_rows %.17g\n", r.n1,
+          r.n2, r.k, r.fit_steps, r.neff, r.lstar, r.log_z, r.se, r.re2_draws, r.re2_rows);
+  fprintf(o, "ess_f2 %.17g\nlog_z_is %.17g\nlog_z_ris %.17g\nndraw_zero %lld\niters %d\nflags %d\n", r.ess_f2, r.log_z_is, r.log_z_ris,
+          r.ndraw_zero, r.iters, r.flags);
+  return fclose(o) != 0 ? 1 : 0;
 }
 
 // --modes and its companions: one modes call on MCout's rows (mcx_rows_modes), the files made of its tables and labels
@@ -1240,6 +1330,7 @@ int main(int argc, char *argv[])
   std::string step_table_file, intervals_file, mess_file, ccf_file;
   int mess_max_lag = 0, ccf_lags = 0;
   ModesFiles modes_files;
+  EvidenceOpts evidence;
   mcx_modes_spec modes_spec = {0, 50, 1, 16384, 0u, 0};
   bool mess_with_ll = false;
   std::vector<double> hdi_mass = {0.9}, interval_probs = {0.05, 0.5, 0.95};
@@ -1264,14 +1355,14 @@ int main(int argc, char *argv[])
   int derive_nout = 0;
   long long ndraw = 0;
   unsigned draw_seed = 8675309u;
-  std::string read_file, run_only;  // run_only: the first option given that only a run takes
+  std::string read_file, run_only, func_flag;  // run_only: the first option given that only a run takes
   bool np_given = false, nc_given = false;
   long long read_skip = 0, read_rows = -1;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : "0"; };
-    if (run_only.empty() && (a == "--func" || a == "--func-source" || a == "--nsamp" || a == "--nburn" || a == "--out" || a == "--stream-text"))
-      run_only = a;
+    if (run_only.empty() && (a == "--nsamp" || a == "--nburn" || a == "--out" || a == "--stream-text")) run_only = a;
+    if (func_flag.empty() && (a == "--func" || a == "--func-source")) func_flag = a;  // (run-only unless --evidence wants a likelihood)
     if (a == "--func") func = val();
     else if (a == "--func-source") func_source = val();
     else if (a == "--par") {
@@ -1387,6 +1478,12 @@ int main(int argc, char *argv[])
     else if (a == "--resample-n") resample_n = atoll(val());
     else if (a == "--resample-seed") resample_seed = (unsigned)strtoul(val(), 0, 10);
     else if (a == "--intervals") intervals_file = val();
+    else if (a == "--evidence") evidence.file = val();
+    else if (a == "--evidence-draws") { evidence.ndraw = atoll(val()); evidence.any_option = true; }
+    else if (a == "--evidence-seed") { evidence.seed = (unsigned)strtoul(val(), 0, 10); evidence.any_option = true; }
+    else if (a == "--evidence-fit-steps") { evidence.fit_steps = atoi(val()); evidence.any_option = true; }
+    else if (a == "--evidence-modes") { evidence.modes_k = atoi(val()); evidence.any_option = true; }
+    else if (a == "--evidence-scale") { evidence.scale = atof(val()); evidence.any_option = true; }
     else if (a == "--modes") modes_files.modes = val();
     else if (a == "--modes-k") modes_spec.k = atoi(val());
     else if (a == "--modes-seed") modes_spec.seed = (uint32_t)strtoul(val(), 0, 10);
@@ -1444,6 +1541,7 @@ int main(int argc, char *argv[])
   int size, rank;
   MPI_Comm_size(MPI_COMM_WORLD, &size);
   MPI_Comm_rank(MPI_COMM_WORLD, &rank);
+  if (run_only.empty() && evidence.file.empty()) run_only = func_flag;
   if (!read_file.empty() && (!run_only.empty() || !nc_given || size > 1)) {
     if (rank == 0) {
       if (!run_only.empty()) std::cerr << "--read parses a file, there is no run: not with " << run_only << "\n";
@@ -1526,6 +1624,23 @@ int main(int argc, char *argv[])
     if (rank == 0)
       std::cerr << "--modes and the --mode-* files need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!evidence.file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--evidence needs the rows on the host of a single rank: not with " << (stream_text ? "--stream-text" : "more than one rank")
+                << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (evidence.file.empty() && evidence.any_option) {
+    if (rank == 0) std::cerr << "--evidence-draws, --evidence-seed, --evidence-fit-steps, --evidence-modes and --evidence-scale belong to --evidence FILE\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!evidence.file.empty() && (evidence.ndraw < 0 || evidence.fit_steps < -1 || evidence.modes_k < 0)) {
+    if (rank == 0) std::cerr << "--evidence-draws, --evidence-fit-steps and --evidence-modes take numbers that are not negative\n";
     MPI_Finalize();
     return 2;
   }
@@ -1642,7 +1757,7 @@ int main(int argc, char *argv[])
   VLFunc *L = 0;
   std::vector<float> means, w;
   try {
-    if (!read_file.empty()) L = 0;  // (no run: no likelihood)
+    if (!read_file.empty() && evidence.file.empty()) L = 0;  // (no run: no likelihood unless --evidence evaluates one)
     else if (!func_source.empty()) {
       FILE *f = fopen(func_source.c_str(), "rb");
       if (!f) { std::cerr << "cannot read " << func_source << "\n"; return 2; }
@@ -1765,6 +1880,10 @@ int main(int argc, char *argv[])
   if ((!mess_file.empty() || !ccf_file.empty()) &&
       write_lagcov(mess_file.empty() ? 0 : mess_file.c_str(), ccf_file.empty() ? 0 : ccf_file.c_str(), mess_max_lag, mess_with_ll, ccf_lags,
                    rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (!evidence.file.empty() && write_evidence(evidence, L, rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

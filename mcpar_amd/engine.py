@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, Density2dSpecC,
+from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, EvidenceGeometry, EvidenceMixtureC, EvidenceResultC, EvidenceSpecC, Density2dSpecC,
                    DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, ModesGeometry, ModesResultC, ModesSpecC, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
@@ -106,6 +106,9 @@ LAGCOV_TIMES = 5
 DENSITY_GRID = 512  # grid points per column; a column's slots are [DENSITY_GRID + 1, 2] uint64 (cnt, frac)
 RANK_Z, RANK_Z_FOLDED, RANK_I05, RANK_I95 = 0, 1, 2, 3  # mcx_debug_rows_rank_transform's `what`
 DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
+EVIDENCE_MAX_K, EVIDENCE_TIMES = 8, 8                   # include/mcx.h MCX_EVIDENCE_MAX_K, MCX_EVIDENCE_TIMES
+EVIDENCE_NOT_CONVERGED, EVIDENCE_NO_ESS = 1, 2          # mcx_evidence_result.flags
+EVIDENCE_STREAM = 8                                     # the Philox stream of the proposal's draws
 
 
 def _fp(a):
@@ -661,6 +664,10 @@ class DerivedStore:
         t, nc, ncol = self.shape
         return _modes_call(lambda *a: load().mcx_store_modes(self.h, *a), _modes_spec(k, ncol - 1, **spec), ncol - 1, (t, nc, ncol),
                            lambda *a: load().mcx_store_mode_rows(self.h, *a))
+
+    def evidence(self, vl, proposal=None, **spec):
+        """mcx_store_evidence: Engine.evidence's dict for a store whose columns are the parameters vl was sampled in"""
+        return _evidence_call(lambda *a: load().mcx_store_evidence(self.h, *a), vl, proposal, **spec)
 
     def compare(self, other, iid=False):
         """compare_stores(self, other)"""
@@ -1415,6 +1422,121 @@ def debug_modes_geometry(np_, nsteps, nc, k):
     return {name: int(getattr(g, name)) for name, _ in ModesGeometry._fields_}
 
 
+# ---- evidence: log Z by bridge sampling ---------------------------------------------------------------------
+class Proposal:
+    """an mcx_evidence_mixture: weights [k], centres [k, np], covs [k, np, np] in float64 and a scale of the standard deviations"""
+
+    def __init__(self, weights, centres, covs, scale=1.0):
+        self.weights = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+        self.k = self.weights.size
+        self.centres = np.ascontiguousarray(np.asarray(centres, np.float64).reshape(self.k, -1))
+        self.np = self.centres.shape[1]
+        self.covs = np.ascontiguousarray(np.asarray(covs, np.float64).reshape(self.k, self.np, self.np))
+        self.scale = float(scale)
+        self.c = EvidenceMixtureC(self.k, 0, _dp(self.weights), _dp(self.centres), _dp(self.covs), self.scale)
+
+
+def _evidence_spec(ndraw=0, seed=0, fit_steps=-1, use_neff=True, max_iter=1000, tol=1e-10, scale=1.0):
+    return EvidenceSpecC(int(ndraw), int(seed) & 0xffffffff, int(fit_steps), 1 if use_neff else 0, int(max_iter), float(tol), float(scale))
+
+
+def _evidence_dict(res):
+    return {name: getattr(res, name) for name, _ in EvidenceResultC._fields_}
+
+
+def _evidence_call(fn, vl, proposal, **spec):
+    """fn(L, spec, proposal, res) of one of the evidence entry points -> the dict of mcx_evidence_result's fields"""
+    res, sp = EvidenceResultC(), _evidence_spec(**spec)
+    check(fn(None if vl is None else C.byref(vl), C.byref(sp), None if proposal is None else C.byref(proposal.c), C.byref(res)))
+    return _evidence_dict(res)
+
+
+def rows_evidence(rows, nsteps, nc, vl, proposal=None, **spec):
+    """mcx_rows_evidence: Engine.evidence's dict for rows [nsteps * nc, np + 1] on the host (MCout layout) and the likelihood vl
+    (make_vlfunc's struct) they were sampled from"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    np_ = rows.shape[1] - 1
+    return _evidence_call(lambda *a: load().mcx_rows_evidence(_fp(rows), nsteps, nc, np_, *a), vl, proposal, **spec)
+
+
+def evidence_proposal(proposal):
+    """mcx_evidence_proposal (host only): (C [k, np, np] lower Cholesky factors of scale^2 covs, W = their inverses, lc [k])"""
+    k, np_ = min(max(proposal.k, 1), EVIDENCE_MAX_K), proposal.np
+    Cf, W, lc = np.zeros((k, np_, np_)), np.zeros((k, np_, np_)), np.zeros(k)
+    check(load().mcx_evidence_proposal(np_, C.byref(proposal.c), _dp(Cf), _dp(W), _dp(lc)))
+    return Cf, W, lc
+
+
+def evidence_iterate(l1, l2, neff=None, tol=1e-10, max_iter=1000):
+    """mcx_evidence_iterate (host only): the bridge on host arrays l1 (rows) and l2 (draws; -inf = a draw with L = 0) -> the dict of
+    mcx_evidence_result's fields (ess_f2 = n1: the host has no spectral estimate).  neff None: n1"""
+    l1 = np.ascontiguousarray(np.asarray(l1, np.float64).reshape(-1))
+    l2 = np.ascontiguousarray(np.asarray(l2, np.float64).reshape(-1))
+    res = EvidenceResultC()
+    check(load().mcx_evidence_iterate(_dp(l1), l1.size, _dp(l2), l2.size, float(l1.size if neff is None else neff), float(tol),
+                                      int(max_iter), C.byref(res)))
+    return _evidence_dict(res)
+
+
+def proposal_from_modes(modes, scale=1.0, nc=1):
+    """a k-component Proposal from a Modes (section 25): the weights and centres (the modes' means) of the mode table, each
+    component's covariance from section 10 on the rows of that mode (modes.rows(k) as a store of nc pseudo-chains)"""
+    k = modes.k
+    np_ = modes.ncol - 1
+    covs = np.zeros((k, np_, np_))
+    for j in range(k):
+        rs = modes.rows(j)
+        try:
+            st = rs.store(nc=nc)
+            try:
+                covs[j] = st.covariance()["cov"][:np_, :np_]
+            finally:
+                st.close()
+        finally:
+            rs.close()
+    return Proposal(np.asarray(modes.table["weight"], np.float64), np.asarray(modes.table["mean"], np.float64), covs, scale)
+
+
+def debug_evidence_logg(x, proposal):
+    """mcx_debug_evidence_logg: log g of rows x [n, np] (parameters alone) by the sweep kernel -> lg [n] float64"""
+    x = np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1, proposal.np))
+    lg = np.zeros(x.shape[0])
+    check(load().mcx_debug_evidence_logg(_fp(x), x.shape[0], proposal.np, C.byref(proposal.c), _dp(lg)))
+    return lg
+
+
+def debug_evidence_draws(proposal, ndraw, seed=0, vl=None):
+    """mcx_debug_evidence_draws: (x [ndraw, np] float32, comp [ndraw] int32, lg [ndraw] float64, ll [ndraw] float32 or None)"""
+    n = max(int(ndraw), 1)
+    x, comp, lg = np.zeros((n, proposal.np), np.float32), np.zeros(n, np.int32), np.zeros(n)
+    ll = None if vl is None else np.zeros(n, np.float32)
+    check(load().mcx_debug_evidence_draws(proposal.np, C.byref(proposal.c), None if vl is None else C.byref(vl), int(seed) & 0xffffffff,
+                                          int(ndraw), _fp(x), comp.ctypes.data_as(C.POINTER(C.c_int)), _dp(lg),
+                                          None if ll is None else _fp(ll)))
+    return x, comp, lg, ll
+
+
+def debug_evidence_l(rows, nsteps, nc, vl, proposal=None, **spec):
+    """mcx_debug_evidence_l: (rows_evidence's dict, l1 [N1], l2 [N2]) as the bridge passes read them"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    np_ = rows.shape[1] - 1
+    sp = _evidence_spec(**spec)
+    fit = sp.fit_steps if sp.fit_steps >= 0 else (0 if proposal is not None else nsteps // 2)
+    n1 = max((nsteps - fit) * nc, 1)
+    n2 = sp.ndraw if sp.ndraw > 0 else min(n1, 1 << 20)
+    l1, l2, res = np.zeros(n1), np.zeros(n2), EvidenceResultC()
+    check(load().mcx_debug_evidence_l(_fp(rows), nsteps, nc, np_, C.byref(vl), C.byref(sp), None if proposal is None else C.byref(proposal.c),
+                                      C.byref(res), _dp(l1), _dp(l2)))
+    return _evidence_dict(res), l1, l2
+
+
+def debug_evidence_geometry(np_, n1, n2, k=1):
+    """mcx_debug_evidence_geometry (host only): the launch geometry of an evidence call as a dict of include/mcx.h's fields"""
+    g = EvidenceGeometry()
+    check(load().mcx_debug_evidence_geometry(np_, n1, n2, k, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in EvidenceGeometry._fields_}
+
+
 def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
     """mcx_debug_reweight_geometry (host only): the launch geometry of a reweight of N rows of ncol columns with nprobs
     probabilities and of a resample of K draws, as a dict of include/mcx.h's fields"""
@@ -2049,6 +2171,21 @@ class Engine:
         return _modes_call(lambda *a: load().mcx_samples_modes(self.h, first_step, nsteps, *a), _modes_spec(k, self.np, **spec), self.np,
                            (nsteps, self.nc, self.np + 1),
                            lambda *a: load().mcx_samples_mode_rows(self.h, first_step, nsteps, *a))
+
+    def evidence(self, vl=None, proposal=None, first_step=0, nsteps=None, **spec):
+        """mcx_samples_evidence of kept steps [first_step, first_step + nsteps): log Z of the sampled function by bridge sampling
+        -> a dict of mcx_evidence_result's fields (log_z, se, neff, iters, flags, the by-products log_z_is and log_z_ris, ...).
+        vl None: the last run's likelihood.  proposal None: one Gaussian fitted on the first fit_steps steps, which are then left
+        out.  spec: ndraw=0 (min(N1, 2^20)), seed=0, fit_steps=-1, use_neff=True, max_iter=1000, tol=1e-10, scale=1.0"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _evidence_call(lambda *a: load().mcx_samples_evidence(self.h, first_step, nsteps, *a), vl, proposal, **spec)
+
+    def evidence_times(self, vl=None, proposal=None, first_step=0, nsteps=None, **spec):
+        """mcx_debug_evidence_times: (ms[EVIDENCE_TIMES] of one evidence() call -- include/mcx.h lists them --, the result dict)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        ms = np.zeros(EVIDENCE_TIMES)
+        res = _evidence_call(lambda *a: load().mcx_debug_evidence_times(self.h, first_step, nsteps, *a, _dp(ms)), vl, proposal, **spec)
+        return ms, res
 
     def modes_times(self, k, first_step=0, nsteps=None, **spec):
         """mcx_debug_modes_times: (ms[MODES_TIMES] of one modes() call -- include/mcx.h lists them --, the result dict)"""
