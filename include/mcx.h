@@ -1610,6 +1610,127 @@ enum { MCX_EVIDENCE_TIMES = 8 };
 int mcx_debug_evidence_times(mcx_engine *e, int first_step, int nsteps, const mcx_vlfunc *L, const mcx_evidence_spec *spec,
                              const mcx_evidence_mixture *proposal, mcx_evidence_result *res, double *ms);
 
+/* ---- profile likelihoods of a store: per parameter, per pair, with intervals --------------------------
+ * pl_c(x) = max { log L(row) : the row's column c in the bin of x } - max log L, over the N = nsteps * nc rows of a view, 2 <= N <
+ * 2^32 (MCX_ERR_UNSUPPORTED from 2^32 on).  The columns profiled are the np parameters (of a derived store the nout outputs), not
+ * log L.  Integer maxima and integer adds on the device, serial host steps: the same arguments give the same bytes.
+ *   order      log L in section 9's float order as a u32 key k(l) = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000): -0 before
+ *              +0, a NaN counted as -inf.  The key of row r is K(r) = k(l_r) << 32 | (0xFFFFFFFF - r): its maximum is the largest
+ *              log L, the first row on ties; 0 is "empty"
+ *   grid       from / to: the column's min / max; with a clip pair other than (0, 1) its type-7 quantiles; the spec's from[c] /
+ *              to[c] over both where not NaN.  n bins, inv = n / (to - from); a value v goes to bin floor(((double)v - from) inv)
+ *              (no fused multiply-add), v == to to bin n - 1, anything else outside [0, n) is dropped; with to == from the
+ *              values equal to it go to bin 0
+ *   bin        cnt; the maximum key of its rows -> lmax (the row's log L as stored, -inf for a NaN), row; xat = the column's value
+ *              in that row, the abscissa of the curve; path = the whole row, log L last.  An empty bin has row -1, lmax -inf,
+ *              NaN xat, pl -inf, NaN plh and path
+ *   fit        lhat / row_hat: the maximum key of all N rows, binned or not; xhat the column's value there.  pl = (double)lmax -
+ *              (double)lhat.  A lhat that is not finite sets MCX_PROFILE_LL_NONFINITE and makes every pl, plh and interval NaN
+ *   hull       plh: the least concave majorant of the points (xat, pl) of the non-empty bins, evaluated at xat (Andrew's monotone
+ *              chain, a point popped on a cross product >= 0; between two vertices the chord, never below pl).  A non-empty bin at
+ *              pl = -inf takes no part and keeps -inf
+ *   intervals  per level p: drop = z^2 / 2, z the normal quantile of (1 + p) / 2 (levels_are_drops: the entries are drops); on
+ *              the raw curve and on the hull each, jl / jh the first / last non-empty bins with y >= -drop, the end the linear
+ *              interpolation at -drop towards the nearest non-empty bin outside (xat[jl] itself when that bin is at -inf), or
+ *              xat[jl] with MCX_PROFILE_OPEN_LO (MCX_PROFILE_HULL_OPEN_LO) when there is none; the upper end alike; NaN ends with
+ *              MCX_PROFILE_NO_BIN when no bin reaches the level.  nseg: the maximal runs of non-empty bins with pl >= -drop
+ *   pairs      cell (ia, ib) of pair (a, b), a != b, from each column's own grid at n = g, 8 <= g <= 64; a row counts when both
+ *              values are binned; z = lmax - lhat; levels by drop = -log(1 - p); nlevel = the non-empty cells with z >= -drop
+ * A column holding an inf or NaN has MCX_SUMMARY_NONFINITE, bins nothing and has NaN in every double of its record, curves and
+ * intervals (of its pairs: in z); every other column is what it would be without it. */
+enum { MCX_PROFILE_MAX_LEVELS = 8 };
+enum { MCX_PROFILE_LL_NONFINITE = 2, MCX_PROFILE_OPEN_LO = 4, MCX_PROFILE_OPEN_HI = 8, MCX_PROFILE_NO_BIN = 16,
+       MCX_PROFILE_HULL_OPEN_LO = 32, MCX_PROFILE_HULL_OPEN_HI = 64 };
+typedef struct mcx_profile_spec {
+  int n;                   /* bins per column, 2 .. 512 */
+  double clip_lo, clip_hi; /* (0, 1): from min to max */
+  const double *from, *to; /* [np], NaN for a column's default; may be NULL */
+  int nlevels;             /* 0: the levels 0.6827 and 0.9545; at most MCX_PROFILE_MAX_LEVELS */
+  const double *levels;    /* [nlevels] confidence levels in (0, 1), or drops of log L > 0 */
+  int levels_are_drops;
+} mcx_profile_spec;
+typedef struct mcx_col_profile {
+  double from, to, lhat, xhat;
+  long long row_hat, nvalues, nbinned, ndropped;
+  int nempty, flags; /* MCX_SUMMARY_NONFINITE, MCX_PROFILE_LL_NONFINITE */
+} mcx_col_profile;
+typedef struct mcx_profile_interval_t {
+  double p, drop, lo, hi, lo_hull, hi_hull; /* p is NaN where the spec gave drops */
+  int nseg, flags;                          /* MCX_PROFILE_OPEN_*, MCX_PROFILE_HULL_OPEN_*, MCX_PROFILE_NO_BIN, MCX_SUMMARY_NONFINITE */
+} mcx_profile_interval_t;
+/* Steps [first_step, first_step + nsteps) of the store; cols[np]; cnt, lmax, row, xat, pl, plh [np][n]; intervals[np][L], L =
+ * nlevels, or 2 for the defaults; path[np][n][np + 1] or NULL.  MCX_ERR_INVALID, before a device is touched, in the cases
+ * mcx_samples_density refuses (n outside 2 .. 512 for its n) and for nlevels outside 0 .. 8, a level outside (0, 1), a drop that is
+ * not positive and finite; MCX_ERR_ALLOC with the bytes needed in mcx_last_error when the scratch does not fit.  A queued
+ * MCX_OPT_ASYNC_RUN run is finished first. */
+int mcx_samples_profile(mcx_engine *e, int first_step, int nsteps, const mcx_profile_spec *spec, mcx_col_profile *cols,
+                        unsigned long long *cnt, float *lmax, long long *row, float *xat, double *pl, double *plh,
+                        mcx_profile_interval_t *intervals, float *path);
+/* the same of rows [nsteps * nc][np + 1] on the host (MCout layout), and of a derived store (its nout outputs) */
+int mcx_rows_profile(const float *rows, int nsteps, int nc, int np, const mcx_profile_spec *spec, mcx_col_profile *cols,
+                     unsigned long long *cnt, float *lmax, long long *row, float *xat, double *pl, double *plh,
+                     mcx_profile_interval_t *intervals, float *path);
+int mcx_store_profile(mcx_store *s, const mcx_profile_spec *spec, mcx_col_profile *cols, unsigned long long *cnt, float *lmax,
+                      long long *row, float *xat, double *pl, double *plh, mcx_profile_interval_t *intervals, float *path);
+typedef struct mcx_profile2d_spec {
+  int g;                   /* nodes per axis, 8 .. 64 */
+  double clip_lo, clip_hi;
+  const double *from, *to;
+  int npairs;              /* of pairs; not read when pairs is NULL */
+  const int *pairs;        /* [npairs][2] columns, or NULL: every a < b in ascending order */
+  int nlevels;
+  const double *levels;
+  int levels_are_drops;
+} mcx_profile2d_spec;
+typedef struct mcx_pair_profile {
+  int a, b;
+  long long nbinned; /* rows with both values binned */
+  int nempty, flags; /* MCX_SUMMARY_NONFINITE (one of the two columns), MCX_PROFILE_LL_NONFINITE */
+} mcx_pair_profile;
+/* cols[np] (from, to at n = g, lhat, xhat, row_hat, nvalues, flags; the counts are 0); pairs_out[npairs]; cnt, lmax, row, xat_a,
+ * xat_b, z [npairs][g][g], cell (ia, ib) at ia * g + ib; nlevel[npairs][L].  npairs = np (np - 1) / 2 when spec->pairs is NULL.
+ * The refusals of mcx_samples_profile and of mcx_samples_density2d's pair list over the np columns */
+int mcx_samples_profile2d(mcx_engine *e, int first_step, int nsteps, const mcx_profile2d_spec *spec, mcx_col_profile *cols,
+                          mcx_pair_profile *pairs_out, unsigned long long *cnt, float *lmax, long long *row, float *xat_a, float *xat_b,
+                          double *z, long long *nlevel);
+int mcx_rows_profile2d(const float *rows, int nsteps, int nc, int np, const mcx_profile2d_spec *spec, mcx_col_profile *cols,
+                       mcx_pair_profile *pairs_out, unsigned long long *cnt, float *lmax, long long *row, float *xat_a, float *xat_b,
+                       double *z, long long *nlevel);
+int mcx_store_profile2d(mcx_store *s, const mcx_profile2d_spec *spec, mcx_col_profile *cols, mcx_pair_profile *pairs_out,
+                        unsigned long long *cnt, float *lmax, long long *row, float *xat_a, float *xat_b, double *z, long long *nlevel);
+/* host only, no device: one curve -> one interval.  x[n] ascending over the non-empty bins and NaN for an empty one, y[n] the
+ * curve, drop > 0 -> lo, hi, nseg, flags (MCX_PROFILE_OPEN_LO / _OPEN_HI / _NO_BIN) */
+int mcx_profile_interval(int n, const double *x, const double *y, double drop, double *lo, double *hi, int *nseg, int *flags);
+/* host only: the drop of log L of a confidence level p for nparams = 1 (z^2 / 2) or 2 (-log(1 - p)) */
+int mcx_profile_drop(double p, int nparams, double *drop);
+/* host only: one column from its swept keys[n], cnt[n], xat[n] and the maximum key of all rows, by the functions of the calls */
+int mcx_debug_profile_finish(int n, const unsigned long long *keys, const unsigned long long *cnt, const float *xat, unsigned long long hat,
+                             int nlevels, const double *levels, int levels_are_drops, float *lmax, long long *row, double *pl, double *plh,
+                             mcx_profile_interval_t *intervals, long long *nbinned, int *nempty, int *flags);
+/* tests only: the sweep alone over host rows on given grids from[np] <= to[np] -> keys, cnt [np][n], hat[1] */
+int mcx_debug_rows_profile_bins(const float *rows, int nsteps, int nc, int np, int n, const double *from, const double *to,
+                                unsigned long long *keys, unsigned long long *cnt, unsigned long long *hat);
+/* host only, no device: the launch geometry of the sweeps of a call */
+typedef struct mcx_profile_geometry {
+  long long block;                /* threads per workgroup of k_profile_bins: 256 */
+  long long tile_columns;         /* ct = min(np, 8) adjacent columns per workgroup */
+  long long chains_per_workgroup; /* 256 / ct */
+  long long column_tiles, chain_blocks;
+  long long chunk_steps;          /* steps per workgroup: 2^16 / chains_per_workgroup, so that a bin's count stays a u32 */
+  long long chunks, workgroups;
+  long long lds_bytes;            /* 12 ct n */
+  long long unroll;               /* steps whose loads are issued together */
+  long long pair_block, pair_chunk_rows, pair_chunks, pair_workgroups, pair_lds_bytes; /* k_profile_pairs: 12 g^2 bytes */
+  long long scratch_bytes;        /* of a profile call without a path, behind the statistics' */
+} mcx_profile_geometry;
+int mcx_debug_profile_geometry(int np, int nsteps, int nc, int n, int g, int npairs, mcx_profile_geometry *geom);
+/* one call with its results let go, for tools/profile_bench.py.  Profile: ms[0] the statistics passes (wall clock), ms[1]
+ * k_profile_bins (HIP events), ms[2] the host grids and finish (wall clock), ms[3] the whole call.  Pairs: ms[0] the statistics,
+ * ms[1] k_profile_codes and k_profile_keys, ms[2] k_profile_pairs, ms[3] k_profile_at (HIP events), ms[4] the host, ms[5] the call */
+int mcx_debug_profile_times(mcx_engine *e, int first_step, int nsteps, const mcx_profile_spec *spec, double *ms);
+int mcx_debug_store_profile_times(mcx_store *s, const mcx_profile_spec *spec, double *ms);
+int mcx_debug_profile2d_times(mcx_engine *e, int first_step, int nsteps, const mcx_profile2d_spec *spec, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -231,6 +231,26 @@ class EvidenceGeometry(C.Structure):
                                             "terms_workgroups_rows", "terms_workgroups_draws", "scratch_bytes")]
 
 
+class ProfileSpecC(C.Structure):
+    """include/mcx.h mcx_profile_spec"""
+    _fields_ = [("n", C.c_int), ("clip_lo", C.c_double), ("clip_hi", C.c_double), ("from_", C.POINTER(C.c_double)),
+                ("to", C.POINTER(C.c_double)), ("nlevels", C.c_int), ("levels", C.POINTER(C.c_double)), ("levels_are_drops", C.c_int)]
+
+
+class Profile2dSpecC(C.Structure):
+    """include/mcx.h mcx_profile2d_spec"""
+    _fields_ = [("g", C.c_int), ("clip_lo", C.c_double), ("clip_hi", C.c_double), ("from_", C.POINTER(C.c_double)),
+                ("to", C.POINTER(C.c_double)), ("npairs", C.c_int), ("pairs", C.POINTER(C.c_int)), ("nlevels", C.c_int),
+                ("levels", C.POINTER(C.c_double)), ("levels_are_drops", C.c_int)]
+
+
+class ProfileGeometry(C.Structure):
+    """include/mcx.h mcx_profile_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "tile_columns", "chains_per_workgroup", "column_tiles", "chain_blocks", "chunk_steps",
+                                            "chunks", "workgroups", "lds_bytes", "unroll", "pair_block", "pair_chunk_rows", "pair_chunks",
+                                            "pair_workgroups", "pair_lds_bytes", "scratch_bytes")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 12), ("launches", C.c_uint64 * 12), ("chain_steps", C.c_uint64 * 12)]
 
@@ -438,6 +458,27 @@ def load():
         "mcx_debug_evidence_geometry": [C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.POINTER(EvidenceGeometry)],
         "mcx_debug_evidence_times": [vp, C.c_int, C.c_int, C.POINTER(VLFunc), C.POINTER(EvidenceSpecC), C.POINTER(EvidenceMixtureC),
                                      C.POINTER(EvidenceResultC), dp],
+        "mcx_samples_profile": [vp, C.c_int, C.c_int, C.POINTER(ProfileSpecC), vp, C.POINTER(C.c_ulonglong), fp, C.POINTER(C.c_longlong), fp,
+                                dp, dp, vp, fp],
+        "mcx_rows_profile": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(ProfileSpecC), vp, C.POINTER(C.c_ulonglong), fp, C.POINTER(C.c_longlong),
+                             fp, dp, dp, vp, fp],
+        "mcx_store_profile": [vp, C.POINTER(ProfileSpecC), vp, C.POINTER(C.c_ulonglong), fp, C.POINTER(C.c_longlong), fp, dp, dp, vp, fp],
+        "mcx_samples_profile2d": [vp, C.c_int, C.c_int, C.POINTER(Profile2dSpecC), vp, vp, C.POINTER(C.c_ulonglong), fp,
+                                  C.POINTER(C.c_longlong), fp, fp, dp, C.POINTER(C.c_longlong)],
+        "mcx_rows_profile2d": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(Profile2dSpecC), vp, vp, C.POINTER(C.c_ulonglong), fp,
+                               C.POINTER(C.c_longlong), fp, fp, dp, C.POINTER(C.c_longlong)],
+        "mcx_store_profile2d": [vp, C.POINTER(Profile2dSpecC), vp, vp, C.POINTER(C.c_ulonglong), fp, C.POINTER(C.c_longlong), fp, fp, dp,
+                                C.POINTER(C.c_longlong)],
+        "mcx_profile_interval": [C.c_int, dp, dp, C.c_double, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+        "mcx_profile_drop": [C.c_double, C.c_int, dp],
+        "mcx_debug_profile_finish": [C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), fp, C.c_ulonglong, C.c_int, dp, C.c_int, fp,
+                                     C.POINTER(C.c_longlong), dp, dp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+        "mcx_debug_rows_profile_bins": [fp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                        C.POINTER(C.c_ulonglong)],
+        "mcx_debug_profile_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ProfileGeometry)],
+        "mcx_debug_profile_times": [vp, C.c_int, C.c_int, C.POINTER(ProfileSpecC), dp],
+        "mcx_debug_store_profile_times": [vp, C.POINTER(ProfileSpecC), dp],
+        "mcx_debug_profile2d_times": [vp, C.c_int, C.c_int, C.POINTER(Profile2dSpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

@@ -9,6 +9,8 @@
 //             [--draws FILE --ndraw N [--draw-seed S]]
 //             [--density FILE] [--derived-density FILE] [--density-n N] [--density-clip QLO,QHI]
 //             [--density2d FILE] [--derived-density2d FILE] [--density2d-n G] [--density2d-pairs a:b,c:d,...]
+//             [--profile FILE] [--profile-intervals FILE] [--profile-path C,FILE] [--profile-n N] [--profile-levels p1,p2,...]
+//             [--profile-clip QLO,QHI] [--profile2d FILE] [--profile2d-n G] [--profile2d-pairs a:b,c:d,...]
 //             [--clip QLO,QHI] [--clip-ll-hi V] [--clip-report FILE] [--clipped FILE] [--clipped-density FILE [--clip-nc NC]]
 //             [--chain-table FILE] [--chain-keep Z[,MINMOVES[,MAXSTAY]]] [--kept-chains FILE] [--kept-summary FILE]
 //             [--step-table FILE [--step-probs p1,p2,...] [--settle TOLM[,TOLS[,REF]]]]
@@ -422,6 +424,135 @@ static int write_density2d(const char *path, const mcx_density2d_spec &spec, MCo
     return 1;
   }
   return print_density2d(path, o.pairs, o.axes, o.z, np, spec.g, 'p');
+}
+
+// --profile / --profile-intervals / --profile-path: the profile likelihood of every parameter of MCout's rows (mcx_rows_profile).
+// --profile: a header `column bin cnt row xat lmax pl plh`, then a line per (column, bin); --profile-intervals: `column p drop lo hi
+// lo_hull hi_hull nseg flags`, a line per (column, level); --profile-path C,FILE: `bin` and the names of the columns, then the whole
+// row of every non-empty bin of column C
+struct ProfileFiles {
+  std::string curves, intervals, path, pairs;
+  int path_col = -1;
+  std::vector<double> levels;
+  std::vector<int> pair_list;
+  mcx_profile_spec spec = {64, 0.0, 1.0, 0, 0, 0, 0, 0};
+  mcx_profile2d_spec spec2 = {32, 0.0, 1.0, 0, 0, 0, 0, 0, 0, 0};
+  bool any1() const { return !curves.empty() || !intervals.empty() || !path.empty(); }
+  bool any() const { return any1() || !pairs.empty(); }
+};
+
+static int write_profile(const ProfileFiles &pf, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || (long long)nsamp * nc < 2) {
+    std::cerr << "--profile: " << rows.size() << " rows stored, a profile needs nsamp * nc >= 2 of them\n";
+    return 1;
+  }
+  if (!pf.path.empty() && (pf.path_col < 0 || pf.path_col >= np)) {
+    std::cerr << "--profile-path C,FILE: C is a parameter, 0 to " << np - 1 << "\n";
+    return 1;
+  }
+  const size_t n = (size_t)(pf.spec.n > 0 && pf.spec.n <= 512 ? pf.spec.n : 512), ns = (size_t)np * n, ncol = (size_t)np + 1;
+  const int nl = pf.spec.nlevels > 0 ? (pf.spec.nlevels <= MCX_PROFILE_MAX_LEVELS ? pf.spec.nlevels : MCX_PROFILE_MAX_LEVELS) : 2;
+  std::vector<mcx_col_profile> cols(np);
+  std::vector<unsigned long long> cnt(ns);
+  std::vector<float> lmax(ns), xat(ns), path(pf.path.empty() ? 0 : ns * ncol);
+  std::vector<long long> row(ns);
+  std::vector<double> pl(ns), plh(ns);
+  std::vector<mcx_profile_interval_t> iv((size_t)np * nl);
+  if (mcx_rows_profile(rows.getpset(0), nsamp, nc, np, &pf.spec, cols.data(), cnt.data(), lmax.data(), row.data(), xat.data(), pl.data(),
+                       plh.data(), iv.data(), path.empty() ? 0 : path.data()) != MCX_OK) {
+    std::cerr << "--profile: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  if (!pf.curves.empty()) {
+    FILE *f = fopen(pf.curves.c_str(), "w");
+    if (!f) {
+      std::cerr << "cannot open " << pf.curves << "\n";
+      return 1;
+    }
+    fprintf(f, "column bin cnt row xat lmax pl plh\n");
+    for (int c = 0; c < np; ++c)
+      for (size_t j = 0; j < n; ++j) {
+        const size_t i = (size_t)c * n + j;
+        fprintf(f, "%s %zu %llu %lld %.9g %.9g %.17g %.17g\n", colname('p', c, np).c_str(), j, cnt[i], row[i], xat[i], lmax[i], pl[i], plh[i]);
+      }
+    if (fclose(f) != 0) return 1;
+  }
+  if (!pf.intervals.empty()) {
+    FILE *f = fopen(pf.intervals.c_str(), "w");
+    if (!f) {
+      std::cerr << "cannot open " << pf.intervals << "\n";
+      return 1;
+    }
+    fprintf(f, "column p drop lo hi lo_hull hi_hull nseg flags\n");
+    for (int c = 0; c < np; ++c)
+      for (int l = 0; l < nl; ++l) {
+        const mcx_profile_interval_t &v = iv[(size_t)c * nl + l];
+        fprintf(f, "%s %.17g %.17g %.17g %.17g %.17g %.17g %d %d\n", colname('p', c, np).c_str(), v.p, v.drop, v.lo, v.hi, v.lo_hull,
+                v.hi_hull, v.nseg, v.flags);
+      }
+    if (fclose(f) != 0) return 1;
+  }
+  if (!pf.path.empty()) {
+    FILE *f = fopen(pf.path.c_str(), "w");
+    if (!f) {
+      std::cerr << "cannot open " << pf.path << "\n";
+      return 1;
+    }
+    fprintf(f, "bin");
+    for (int c = 0; c <= np; ++c) fprintf(f, " %s", colname('p', c, np).c_str());
+    fprintf(f, "\n");
+    for (size_t j = 0; j < n; ++j) {
+      const size_t i = (size_t)pf.path_col * n + j;
+      if (row[i] < 0) continue;
+      fprintf(f, "%zu", j);
+      for (size_t c = 0; c < ncol; ++c) fprintf(f, " %.9g", path[i * ncol + c]);
+      fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) return 1;
+  }
+  return 0;
+}
+
+// --profile2d: the profile likelihood over the cells of pairs of parameters (mcx_rows_profile2d): a header `a b ia ib cnt row xat_a
+// xat_b lmax z`, then a line per (pair, cell), ia varying slowest
+static int write_profile2d(const ProfileFiles &pf, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || (long long)nsamp * nc < 2) {
+    std::cerr << "--profile2d: " << rows.size() << " rows stored, a profile needs nsamp * nc >= 2 of them\n";
+    return 1;
+  }
+  const mcx_profile2d_spec &sp = pf.spec2;
+  const size_t g = (size_t)(sp.g > 0 && sp.g <= 64 ? sp.g : 64);
+  size_t npairs = sp.pairs ? (size_t)(sp.npairs > 0 ? sp.npairs : 1) : (size_t)np * (np - 1) / 2;
+  if (npairs < 1 || npairs > 1024) npairs = 1;
+  const size_t ns = npairs * g * g;
+  std::vector<mcx_col_profile> cols(np);
+  std::vector<mcx_pair_profile> po(npairs);
+  std::vector<unsigned long long> cnt(ns);
+  std::vector<float> lmax(ns), xa(ns), xb(ns);
+  std::vector<long long> row(ns), nlev(npairs * MCX_PROFILE_MAX_LEVELS);
+  std::vector<double> z(ns);
+  if (mcx_rows_profile2d(rows.getpset(0), nsamp, nc, np, &sp, cols.data(), po.data(), cnt.data(), lmax.data(), row.data(), xa.data(), xb.data(),
+                         z.data(), nlev.data()) != MCX_OK) {
+    std::cerr << "--profile2d: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *f = fopen(pf.pairs.c_str(), "w");
+  if (!f) {
+    std::cerr << "cannot open " << pf.pairs << "\n";
+    return 1;
+  }
+  fprintf(f, "a b ia ib cnt row xat_a xat_b lmax z\n");
+  for (size_t p = 0; p < npairs; ++p) {
+    const std::string na = colname('p', po[p].a, np), nb = colname('p', po[p].b, np);
+    for (size_t j = 0; j < g; ++j)
+      for (size_t k = 0; k < g; ++k) {
+        const size_t i = (p * g + j) * g + k;
+        fprintf(f, "%s %s %zu %zu %llu %lld %.9g %.9g %.9g %.17g\n", na.c_str(), nb.c_str(), j, k, cnt[i], row[i], xa[i], xb[i], lmax[i], z[i]);
+      }
+  }
+  return fclose(f) == 0 ? 0 : 1;
 }
 
 // --clip-report / --clipped / --clipped-density: one clip of MCout's rows, the row set's files
@@ -1349,6 +1480,7 @@ int main(int argc, char *argv[])
   bool settle = false;
   mcx_density_spec density_spec = {512, 1.0, 0.0, 1.0, 0, 0, 0};
   std::string density2d_file, derived_density2d_file;
+  ProfileFiles profile_files;
   mcx_density2d_spec density2d_spec = {64, 1.0, 0.0, 1.0, 0, 0, 0, 0, 0};
   std::vector<int> density2d_pairs;
   std::vector<float> user_par, derive_par;
@@ -1406,6 +1538,50 @@ int main(int argc, char *argv[])
       if (sscanf(val(), "%lf,%lf", &density_spec.clip_lo, &density_spec.clip_hi) != 2) {
         std::cerr << "--density-clip takes QLO,QHI\n";
         return 2;
+      }
+    }
+    else if (a == "--profile") profile_files.curves = val();
+    else if (a == "--profile-intervals") profile_files.intervals = val();
+    else if (a == "--profile-n") profile_files.spec.n = atoi(val());
+    else if (a == "--profile2d") profile_files.pairs = val();
+    else if (a == "--profile2d-n") profile_files.spec2.g = atoi(val());
+    else if (a == "--profile-path") {
+      const char *v = val();
+      const char *comma = strchr(v, ',');
+      if (!comma || comma == v || !comma[1]) {
+        std::cerr << "--profile-path takes C,FILE\n";
+        return 2;
+      }
+      profile_files.path_col = atoi(v);
+      profile_files.path = comma + 1;
+    }
+    else if (a == "--profile-levels") {
+      for (const char *v = val(); *v;) {
+        char *end;
+        profile_files.levels.push_back(strtod(v, &end));
+        if (end == v || (*end && *end != ',')) {
+          std::cerr << "--profile-levels takes p1,p2,...\n";
+          return 2;
+        }
+        v = *end ? end + 1 : end;
+      }
+    }
+    else if (a == "--profile-clip") {
+      if (sscanf(val(), "%lf,%lf", &profile_files.spec.clip_lo, &profile_files.spec.clip_hi) != 2) {
+        std::cerr << "--profile-clip takes QLO,QHI\n";
+        return 2;
+      }
+    }
+    else if (a == "--profile2d-pairs") {
+      for (const char *v = val(); *v;) {
+        int pa, pb, used = 0;
+        if (sscanf(v, "%d:%d%n", &pa, &pb, &used) != 2 || (v[used] && v[used] != ',')) {
+          std::cerr << "--profile2d-pairs takes a:b,c:d,...\n";
+          return 2;
+        }
+        profile_files.pair_list.push_back(pa);
+        profile_files.pair_list.push_back(pb);
+        v += used + (v[used] ? 1 : 0);
       }
     }
     else if (a == "--density2d") density2d_file = val();
@@ -1531,6 +1707,16 @@ int main(int argc, char *argv[])
     else if (a == "--draw-seed") draw_seed = (unsigned)strtoul(val(), 0, 10);
     else { std::cerr << "unknown option " << a << "\n"; return 2; }
   }
+  profile_files.spec2.clip_lo = profile_files.spec.clip_lo;  // --profile-clip and --profile-levels apply to both
+  profile_files.spec2.clip_hi = profile_files.spec.clip_hi;
+  if (!profile_files.levels.empty()) {
+    profile_files.spec.nlevels = profile_files.spec2.nlevels = (int)profile_files.levels.size();
+    profile_files.spec.levels = profile_files.spec2.levels = profile_files.levels.data();
+  }
+  if (!profile_files.pair_list.empty()) {
+    profile_files.spec2.npairs = (int)(profile_files.pair_list.size() / 2);
+    profile_files.spec2.pairs = profile_files.pair_list.data();
+  }
   density2d_spec.clip_lo = density_spec.clip_lo;  // --density-clip applies to both
   density2d_spec.clip_hi = density_spec.clip_hi;
   if (!density2d_pairs.empty()) {
@@ -1572,6 +1758,13 @@ int main(int argc, char *argv[])
   if ((!covariance_file.empty() || !proposal_file.empty()) && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--covariance / --proposal need the rows on the host of a single rank: not with "
+                << (stream_text ? "--stream-text" : "more than one rank") << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (profile_files.any() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--profile, --profile-intervals, --profile-path and --profile2d need the rows on the host of a single rank: not with "
                 << (stream_text ? "--stream-text" : "more than one rank") << "\n";
     MPI_Finalize();
     return 2;
@@ -1857,6 +2050,14 @@ int main(int argc, char *argv[])
     return 2;
   }
   if (!density2d_file.empty() && write_density2d(density2d_file.c_str(), density2d_spec, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (profile_files.any1() && write_profile(profile_files, rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (!profile_files.pairs.empty() && write_profile2d(profile_files, rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

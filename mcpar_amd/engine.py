@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, EvidenceGeometry, EvidenceMixtureC, EvidenceResultC, EvidenceSpecC, Density2dSpecC,
-                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, ModesGeometry, ModesResultC, ModesSpecC, PlanItem, Profile, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
+                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, ModesGeometry, ModesResultC, ModesSpecC, PlanItem, Profile, Profile2dSpecC, ProfileGeometry, ProfileSpecC, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -109,6 +109,17 @@ DERIVE_LINEAR, DERIVE_SOURCE = 1, 2  # include/mcx.h mcx_derive.kind
 EVIDENCE_MAX_K, EVIDENCE_TIMES = 8, 8                   # include/mcx.h MCX_EVIDENCE_MAX_K, MCX_EVIDENCE_TIMES
 EVIDENCE_NOT_CONVERGED, EVIDENCE_NO_ESS = 1, 2          # mcx_evidence_result.flags
 EVIDENCE_STREAM = 8                                     # the Philox stream of the proposal's draws
+# include/mcx.h mcx_col_profile, mcx_profile_interval_t, mcx_pair_profile
+COL_PROFILE_DTYPE = np.dtype([("from", np.float64), ("to", np.float64), ("lhat", np.float64), ("xhat", np.float64), ("row_hat", np.int64),
+                              ("nvalues", np.int64), ("nbinned", np.int64), ("ndropped", np.int64), ("nempty", np.int32),
+                              ("flags", np.int32)], align=True)
+PROFILE_INTERVAL_DTYPE = np.dtype([("p", np.float64), ("drop", np.float64), ("lo", np.float64), ("hi", np.float64), ("lo_hull", np.float64),
+                                   ("hi_hull", np.float64), ("nseg", np.int32), ("flags", np.int32)], align=True)
+PAIR_PROFILE_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("nbinned", np.int64), ("nempty", np.int32), ("flags", np.int32)], align=True)
+assert COL_PROFILE_DTYPE.itemsize == 72 and PROFILE_INTERVAL_DTYPE.itemsize == 56 and PAIR_PROFILE_DTYPE.itemsize == 24
+PROFILE_MAX_LEVELS = 8  # include/mcx.h MCX_PROFILE_MAX_LEVELS
+# flags beside SUMMARY_NONFINITE: of a column or pair, then of an interval
+PROFILE_LL_NONFINITE, PROFILE_OPEN_LO, PROFILE_OPEN_HI, PROFILE_NO_BIN, PROFILE_HULL_OPEN_LO, PROFILE_HULL_OPEN_HI = 2, 4, 8, 16, 32, 64
 
 
 def _fp(a):
@@ -668,6 +679,26 @@ class DerivedStore:
     def evidence(self, vl, proposal=None, **spec):
         """mcx_store_evidence: Engine.evidence's dict for a store whose columns are the parameters vl was sampled in"""
         return _evidence_call(lambda *a: load().mcx_store_evidence(self.h, *a), vl, proposal, **spec)
+
+    def profile_likelihood(self, n=64, levels=None, drops=None, clip=(0, 1), from_=None, to=None, path=False):
+        """mcx_store_profile: Engine.profile_likelihood's dict for the columns of this store (of a derived store: the profile
+        likelihood of its outputs, functions of the parameters)"""
+        ncol = self.shape[2] - 1
+        spec = ProfileSpec(n, clip, from_, to, levels, drops).fits(ncol)
+        return _profile_call(lambda *a: load().mcx_store_profile(self.h, *a), spec, ncol, path)
+
+    def profile_likelihood2d(self, g=32, pairs=None, levels=None, drops=None, clip=(0, 1), from_=None, to=None):
+        """mcx_store_profile2d: Engine.profile_likelihood2d's dict for the columns of this store"""
+        ncol = self.shape[2] - 1
+        spec = ProfileSpec(g, clip, from_, to, levels, drops, pairs, two_d=True).fits(ncol)
+        return _profile2d_call(lambda *a: load().mcx_store_profile2d(self.h, *a), spec, ncol)
+
+    def profile_likelihood_times(self, n=64, clip=(0, 1)):
+        """mcx_debug_store_profile_times: Engine.profile_likelihood_times' four stage times for this store"""
+        spec = ProfileSpec(n, clip)
+        ms = np.zeros(4)
+        check(load().mcx_debug_store_profile_times(self.h, C.byref(spec.c), _dp(ms)))
+        return ms
 
     def compare(self, other, iid=False):
         """compare_stores(self, other)"""
@@ -1537,6 +1568,160 @@ def debug_evidence_geometry(np_, n1, n2, k=1):
     return {name: int(getattr(g, name)) for name, _ in EvidenceGeometry._fields_}
 
 
+# ---- profile likelihoods (include/mcx.h) ----
+def _ullp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+
+def _llp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+class ProfileSpec:
+    """an mcx_profile_spec / mcx_profile2d_spec and the arrays it points to: n bins per column (g nodes per axis with pairs or
+    two_d), clip = (qlo, qhi) quantiles as the range ((0, 1): min to max), from_ / to = None or [ncol] with NaN for a column's
+    default, levels = confidence levels in (0, 1) (None: 0.6827 and 0.9545) or drops = drops of log L instead"""
+
+    def __init__(self, n=64, clip=(0, 1), from_=None, to=None, levels=None, drops=None, pairs=None, two_d=False):
+        arr = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1))  # noqa: E731
+        ptr = lambda a: None if a is None else _dp(a)  # noqa: E731
+        if levels is not None and drops is not None:
+            raise ValueError("levels or drops, not both")
+        self.n, self.from_, self.to = int(n), arr(from_), arr(to)
+        self.lv = arr(drops if drops is not None else levels)
+        nlv = 0 if self.lv is None else self.lv.size
+        self.nlevels = nlv if nlv else 2
+        head = (self.n, float(clip[0]), float(clip[1]), ptr(self.from_), ptr(self.to))
+        tail = (nlv, ptr(self.lv) if nlv else None, int(drops is not None))
+        if two_d or pairs is not None:
+            self.pairs = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+            self.c = Profile2dSpecC(*head, 0 if self.pairs is None else self.pairs.shape[0],
+                                    None if self.pairs is None else self.pairs.ctypes.data_as(C.POINTER(C.c_int)), *tail)
+        else:
+            self.c = ProfileSpecC(*head, *tail)
+
+    def fits(self, ncol):
+        for a in (self.from_, self.to):
+            if a is not None and a.size != ncol:
+                raise ValueError("from_ and to take one entry per profiled column (%d), NaN for a column's default" % ncol)
+        return self
+
+    def npairs(self, ncol):
+        return ncol * (ncol - 1) // 2 if self.pairs is None else self.pairs.shape[0]
+
+
+def _profile_call(fn, spec, ncol, path):
+    """fn(spec, cols, cnt, lmax, row, xat, pl, plh, intervals, path) of one of the three profile entry points -> a dict: the
+    fields of mcx_col_profile as arrays [ncol] (from, to, lhat, xhat, row_hat, nvalues, nbinned, ndropped, nempty, flags); cnt,
+    lmax, row, xat, pl, plh [ncol, n]; intervals [ncol, L] of PROFILE_INTERVAL_DTYPE; path [ncol, n, ncol + 1] when asked"""
+    n = min(max(spec.n, 1), 512)  # (a refused n still gets buffers)
+    nl = min(spec.nlevels, PROFILE_MAX_LEVELS)
+    cols = np.zeros(ncol, COL_PROFILE_DTYPE)
+    cnt, lmax, row, xat = np.zeros((ncol, n), np.uint64), np.zeros((ncol, n), np.float32), np.zeros((ncol, n), np.int64), np.zeros((ncol, n), np.float32)
+    pl, plh, iv = np.zeros((ncol, n)), np.zeros((ncol, n)), np.zeros((ncol, nl), PROFILE_INTERVAL_DTYPE)
+    pa = np.zeros((ncol, n, ncol + 1), np.float32) if path else None
+    check(fn(C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), _ullp(cnt), _fp(lmax), _llp(row), _fp(xat), _dp(pl), _dp(plh),
+             iv.ctypes.data_as(C.c_void_p), None if pa is None else _fp(pa)))
+    out = {name: cols[name].copy() for name in COL_PROFILE_DTYPE.names}
+    out.update(cnt=cnt, lmax=lmax, row=row, xat=xat, pl=pl, plh=plh, intervals=iv)
+    if path:
+        out["path"] = pa
+    return out
+
+
+def _profile2d_call(fn, spec, ncol):
+    """fn(spec, cols, pairs_out, cnt, lmax, row, xat_a, xat_b, z, nlevel) -> a dict: from, to, lhat, xhat, row_hat, nvalues and
+    col_flags [ncol]; pairs [npairs, 2], nbinned, nempty, flags [npairs]; cnt, lmax, row, xat_a, xat_b, z [npairs, g, g], cell
+    (ia, ib) of the pair's two grids; drops [L], nlevel [npairs, L]"""
+    g = min(max(spec.n, 1), 64)  # (a refused g or list of pairs still gets buffers)
+    npairs = min(max(spec.npairs(ncol), 1), 1024)
+    nl = min(spec.nlevels, PROFILE_MAX_LEVELS)
+    cols, po = np.zeros(ncol, COL_PROFILE_DTYPE), np.zeros(npairs, PAIR_PROFILE_DTYPE)
+    sh = (npairs, g, g)
+    cnt, lmax, row = np.zeros(sh, np.uint64), np.zeros(sh, np.float32), np.zeros(sh, np.int64)
+    xa, xb, z, nlev = np.zeros(sh, np.float32), np.zeros(sh, np.float32), np.zeros(sh), np.zeros((npairs, nl), np.int64)
+    check(fn(C.byref(spec.c), cols.ctypes.data_as(C.c_void_p), po.ctypes.data_as(C.c_void_p), _ullp(cnt), _fp(lmax), _llp(row), _fp(xa),
+             _fp(xb), _dp(z), _llp(nlev)))
+    out = {name: cols[name].copy() for name in ("from", "to", "lhat", "xhat", "row_hat", "nvalues")}
+    out["col_flags"] = cols["flags"].copy()
+    out["pairs"] = np.stack([po["a"], po["b"]], axis=1)
+    out["nbinned"], out["nempty"], out["flags"] = po["nbinned"].copy(), po["nempty"].copy(), po["flags"].copy()
+    out.update(cnt=cnt, lmax=lmax, row=row, xat_a=xa, xat_b=xb, z=z, nlevel=nlev)
+    return out
+
+
+def rows_profile(rows, nsteps, nc, n=64, levels=None, drops=None, clip=(0, 1), from_=None, to=None, path=False):
+    """mcx_rows_profile: Engine.profile_likelihood's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1] - 1
+    spec = ProfileSpec(n, clip, from_, to, levels, drops).fits(ncol)
+    return _profile_call(lambda *a: load().mcx_rows_profile(_fp(rows), nsteps, nc, ncol, *a), spec, ncol, path)
+
+
+def rows_profile2d(rows, nsteps, nc, g=32, pairs=None, levels=None, drops=None, clip=(0, 1), from_=None, to=None):
+    """mcx_rows_profile2d: Engine.profile_likelihood2d's dict for rows [nsteps * nc, np + 1] on the host (MCout layout)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1] - 1
+    spec = ProfileSpec(g, clip, from_, to, levels, drops, pairs, two_d=True).fits(ncol)
+    return _profile2d_call(lambda *a: load().mcx_rows_profile2d(_fp(rows), nsteps, nc, ncol, *a), spec, ncol)
+
+
+def profile_interval(x, y, drop):
+    """mcx_profile_interval (host only): the outermost interval of the curve y at y >= -drop over the points x (ascending; NaN
+    for an empty bin) -> (lo, hi, nseg, flags)"""
+    x = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1))
+    y = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1))
+    if x.size != y.size:
+        raise ValueError("x and y take one entry per bin")
+    lo, hi, nseg, flags = C.c_double(0), C.c_double(0), C.c_int(0), C.c_int(0)
+    check(load().mcx_profile_interval(x.size, _dp(x), _dp(y), float(drop), C.byref(lo), C.byref(hi), C.byref(nseg), C.byref(flags)))
+    return lo.value, hi.value, nseg.value, flags.value
+
+
+def profile_drop(p, nparams=1):
+    """mcx_profile_drop (host only): the drop of log L of confidence level p for one parameter or a pair"""
+    d = C.c_double(0)
+    check(load().mcx_profile_drop(float(p), nparams, C.byref(d)))
+    return d.value
+
+
+def debug_profile_finish(keys, cnt, xat, hat, levels=None, drops=None):
+    """mcx_debug_profile_finish (host only): one column from its swept keys [n], counts [n], values at the keys [n] and the
+    maximum key of all rows -> a dict: lmax, row, pl, plh [n], intervals [L], nbinned, nempty, flags"""
+    keys, cnt = np.ascontiguousarray(keys, np.uint64), np.ascontiguousarray(cnt, np.uint64)
+    xat = np.ascontiguousarray(xat, np.float32)
+    n = keys.size
+    spec = ProfileSpec(2, levels=levels, drops=drops)
+    lmax, row, pl, plh = np.zeros(n, np.float32), np.zeros(n, np.int64), np.zeros(n), np.zeros(n)
+    iv = np.zeros(min(spec.nlevels, PROFILE_MAX_LEVELS), PROFILE_INTERVAL_DTYPE)
+    nb, ne, fl = C.c_longlong(0), C.c_int(0), C.c_int(0)
+    check(load().mcx_debug_profile_finish(n, _ullp(keys), _ullp(cnt), _fp(xat), int(hat), spec.c.nlevels, spec.c.levels, spec.c.levels_are_drops,
+                                          _fp(lmax), _llp(row), _dp(pl), _dp(plh), iv.ctypes.data_as(C.c_void_p), C.byref(nb), C.byref(ne),
+                                          C.byref(fl)))
+    return dict(lmax=lmax, row=row, pl=pl, plh=plh, intervals=iv, nbinned=nb.value, nempty=ne.value, flags=fl.value)
+
+
+def debug_rows_profile_bins(rows, nsteps, nc, n, from_, to):
+    """mcx_debug_rows_profile_bins: the sweep alone over rows [nsteps * nc, np + 1] on the grids from_ [np] <= to [np] -> (keys
+    [np, n] uint64, cnt [np, n] uint64, the maximum key of all rows)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1] - 1
+    from_ = np.ascontiguousarray(np.asarray(from_, np.float64).reshape(-1))
+    to = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1))
+    if from_.size != ncol or to.size != ncol:
+        raise ValueError("from_ and to take one entry per parameter")
+    keys, cnt, hat = np.zeros((ncol, max(n, 1)), np.uint64), np.zeros((ncol, max(n, 1)), np.uint64), np.zeros(1, np.uint64)
+    check(load().mcx_debug_rows_profile_bins(_fp(rows), nsteps, nc, ncol, n, _dp(from_), _dp(to), _ullp(keys), _ullp(cnt), _ullp(hat)))
+    return keys, cnt, int(hat[0])
+
+
+def debug_profile_geometry(np_, nsteps, nc, n=64, g=32, npairs=1):
+    """mcx_debug_profile_geometry (host only): the launch geometry of the sweeps of a profile and a pair profile call"""
+    geo = ProfileGeometry()
+    check(load().mcx_debug_profile_geometry(np_, nsteps, nc, n, g, npairs, C.byref(geo)))
+    return {name: int(getattr(geo, name)) for name, _ in ProfileGeometry._fields_}
+
+
 def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
     """mcx_debug_reweight_geometry (host only): the launch geometry of a reweight of N rows of ncol columns with nprobs
     probabilities and of a resample of K draws, as a dict of include/mcx.h's fields"""
@@ -2186,6 +2371,38 @@ class Engine:
         ms = np.zeros(EVIDENCE_TIMES)
         res = _evidence_call(lambda *a: load().mcx_debug_evidence_times(self.h, first_step, nsteps, *a, _dp(ms)), vl, proposal, **spec)
         return ms, res
+
+    def profile_likelihood(self, n=64, levels=None, drops=None, clip=(0, 1), from_=None, to=None, path=False, first_step=0, nsteps=None):
+        """mcx_samples_profile: per parameter of kept steps [first_step, first_step + nsteps) the profile likelihood pl(x) = max
+        { log L of the rows whose value is in the bin of x } - max log L on n bins, its least concave majorant plh, and per level
+        (confidence levels, or drops of log L) the interval where the curve is within the drop (_profile_call lists the fields).
+        xat, the value in the winning row, is the abscissa.  (Engine.profile is the kernel timing table; hence the name.)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        spec = ProfileSpec(n, clip, from_, to, levels, drops).fits(self.np)
+        return _profile_call(lambda *a: load().mcx_samples_profile(self.h, first_step, nsteps, *a), spec, self.np, path)
+
+    def profile_likelihood2d(self, g=32, pairs=None, levels=None, drops=None, clip=(0, 1), from_=None, to=None, first_step=0, nsteps=None):
+        """mcx_samples_profile2d: per pair of parameters (pairs [npairs, 2]; None: every a < b) the profile likelihood z = max log
+        L of the cell - max log L on g x g cells, for contours on the corner plot (_profile2d_call lists the fields)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        spec = ProfileSpec(g, clip, from_, to, levels, drops, pairs, two_d=True).fits(self.np)
+        return _profile2d_call(lambda *a: load().mcx_samples_profile2d(self.h, first_step, nsteps, *a), spec, self.np)
+
+    def profile_likelihood_times(self, n=64, clip=(0, 1), first_step=0, nsteps=None):
+        """mcx_debug_profile_times: ms of (the statistics passes, k_profile_bins, the host grids and finish, the whole call) of one
+        profile_likelihood() call"""
+        spec = ProfileSpec(n, clip)
+        ms = np.zeros(4)
+        self._on_store(load().mcx_debug_profile_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
+        return ms
+
+    def profile_likelihood2d_times(self, g=32, pairs=None, clip=(0, 1), first_step=0, nsteps=None):
+        """mcx_debug_profile2d_times: ms of (the statistics passes, the code and key sweeps, k_profile_pairs, k_profile_at, the host
+        grids and finish, the whole call) of one profile_likelihood2d() call"""
+        spec = ProfileSpec(g, clip, pairs=pairs, two_d=True)
+        ms = np.zeros(6)
+        self._on_store(load().mcx_debug_profile2d_times, first_step, nsteps, C.byref(spec.c), _dp(ms))
+        return ms
 
     def modes_times(self, k, first_step=0, nsteps=None, **spec):
         """mcx_debug_modes_times: (ms[MODES_TIMES] of one modes() call -- include/mcx.h lists them --, the result dict)"""
