@@ -16,7 +16,7 @@ OBJS = $(CSRC)/mcx_engine.o $(CSRC)/mcx_run.o $(CSRC)/mcx_plan.o $(CSRC)/mcx_exc
        $(CSRC)/mcx_ranks.o $(CSRC)/mcx_derive.o $(CSRC)/mcx_density.o $(CSRC)/mcx_clip.o $(CSRC)/mcx_chains.o $(CSRC)/mcx_density2d.o \
        $(CSRC)/mcx_steptable.o $(CSRC)/mcx_parse.o $(CSRC)/mcx_compare.o $(CSRC)/mcx_energy.o \
        $(CSRC)/mcx_reweight.o $(CSRC)/mcx_intervals.o $(CSRC)/mcx_lagcov.o $(CSRC)/mcx_modes.o \
-       $(CSRC)/mcx_evidence.o $(CSRC)/mcx_profile.o
+       $(CSRC)/mcx_evidence.o $(CSRC)/mcx_profile.o $(CSRC)/mcx_mutinfo.o
 HDRS = $(CSRC)/mcx_device.hpp $(CSRC)/mcx_block.hpp $(CSRC)/mcx_numerics.hpp $(CSRC)/mcx_launch.hpp $(CSRC)/mcx_persist.hpp $(CSRC)/mcx_engine_internal.hpp include/mcx.h
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
@@ -31,7 +31,7 @@ $(CSRC)/mcx_user.o: $(CSRC)/mcx_rtc_headers.inc
 $(CSRC)/mcx_murray.o: $(CSRC)/mcx_remote.hpp $(CSRC)/mcx_cull_proj.hpp $(CSRC)/mcx_screen.hpp
 $(CSRC)/mcx_sink.o: $(CSRC)/mcx_text.hpp $(CSRC)/fmt_g6.hpp
 $(CSRC)/mcx_k_fastb.o $(CSRC)/mcx_k_fastb_full.o: $(CSRC)/mcx_fastb.hpp
-$(CSRC)/mcx_summary.o $(CSRC)/mcx_covariance.o $(CSRC)/mcx_ranks.o $(CSRC)/mcx_derive.o $(CSRC)/mcx_density.o $(CSRC)/mcx_clip.o $(CSRC)/mcx_chains.o $(CSRC)/mcx_density2d.o $(CSRC)/mcx_steptable.o $(CSRC)/mcx_parse.o $(CSRC)/mcx_compare.o $(CSRC)/mcx_energy.o $(CSRC)/mcx_reweight.o $(CSRC)/mcx_intervals.o $(CSRC)/mcx_lagcov.o $(CSRC)/mcx_modes.o $(CSRC)/mcx_evidence.o $(CSRC)/mcx_profile.o: $(CSRC)/mcx_summary_kernels.hpp
+$(CSRC)/mcx_summary.o $(CSRC)/mcx_covariance.o $(CSRC)/mcx_ranks.o $(CSRC)/mcx_derive.o $(CSRC)/mcx_density.o $(CSRC)/mcx_clip.o $(CSRC)/mcx_chains.o $(CSRC)/mcx_density2d.o $(CSRC)/mcx_steptable.o $(CSRC)/mcx_parse.o $(CSRC)/mcx_compare.o $(CSRC)/mcx_energy.o $(CSRC)/mcx_reweight.o $(CSRC)/mcx_intervals.o $(CSRC)/mcx_lagcov.o $(CSRC)/mcx_modes.o $(CSRC)/mcx_evidence.o $(CSRC)/mcx_profile.o $(CSRC)/mcx_mutinfo.o: $(CSRC)/mcx_summary_kernels.hpp
 $(CSRC)/mcx_derive.o $(CSRC)/mcx_clip.o: $(CSRC)/mcx_derive.hpp $(CSRC)/mcx_store.hpp
 $(CSRC)/mcx_clip.o: $(CSRC)/mcx_clip_host.hpp
 $(CSRC)/mcx_chains.o: $(CSRC)/mcx_store.hpp $(CSRC)/mcx_chains_host.hpp
@@ -47,6 +47,7 @@ $(CSRC)/mcx_lagcov.o: $(CSRC)/mcx_store.hpp $(CSRC)/mcx_lagcov_host.hpp
 $(CSRC)/mcx_modes.o: $(CSRC)/mcx_derive.hpp $(CSRC)/mcx_store.hpp $(CSRC)/mcx_modes_host.hpp
 $(CSRC)/mcx_evidence.o: $(CSRC)/mcx_store.hpp $(CSRC)/mcx_evidence_host.hpp
 $(CSRC)/mcx_profile.o: $(CSRC)/mcx_store.hpp $(CSRC)/mcx_profile_host.hpp $(CSRC)/mcx_ppnd16.hpp
+$(CSRC)/mcx_mutinfo.o: $(CSRC)/mcx_store.hpp $(CSRC)/mcx_mutinfo_host.hpp
 
 mcpar_amd/libmcx.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS)

@@ -1731,6 +1731,105 @@ int mcx_debug_profile_times(mcx_engine *e, int first_step, int nsteps, const mcx
 int mcx_debug_store_profile_times(mcx_store *s, const mcx_profile_spec *spec, double *ms);
 int mcx_debug_profile2d_times(mcx_engine *e, int first_step, int nsteps, const mcx_profile2d_spec *spec, double *ms);
 
+/* ---- mutual information between columns of a store, on the device -------------------------------------
+ * Which columns depend on each other at all, and how strongly: the k-nearest-neighbour estimate of Kraskov, Stoegbauer and
+ * Grassberger (algorithm 1) of the mutual information of every column pair, in nats, with a permutation null.  Covariance and
+ * correlation (sections 10, 24) are blind to a curved valley or to several modes; this is not.  A store view has N = nsteps * nc
+ * rows in MCout order; the columns used are the parameters (a derived store's outputs), MCX_MUTINFO_WITH_LL adds the last one.
+ *   rows            spec.n > 0: the n rows floor(i N / n), i < n, evenly spaced in store order (n <= N); 0: n = min(N, 4096);
+ *                   -1: every row (N <= MCX_MUTINFO_MAX_ROWS).  2 <= n <= MCX_MUTINFO_MAX_ROWS
+ *   scale[c], flags section 21's, over the n selected rows: fp64, centred two-pass, divisor n - 1; a value that is not finite gives
+ *                   MCX_MUTINFO_COL_NONFINITE, scale 0 MCX_MUTINFO_COL_CONSTANT, the last column without MCX_MUTINFO_WITH_LL
+ *                   MCX_MUTINFO_COL_UNUSED and scale NaN; MCX_MUTINFO_RAW: scale = 1.  A pair with a flagged column has
+ *                   MCX_MUTINFO_PAIR_UNUSED and NaN everywhere
+ *   repeated rows   a rejected step repeats its row, and a repeated point is a neighbour at distance 0, which wrecks the estimate.
+ *                   A selected row is dropped when an earlier selected row equals it (float ==) in every column without a flag:
+ *                   m = n - ndup points are left, in selection order.  Dropping thins the cloud where the acceptance is low: the
+ *                   estimate then describes a cloud that is not quite the posterior's.  A large ndup says that the rows are too
+ *                   close in time: take fewer.  m <= k: every pair has MCX_MUTINFO_PAIR_FEW and NaN, and the call returns MCX_OK
+ *   z               z_ic = (double)x_ic / scale[c]
+ *   permutations    pi_0 the identity; p >= 1: a Fisher-Yates shuffle of [0, m) -- for i = 0 ... m - 2, w = philox4x32_10(counter
+ *                   (i, p, 0, 0), key (seed, 9)), r = w.x : w.y, j = i + ((r (m - i)) >> 64), swap.  One pi_p serves every pair
+ *   a pair under p  u_i = z_ia, v_i = z_{pi_p(i) b}; da_ij = |u_i - u_j|, db_ij = |v_i - v_j|, d_ij = max(da_ij, db_ij), every
+ *                   difference formed directly in fp64; eps_i the k-th smallest of {d_ij : j != i} with multiplicity (spec.k = 0: 3);
+ *                   na_i = #{j != i : da_ij < eps_i}, nb_i likewise (strict);
+ *                   mi_p = psi(k) + psi(m) - (1 / m) sum_i [psi(na_i + 1) + psi(nb_i + 1)], psi(q) = H_{q-1} - gamma from the table
+ *                   H_0 = 0, H_q = H_{q-1} + 1 / q
+ *   per pair        mi = mi_0; r_info = sqrt(1 - exp(-2 max(mi, 0))) (Linfoot: |rho| of a Gaussian pair); pearson over the m points
+ *                   (fp64, two-pass, on the host); nzero = #{i : eps_i = 0} at p = 0, above 0: MCX_MUTINFO_PAIR_TIES (an indicator
+ *                   column, say); perm_mean, perm_sd (divisor nperm - 1), nge = #{p >= 1 : mi_p >= mi}, p_value = (1 + nge) /
+ *                   (1 + nperm): NaN at nperm = 0 (perm_sd below 2)
+ *   pairs           spec.pairs == NULL: every a < b among the used columns, flagged ones included (more than 45 used columns:
+ *                   MCX_ERR_INVALID, name the pairs); else spec.pairs[npairs][2], 1 <= npairs <= MCX_MUTINFO_MAX_PAIRS, a != b, both
+ *                   used columns.  pairs[npairs] and perm_mi[npairs][nperm] come in that order
+ * The same store and arguments give the same bytes.  MCX_ERR_INVALID before anything is allocated: a NULL store, rows, res or
+ * pairs, unknown flags, sizes outside the limits.  cols[ncol] and perm_mi may be NULL; spec == NULL is all zeros.  The estimate
+ * assumes independent points: rows of a chain are not, which is why the default takes rows far apart.  Not built: an fp32 or
+ * packed form of the distances (the contract is fp64), more than two dimensions, rank coordinates. */
+enum { MCX_MUTINFO_WITH_LL = 1, MCX_MUTINFO_RAW = 2 };                                             /* mcx_mutinfo_spec.flags */
+enum { MCX_MUTINFO_COL_NONFINITE = 1, MCX_MUTINFO_COL_CONSTANT = 2, MCX_MUTINFO_COL_UNUSED = 4 };   /* mcx_mutinfo_col.flags */
+enum { MCX_MUTINFO_PAIR_UNUSED = 1, MCX_MUTINFO_PAIR_FEW = 2, MCX_MUTINFO_PAIR_TIES = 4 };          /* mcx_mutinfo_pair.flags */
+enum { MCX_MUTINFO_MAX_ROWS = 16384, MCX_MUTINFO_MAX_PERM = 999, MCX_MUTINFO_MAX_K = 8, MCX_MUTINFO_MAX_PAIRS = 1024 };
+typedef struct mcx_mutinfo_spec {
+  int n, k, nperm;
+  uint32_t seed;
+  unsigned flags;
+  int npairs;        /* with pairs: how many */
+  const int *pairs;  /* [npairs][2] or NULL */
+} mcx_mutinfo_spec;
+typedef struct mcx_mutinfo_result {
+  long long n_rows;  /* N */
+  int n_sel, ndup, m, k, npairs, nperm, nused;
+} mcx_mutinfo_result;
+typedef struct mcx_mutinfo_col {
+  double scale;
+  int flags;
+} mcx_mutinfo_col;
+typedef struct mcx_mutinfo_pair {
+  int a, b;
+  double mi, r_info, pearson, perm_mean, perm_sd, p_value;
+  long long nge, nzero;
+  int flags;
+} mcx_mutinfo_pair;
+int mcx_store_mutinfo(mcx_store *s, const mcx_mutinfo_spec *spec, mcx_mutinfo_result *res, mcx_mutinfo_col *cols, mcx_mutinfo_pair *pairs,
+                      double *perm_mi);
+int mcx_rows_mutinfo(const float *rows, int nsteps, int nc, int np, const mcx_mutinfo_spec *spec, mcx_mutinfo_result *res,
+                     mcx_mutinfo_col *cols, mcx_mutinfo_pair *pairs, double *perm_mi);
+/* a step range of an engine's store; a queued MCX_OPT_ASYNC_RUN run is finished first */
+int mcx_samples_mutinfo(mcx_engine *e, int first_step, int nsteps, const mcx_mutinfo_spec *spec, mcx_mutinfo_result *res,
+                        mcx_mutinfo_col *cols, mcx_mutinfo_pair *pairs, double *perm_mi);
+/* host only, no device touched.  index[n]: the rows floor(i N / n) of the rule above, 1 <= n <= min(N, MCX_MUTINFO_MAX_ROWS) */
+int mcx_debug_mutinfo_rows(long long N, int n, long long *index);
+/* perm[m] = pi_p, 1 <= m <= MCX_MUTINFO_MAX_ROWS, 0 <= p <= MCX_MUTINFO_MAX_PERM */
+int mcx_debug_mutinfo_perm(uint32_t seed, int m, int p, int *perm);
+/* table[q - 1] = psi(q), q = 1 ... q_max <= MCX_MUTINFO_MAX_ROWS: what a call uploads */
+int mcx_debug_mutinfo_psi(int q_max, double *table);
+/* eps, na, nb [m] of one pair under one permutation -> mi (the sum over i in index order, a point's two table values added first)
+ * and nzero; k < m <= MCX_MUTINFO_MAX_ROWS, 1 <= k <= MCX_MUTINFO_MAX_K, 0 <= na, nb < m */
+int mcx_mutinfo_finish(const double *eps, const int *na, const int *nb, int m, int k, double *mi, long long *nzero);
+/* the whole host half on host rows: res (n_rows, n_sel, ndup, m, k, nperm, nused; npairs as the call would have it), index[n_sel]
+ * the selected rows, kept[n_sel] (0: dropped as a repeat), cols[np + 1], z[np + 1][m] (column-major, the m kept points in order;
+ * a flagged column's stretch is 0; room for [np + 1][n_sel]).  Each output may be NULL */
+int mcx_debug_mutinfo_points(const float *rows, int nsteps, int nc, int np, const mcx_mutinfo_spec *spec, mcx_mutinfo_result *res,
+                             long long *index, unsigned char *kept, mcx_mutinfo_col *cols, double *z);
+/* the launch geometry of m points, npairs pairs, nperm permutations: k_mi_pairs has a grid of (tiles, pairs, 1 + nperm)
+ * workgroups of block threads, each lane with queries_per_lane queries, the m points streamed through LDS stage_rows at a time
+ * (MCX_MUTINFO_STAGE_ROWS lowers the stage to a multiple of 64: a knob for tests only) */
+typedef struct mcx_mutinfo_geometry {
+  long long block, queries_per_lane, tile_rows, stage_rows, stages, tiles, workgroups;
+  long long lds_bytes;      /* of a k_mi_pairs workgroup */
+  long long scratch_bytes;  /* the permutations, the table, the pair list, the partials and the sums; z takes 8 m bytes a column */
+} mcx_mutinfo_geometry;
+int mcx_debug_mutinfo_geometry(int m, int npairs, int nperm, int k, mcx_mutinfo_geometry *g);
+/* on the device: eps, na, nb [m] of pair `pair` of the call's list under permutation p, written by k_mi_pairs itself (the same
+ * kernel with an output pointer).  MCX_ERR_INVALID for a pair that has MCX_MUTINFO_PAIR_UNUSED or _FEW */
+int mcx_debug_mutinfo_counts(const float *rows, int nsteps, int nc, int np, const mcx_mutinfo_spec *spec, int pair, int p, double *eps,
+                             int *na, int *nb);
+/* one mcx_samples_mutinfo call, its results let go, ms[8]: 0 the gather, 3 the uploads, 4 k_mi_pairs, 5 the reducer and its copy
+ * (HIP events); 1 scale, flags, repeats and z, 2 the permutations and the table, 6 pearson and the null, 7 the whole call (the
+ * host's clock) */
+int mcx_debug_mutinfo_times(mcx_engine *e, int first_step, int nsteps, const mcx_mutinfo_spec *spec, double *ms);
+
 /* ---- the schedule of one run (host logic only, no device needed) --------------------------
  * mcx_run cuts MCPar::run's two loops (src/mcpar.cc:55-97, 99-210) into device launches between the
  * events it knows in advance: tuner checks, output dumps, exchanges and -- because the local/remote

@@ -17,10 +17,12 @@ from .engine import (debug_density2d_finish, debug_density2d_grid, debug_rows_de
                      rows_density2d)
 from .engine import (Proposal, evidence_iterate, evidence_proposal, proposal_from_modes, rows_evidence)  # noqa: F401
 from .engine import profile_drop, profile_interval, rows_profile, rows_profile2d  # noqa: F401
+from .engine import mutinfo_finish, rows_mutual_info  # noqa: F401
 
 __all__ = ["Engine", "McxError", "load", "lib_path", "make_vlfunc", "vlfunc_eval", "device_info", "RowSet", "clip_rows",
            "debug_clip_thresholds", "debug_store_geometry", "rows_density2d", "debug_density2d_grid", "debug_density2d_finish",
            "debug_rows_density2d_bins", "rows_chain_table", "keep_chains", "select_chains_rows", "debug_chains_geometry",
            "debug_numerics", "debug_normals", "DerivedStore", "derive_linear", "derive_source", "derive_rows",
            "debug_draw_indices", "debug_derive_compile", "user_source_available", "Proposal", "rows_evidence", "evidence_proposal",
-           "evidence_iterate", "proposal_from_modes", "rows_profile", "rows_profile2d", "profile_interval", "profile_drop"]
+           "evidence_iterate", "proposal_from_modes", "rows_profile", "rows_profile2d", "profile_interval", "profile_drop",
+           "rows_mutual_info", "mutinfo_finish"]

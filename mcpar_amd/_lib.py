@@ -121,6 +121,23 @@ class EnergyGeometry(C.Structure):
                                             "chunk_blocks", "chunks", "col_chunk", "workgroups", "lds_bytes", "scratch_bytes")]
 
 
+class MutinfoSpecC(C.Structure):
+    """include/mcx.h mcx_mutinfo_spec"""
+    _fields_ = [("n", C.c_int), ("k", C.c_int), ("nperm", C.c_int), ("seed", C.c_uint32), ("flags", C.c_uint), ("npairs", C.c_int),
+                ("pairs", C.POINTER(C.c_int))]
+
+
+class MutinfoResultC(C.Structure):
+    """include/mcx.h mcx_mutinfo_result"""
+    _fields_ = [("n_rows", C.c_longlong)] + [(n, C.c_int) for n in ("n_sel", "ndup", "m", "k", "npairs", "nperm", "nused")]
+
+
+class MutinfoGeometry(C.Structure):
+    """include/mcx.h mcx_mutinfo_geometry"""
+    _fields_ = [(n, C.c_longlong) for n in ("block", "queries_per_lane", "tile_rows", "stage_rows", "stages", "tiles", "workgroups",
+                                            "lds_bytes", "scratch_bytes")]
+
+
 class WeightsC(C.Structure):
     """include/mcx.h mcx_weights"""
     _fields_ = [("kind", C.c_int), ("logw", C.POINTER(C.c_float)), ("store", C.c_void_p), ("col", C.c_int), ("scale", C.c_double)]
@@ -479,6 +496,19 @@ def load():
         "mcx_debug_profile_times": [vp, C.c_int, C.c_int, C.POINTER(ProfileSpecC), dp],
         "mcx_debug_store_profile_times": [vp, C.POINTER(ProfileSpecC), dp],
         "mcx_debug_profile2d_times": [vp, C.c_int, C.c_int, C.POINTER(Profile2dSpecC), dp],
+        "mcx_store_mutinfo": [vp, C.POINTER(MutinfoSpecC), C.POINTER(MutinfoResultC), vp, vp, dp],
+        "mcx_rows_mutinfo": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(MutinfoSpecC), C.POINTER(MutinfoResultC), vp, vp, dp],
+        "mcx_samples_mutinfo": [vp, C.c_int, C.c_int, C.POINTER(MutinfoSpecC), C.POINTER(MutinfoResultC), vp, vp, dp],
+        "mcx_debug_mutinfo_rows": [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)],
+        "mcx_debug_mutinfo_perm": [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)],
+        "mcx_debug_mutinfo_psi": [C.c_int, dp],
+        "mcx_mutinfo_finish": [dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, dp, C.POINTER(C.c_longlong)],
+        "mcx_debug_mutinfo_points": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(MutinfoSpecC), C.POINTER(MutinfoResultC),
+                                     C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte), vp, dp],
+        "mcx_debug_mutinfo_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MutinfoGeometry)],
+        "mcx_debug_mutinfo_counts": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(MutinfoSpecC), C.c_int, C.c_int, dp, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int)],
+        "mcx_debug_mutinfo_times": [vp, C.c_int, C.c_int, C.POINTER(MutinfoSpecC), dp],
         "mcx_get_profile": [vp, C.POINTER(Profile)],
         "mcx_copy_to_host": [vp, vp, C.c_size_t, vp],
         "mcx_copy_to_device": [vp, vp, C.c_size_t, vp],

@@ -57,6 +57,24 @@ __global__ void __launch_bounds__(DERIVE_BLOCK) k_gather_rows(const float *x, co
   }
 }
 
+// rows[k][0..np] = (x[j], ly[j]) of store row j = floor(k N / n), k < n <= N: n rows evenly spaced in store order (section 28).
+// k < 2^14 there, so k * N stays below 2^64
+__global__ void __launch_bounds__(DERIVE_BLOCK) k_gather_spaced(const float *x, const float *ly, int np, uint64_t N, uint64_t n, float *rows)
+{
+  __shared__ uint64_t src[DERIVE_BLOCK];
+  const uint64_t base = (uint64_t)blockIdx.x * DERIVE_BLOCK;
+  const int cnt = n - base < (uint64_t)DERIVE_BLOCK ? (int)(n - base) : DERIVE_BLOCK, tid = (int)threadIdx.x;
+  if (tid < cnt) src[tid] = (base + tid) * N / n;
+  __syncthreads();
+  const int ncol = np + 1, total = cnt * ncol;
+  float *out = rows + base * (uint64_t)ncol;
+  for (int e = tid; e < total; e += DERIVE_BLOCK) {
+    const int r = e / ncol, c = e - r * ncol;
+    const uint64_t j = src[r];  // < N: floor(k N / n) with k < n
+    out[e] = c < np ? x[j * (uint64_t)np + c] : ly[j];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // the function of a row
 // ---------------------------------------------------------------------------------------------------------------------
@@ -226,6 +244,25 @@ uint64_t gather_chunk_rows(uint64_t n, uint64_t ncol)
 int gather_span(hipStream_t st, const StoreSpan &s, bool draw, uint32_t seed, uint64_t i0, uint64_t n, float *rows, int64_t *index)
 {
   return draw ? gather_to_host<true>(st, s, seed, i0, n, rows, index) : gather_to_host<false>(st, s, 0u, i0, n, rows, nullptr);
+}
+
+int gather_spaced(hipStream_t st, const StoreSpan &s, uint64_t n, float *rows)
+{
+  const uint64_t N = (uint64_t)s.T * (uint64_t)s.nc, ncol = (uint64_t)s.np + 1;
+  if (n == 0 || n > N || n > ((uint64_t)1 << 14)) return fail(MCX_ERR_INVALID, "gather_spaced: %llu rows of %llu", (unsigned long long)n, (unsigned long long)N);
+  DevBuf<float> dr;
+  auto run = [&]() -> int {
+    MCXCHK(dr.alloc((size_t)(n * ncol)));
+    hipLaunchKernelGGL(k_gather_spaced, dim3((unsigned)((n + DERIVE_BLOCK - 1) / DERIVE_BLOCK)), dim3(DERIVE_BLOCK), 0, st, s.x, s.ly, s.np, N, n,
+                       dr.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rows, dr.p, (size_t)(n * ncol) * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MCX_OK;
+  };
+  const int rc = run();
+  if (rc != MCX_OK) (void)hipStreamSynchronize(st);  // (before the buffer goes)
+  return rc;
 }
 
 namespace {

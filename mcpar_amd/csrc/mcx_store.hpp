@@ -24,6 +24,9 @@ struct mcx_store {
 // or with draw the rows of draws i0 .. i0 + n - 1 of seed among the span's T * nc rows and their indices (index may be NULL),
 // to the host in MCout layout
 MCXI int gather_span(hipStream_t st, const StoreSpan &s, bool draw, uint32_t seed, uint64_t i0, uint64_t n, float *rows, int64_t *index);
+// gather_span's sibling for section 28: the n <= 2^14 rows floor(k N / n), k < n, of the span's N = T * nc rows (n <= N), evenly
+// spaced in store order, to the host in MCout layout; one chunk (mcx_derive.hip)
+MCXI int gather_spaced(hipStream_t st, const StoreSpan &s, uint64_t n, float *rows);
 // the rows of one chunk of that gather when n rows of ncol floats are asked for (mcx_derive.hip)
 MCXI uint64_t gather_chunk_rows(uint64_t n, uint64_t ncol);
 

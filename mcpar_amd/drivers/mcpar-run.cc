@@ -17,6 +17,7 @@
 //             [--compare FILE --compare-to OTHER [--compare-nc NC]] [--compare-halves FILE] [--compare-iid]
 //             [--energy FILE --compare-to OTHER [--compare-nc NC]] [--energy-halves FILE] [--energy-n NA[,NB]] [--energy-perm P]
 //             [--energy-seed S] [--energy-with-ll] [--energy-raw]
+//             [--mutual-info FILE] [--mi-n N] [--mi-k K] [--mi-perm P] [--mi-seed S] [--mi-pairs a:b,c:d,...] [--mi-with-ll] [--mi-raw]
 //             [--reweight-temper BETA | --reweight-source FILE.hip | --reweight-logw FILE] [--reweight FILE]
 //             [--resampled FILE] [--resampled-density FILE] [--resample-n K] [--resample-seed S]
 //             [--intervals FILE [--hdi P1,P2,...] [--interval-probs p1,p2,...]]
@@ -1163,6 +1164,48 @@ static int write_energy(const char *path, const char *other, int other_nc, const
   return 0;
 }
 
+// --mutual-info FILE: which columns of MCout's rows depend on each other at all (mcx_rows_mutinfo): the
+// mutual information of every pair of parameters (--mi-pairs a:b,... names the pairs; --mi-with-ll adds log L) by the k-nearest-
+// neighbour estimator (--mi-k, default 3) on --mi-n rows evenly spaced in store order (default 0: min(rows, 4096); -1: every row),
+// scaled by their sd (--mi-raw: unscaled), under --mi-perm P (default 0) permutations of seed --mi-seed.  FILE: a header and one
+// line of the result's fields, then a header `a b mi r_info pearson perm_mean perm_sd p_value nge nzero flags` and one line per pair.
+// A warning goes to stderr when more than a tenth of the rows taken repeat an earlier one, or a pair has ties
+static int write_mutinfo(const char *path, const mcx_mutinfo_spec &spec, MCout &rows, int nsamp, int nc, int np)
+{
+  if ((long long)rows.size() != (long long)nsamp * nc || nsamp < 1) {
+    std::cerr << "--mutual-info: " << rows.size() << " rows stored, the analysis needs nsamp * nc of them\n";
+    return 1;
+  }
+  const int used = np + ((spec.flags & MCX_MUTINFO_WITH_LL) ? 1 : 0);
+  const size_t room = spec.pairs ? (size_t)std::max(spec.npairs, 1) : (size_t)std::max(used * (used - 1) / 2, 1);
+  mcx_mutinfo_result res;
+  std::vector<mcx_mutinfo_pair> pairs(room);
+  if (mcx_rows_mutinfo(rows.getpset(0), nsamp, nc, np, &spec, &res, 0, pairs.data(), 0) != MCX_OK) {
+    std::cerr << "--mutual-info: " << mcx_last_error() << "\n";
+    return 1;
+  }
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    std::cerr << "cannot open " << path << "\n";
+    return 1;
+  }
+  fprintf(f, "n_rows n_sel ndup m k npairs nperm nused\n");
+  fprintf(f, "%lld %d %d %d %d %d %d %d\n", res.n_rows, res.n_sel, res.ndup, res.m, res.k, res.npairs, res.nperm, res.nused);
+  fprintf(f, "a b mi r_info pearson perm_mean perm_sd p_value nge nzero flags\n");
+  int ties = 0;
+  for (int i = 0; i < res.npairs; ++i) {
+    const mcx_mutinfo_pair &o = pairs[(size_t)i];
+    fprintf(f, "%s %s %.17g %.17g %.17g %.17g %.17g %.17g %lld %lld %d\n", colname('p', o.a, np).c_str(), colname('p', o.b, np).c_str(), o.mi,
+            o.r_info, o.pearson, o.perm_mean, o.perm_sd, o.p_value, o.nge, o.nzero, o.flags);
+    if (o.flags & MCX_MUTINFO_PAIR_TIES) ++ties;
+  }
+  if (res.ndup * 10 > res.n_sel)
+    std::cerr << "--mutual-info: warning: " << res.ndup << " of the " << res.n_sel
+              << " rows taken repeat an earlier one and were dropped: the rows are too close in time, take fewer (--mi-n)\n";
+  if (ties > 0) std::cerr << "--mutual-info: warning: " << ties << " pairs have points whose k nearest neighbours are at distance 0 (flags & 4)\n";
+  return fclose(f) == 0 ? 0 : 1;
+}
+
 // --reweight-temper / --reweight-source / --reweight-logw: the weight source of --reweight, --resampled and --resampled-density
 struct ReweightSource {
   bool temper = false;
@@ -1471,6 +1514,10 @@ int main(int argc, char *argv[])
   std::string energy_file, energy_halves_file;
   mcx_energy_spec energy_spec = {0, 0, 999, 0u, 0u};
   bool energy_opts = false;
+  std::string mutinfo_file;
+  mcx_mutinfo_spec mutinfo_spec = {0, 0, 0, 0u, 0u, 0, 0};
+  std::vector<int> mutinfo_pairs;
+  bool mutinfo_opts = false;
   ReweightSource reweight_source;
   std::string reweight_file, resampled_file, resampled_density_file;
   long long resample_n = 0;
@@ -1624,6 +1671,29 @@ int main(int argc, char *argv[])
     else if (a == "--compare-nc") compare_nc = atoi(val());
     else if (a == "--compare-iid") compare_iid = true;
     else if (a == "--compare-halves") compare_halves_file = val();
+    else if (a == "--mutual-info") mutinfo_file = val();
+    else if (a == "--mi-n" || a == "--mi-k" || a == "--mi-perm") {
+      (a == "--mi-n" ? mutinfo_spec.n : a == "--mi-k" ? mutinfo_spec.k : mutinfo_spec.nperm) = atoi(val());
+      mutinfo_opts = true;
+    } else if (a == "--mi-seed") {
+      mutinfo_spec.seed = (uint32_t)strtoul(val(), 0, 10);
+      mutinfo_opts = true;
+    } else if (a == "--mi-with-ll" || a == "--mi-raw") {
+      mutinfo_spec.flags |= a == "--mi-raw" ? MCX_MUTINFO_RAW : MCX_MUTINFO_WITH_LL;
+      mutinfo_opts = true;
+    } else if (a == "--mi-pairs") {
+      for (const char *v = val(); *v;) {
+        int pa, pb, used = 0;
+        if (sscanf(v, "%d:%d%n", &pa, &pb, &used) != 2 || (v[used] && v[used] != ',')) {
+          std::cerr << "--mi-pairs takes a:b,c:d,...\n";
+          return 2;
+        }
+        mutinfo_pairs.push_back(pa);
+        mutinfo_pairs.push_back(pb);
+        v += used + (v[used] ? 1 : 0);
+      }
+      mutinfo_opts = true;
+    }
     else if (a == "--energy") energy_file = val();
     else if (a == "--energy-halves") energy_halves_file = val();
     else if (a == "--energy-n") {
@@ -1874,6 +1944,22 @@ int main(int argc, char *argv[])
     MPI_Finalize();
     return 2;
   }
+  if (mutinfo_opts && mutinfo_file.empty()) {
+    if (rank == 0) std::cerr << "--mi-n, --mi-k, --mi-perm, --mi-seed, --mi-pairs, --mi-with-ll and --mi-raw belong to --mutual-info\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!mutinfo_file.empty() && (stream_text || size > 1)) {
+    if (rank == 0)
+      std::cerr << "--mutual-info needs the rows on the host of a single rank: not with " << (stream_text ? "--stream-text" : "more than one rank")
+                << "\n";
+    MPI_Finalize();
+    return 2;
+  }
+  if (!mutinfo_pairs.empty()) {
+    mutinfo_spec.npairs = (int)(mutinfo_pairs.size() / 2);
+    mutinfo_spec.pairs = mutinfo_pairs.data();
+  }
   if (want_energy && (stream_text || size > 1)) {
     if (rank == 0)
       std::cerr << "--energy and --energy-halves need the rows on the host of a single rank: not with "
@@ -2103,6 +2189,10 @@ int main(int argc, char *argv[])
   }
   if (want_energy && write_energy(energy_file.empty() ? 0 : energy_file.c_str(), compare_to_file.c_str(), compare_nc ? compare_nc : nc,
                                   energy_spec, energy_halves_file.empty() ? 0 : energy_halves_file.c_str(), rslts, nsamp, nc, np) != 0) {
+    MPI_Finalize();
+    return 2;
+  }
+  if (!mutinfo_file.empty() && write_mutinfo(mutinfo_file.c_str(), mutinfo_spec, rslts, nsamp, nc, np) != 0) {
     MPI_Finalize();
     return 2;
   }

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (HOSTFN, K_NAMES, OUTFN, SINKFN, TEXTSINKFN, XCHGFN, ChainRule, ChainsGeometry, ClipSpecC, CompareGeometry, CompareSpecC, Counters, EnergyGeometry, EnergyResultC, EnergySpecC, EvidenceGeometry, EvidenceMixtureC, EvidenceResultC, EvidenceSpecC, Density2dSpecC,
-                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, ModesGeometry, ModesResultC, ModesSpecC, PlanItem, Profile, Profile2dSpecC, ProfileGeometry, ProfileSpecC, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
+                   DensitySpecC, Derive, IntervalSpecC, IntervalsGeometry, LagcovGeometry, LagcovResultC, LagcovSpecC, ModesGeometry, ModesResultC, ModesSpecC, MutinfoGeometry, MutinfoResultC, MutinfoSpecC, PlanItem, Profile, Profile2dSpecC, ProfileGeometry, ProfileSpecC, ReweightGeometry, ReweightResultC, StepRule, SteptableGeometry, StoreGeometry, TextReport, TextSpec, VLFunc, WeightsC, check, load)
 from ._lib import ERR_NONFINITE  # noqa: F401
 
 VL_ROSENBROCK1, VL_ROSENBROCK2, VL_GAUSSIAN, VL_DUALGAUSS, VL_GAUSSMIX, VL_HOST = 1, 2, 3, 4, 5, 100
@@ -79,6 +79,16 @@ assert ENERGY_COL_DTYPE.itemsize == 16
 ENERGY_WITH_LL, ENERGY_RAW = 1, 2                                        # mcx_energy_spec.flags
 ENERGY_COL_NONFINITE, ENERGY_COL_CONSTANT, ENERGY_COL_UNUSED = 1, 2, 4   # mcx_energy_col.flags
 ENERGY_MAX_SIDE, ENERGY_MAX_PERM = 16384, 4095
+MUTINFO_COL_DTYPE = np.dtype([("scale", np.float64), ("flags", np.int32)], align=True)  # include/mcx.h mcx_mutinfo_col
+MUTINFO_PAIR_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("mi", np.float64), ("r_info", np.float64), ("pearson", np.float64),
+                               ("perm_mean", np.float64), ("perm_sd", np.float64), ("p_value", np.float64), ("nge", np.int64),
+                               ("nzero", np.int64), ("flags", np.int32)], align=True)  # include/mcx.h mcx_mutinfo_pair
+assert MUTINFO_COL_DTYPE.itemsize == 16 and MUTINFO_PAIR_DTYPE.itemsize == 80
+MUTINFO_WITH_LL, MUTINFO_RAW = 1, 2                                          # mcx_mutinfo_spec.flags
+MUTINFO_COL_NONFINITE, MUTINFO_COL_CONSTANT, MUTINFO_COL_UNUSED = 1, 2, 4    # mcx_mutinfo_col.flags
+MUTINFO_PAIR_UNUSED, MUTINFO_PAIR_FEW, MUTINFO_PAIR_TIES = 1, 2, 4           # mcx_mutinfo_pair.flags
+MUTINFO_MAX_ROWS, MUTINFO_MAX_PERM, MUTINFO_MAX_K = 16384, 999, 8
+MUTINFO_MAX_PAIRS = 1024
 # include/mcx.h mcx_col_reweight
 REWEIGHT_DTYPE = np.dtype([("mean", np.float64), ("sd", np.float64), ("mcse_mean", np.float64), ("min", np.float32), ("max", np.float32),
                            ("flags", np.int32), ("reserved", np.int32)], align=True)
@@ -708,6 +718,10 @@ class DerivedStore:
         """energy_stores(self, other)"""
         return energy_stores(self, other, **kw)
 
+    def mutual_info(self, **kw):
+        """mcx_store_mutinfo: rows_mutual_info's dict for this store's outputs (with_ll: and its last column)"""
+        return _mutinfo_call(lambda *a: load().mcx_store_mutinfo(self.h, *a), self.shape[2], **kw)
+
 
 def derive_rows(rows, nsteps, nc, spec):
     """mcx_rows_derive: the DerivedStore of rows [nsteps * nc, np + 1] on the host (MCout layout)"""
@@ -1094,6 +1108,119 @@ def debug_energy_geometry(n_a, n_b, nused, nperm):
     g = EnergyGeometry()
     check(load().mcx_debug_energy_geometry(n_a, n_b, nused, nperm, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in EnergyGeometry._fields_}
+
+
+# ---- mutual information between columns of a store (include/mcx.h) ----
+class _MutinfoSpec:
+    """mcx_mutinfo_spec and the array its pair list points into"""
+
+    def __init__(self, n=0, k=0, nperm=0, seed=0, pairs=None, with_ll=False, raw=False):
+        self.pairs = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        flags = (MUTINFO_WITH_LL if with_ll else 0) | (MUTINFO_RAW if raw else 0)
+        self.c = MutinfoSpecC(n, k, nperm, seed, flags, 0 if self.pairs is None else len(self.pairs),
+                              None if self.pairs is None else self.pairs.ctypes.data_as(C.POINTER(C.c_int)))
+        self.with_ll = bool(with_ll)
+
+    def npairs(self, ncol):
+        """how many pairs the call answers with (what the library refuses is sized for generously)"""
+        if self.pairs is not None:
+            return max(len(self.pairs), 1)
+        u = max(int(ncol) - (0 if self.with_ll else 1), 2)
+        return u * (u - 1) // 2
+
+
+def _mutinfo_call(fn, ncol, **kw):
+    """fn(spec, res, cols, pairs, perm_mi) of one of the three entry points -> the dict of mcx_mutinfo_result's fields (n_rows,
+    n_sel, ndup, m, k, npairs, nperm, nused), scale and flags [ncol] per column, pairs (MUTINFO_PAIR_DTYPE [npairs]: a, b, mi,
+    r_info, pearson, perm_mean, perm_sd, p_value, nge, nzero, flags) and perm_mi [npairs, nperm]"""
+    spec, res = _MutinfoSpec(**kw), MutinfoResultC()
+    cols = np.zeros(max(int(ncol), 1), MUTINFO_COL_DTYPE)
+    room = spec.npairs(ncol)
+    pairs = np.zeros(room, MUTINFO_PAIR_DTYPE)
+    perm_mi = np.zeros((room, max(int(spec.c.nperm), 0)))
+    check(fn(C.byref(spec.c), C.byref(res), cols.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p),
+             _dp(perm_mi) if perm_mi.size else None))
+    out = {name: getattr(res, name) for name, _ in MutinfoResultC._fields_}
+    out.update(scale=cols["scale"].copy(), flags=cols["flags"].copy(), pairs=pairs[:res.npairs], perm_mi=perm_mi[:res.npairs])
+    return out
+
+
+def rows_mutual_info(rows, nsteps, nc, **kw):
+    """mcx_rows_mutinfo: which columns of rows [nsteps * nc, np + 1] (MCout layout) depend on each other at all -- the mutual
+    information of every pair of parameters (pairs: [(a, b), ...] names them; with_ll: log L too) in nats by the k-nearest-neighbour
+    estimator (k, default 3) on n rows evenly spaced in store order (0: min(rows, 4096), -1: all) scaled by their sd (raw:
+    unscaled), repeated rows dropped (ndup), with nperm permutations of the second column as the null: mi, r_info (on the scale of
+    a correlation), pearson, p_value = (1 + nge) / (1 + nperm)"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    return _mutinfo_call(lambda *a: load().mcx_rows_mutinfo(_fp(rows), nsteps, nc, rows.shape[1] - 1, *a), rows.shape[1], **kw)
+
+
+def debug_mutinfo_rows(N, n):
+    """mcx_debug_mutinfo_rows (host only): the n rows floor(i N / n) taken of N"""
+    index = np.zeros(max(int(n), 1), np.int64)
+    check(load().mcx_debug_mutinfo_rows(N, n, index.ctypes.data_as(C.POINTER(C.c_longlong))))
+    return index
+
+
+def debug_mutinfo_perm(seed, m, p):
+    """mcx_debug_mutinfo_perm (host only): pi_p on [0, m)"""
+    perm = np.zeros(max(int(m), 1), np.int32)
+    check(load().mcx_debug_mutinfo_perm(seed, m, p, perm.ctypes.data_as(C.POINTER(C.c_int))))
+    return perm
+
+
+def debug_mutinfo_psi(q_max):
+    """mcx_debug_mutinfo_psi (host only): table[q - 1] = psi(q), q = 1 ... q_max"""
+    table = np.zeros(max(int(q_max), 1))
+    check(load().mcx_debug_mutinfo_psi(q_max, _dp(table)))
+    return table
+
+
+def mutinfo_finish(eps, na, nb, k):
+    """mcx_mutinfo_finish (host only): eps, na, nb [m] of one pair -> (mi, nzero)"""
+    eps = np.ascontiguousarray(eps, np.float64)
+    na, nb = np.ascontiguousarray(na, np.int32), np.ascontiguousarray(nb, np.int32)
+    mi, nzero = C.c_double(0.0), C.c_longlong(0)
+    check(load().mcx_mutinfo_finish(_dp(eps), na.ctypes.data_as(C.POINTER(C.c_int)), nb.ctypes.data_as(C.POINTER(C.c_int)), len(eps), k,
+                                    C.byref(mi), C.byref(nzero)))
+    return mi.value, nzero.value
+
+
+def debug_mutinfo_points(rows, nsteps, nc, **kw):
+    """mcx_debug_mutinfo_points (host only): the host half on host rows -- mcx_mutinfo_result's fields, index and kept [n_sel],
+    scale and flags [ncol], z [ncol, m]"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    ncol = rows.shape[1]
+    spec, res = _MutinfoSpec(**kw), MutinfoResultC()
+    N = int(nsteps) * int(nc)
+    room = max(spec.c.n if spec.c.n > 0 else min(N, 4096) if spec.c.n == 0 else N, 1)
+    index, kept = np.zeros(room, np.int64), np.zeros(room, np.uint8)
+    cols, z = np.zeros(ncol, MUTINFO_COL_DTYPE), np.zeros(ncol * room)
+    check(load().mcx_debug_mutinfo_points(_fp(rows), nsteps, nc, ncol - 1, C.byref(spec.c), C.byref(res),
+                                          index.ctypes.data_as(C.POINTER(C.c_longlong)), kept.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                          cols.ctypes.data_as(C.c_void_p), _dp(z)))
+    out = {name: getattr(res, name) for name, _ in MutinfoResultC._fields_}
+    out.update(index=index[:res.n_sel], kept=kept[:res.n_sel], scale=cols["scale"].copy(), flags=cols["flags"].copy(),
+               z=z[:ncol * res.m].reshape(ncol, res.m).copy())
+    return out
+
+
+def debug_mutinfo_geometry(m, npairs, nperm, k):
+    """mcx_debug_mutinfo_geometry (host only): the launch geometry as a dict of include/mcx.h's fields"""
+    g = MutinfoGeometry()
+    check(load().mcx_debug_mutinfo_geometry(m, npairs, nperm, k, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in MutinfoGeometry._fields_}
+
+
+def debug_mutinfo_counts(rows, nsteps, nc, pair, p, **kw):
+    """mcx_debug_mutinfo_counts: (eps, na, nb) [m] of pair `pair` of the call's list under permutation p, from k_mi_pairs itself"""
+    rows = np.ascontiguousarray(rows, np.float32)
+    m = debug_mutinfo_points(rows, nsteps, nc, **kw)["m"]
+    spec = _MutinfoSpec(**kw)
+    eps, na, nb = np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.int32)
+    check(load().mcx_debug_mutinfo_counts(_fp(rows), nsteps, nc, rows.shape[1] - 1, C.byref(spec.c), pair, p, _dp(eps),
+                                          na.ctypes.data_as(C.POINTER(C.c_int)), nb.ctypes.data_as(C.POINTER(C.c_int))))
+    return eps, na, nb
 
 
 # ---- importance weights on a store (include/mcx.h, DESIGN.md section 22) ----
@@ -2311,6 +2438,19 @@ class Engine:
         uploads, k_energy_pairs, the reducer, the whole call (host clock)"""
         spec, ms = _energy_spec(**kw), np.zeros(7)
         check(load().mcx_debug_energy_times(self.h, first_a, nsteps_a, first_b, nsteps_b, C.byref(spec), _dp(ms)))
+        return ms
+
+    def mutual_info(self, first_step=0, nsteps=None, **kw):
+        """mcx_samples_mutinfo: rows_mutual_info's dict for kept steps [first_step, first_step + nsteps) (nsteps None: to the end)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        return _mutinfo_call(lambda *a: load().mcx_samples_mutinfo(self.h, first_step, nsteps, *a), self.np + 1, **kw)
+
+    def mutual_info_times(self, first_step=0, nsteps=None, **kw):
+        """mcx_debug_mutinfo_times: ms[8] of one mutual_info() call -- the gather, the points (host), the permutations and the
+        table (host), the uploads, k_mi_pairs, the reducer, pearson and the null (host), the whole call (host clock)"""
+        nsteps = self._nsteps(first_step, nsteps)
+        spec, ms = _MutinfoSpec(**kw), np.zeros(8)
+        check(load().mcx_debug_mutinfo_times(self.h, first_step, nsteps, C.byref(spec.c), _dp(ms)))
         return ms
 
     def reweight(self, weights, probs=(0.05, 0.5, 0.95), first_step=0, nsteps=None):
