@@ -1017,8 +1017,14 @@ typedef struct mcx_compare_geometry {
   long long lds_bytes;               /* of a sweep workgroup */
   long long group_cols;              /* columns sorted and swept at a time before any halving for memory (MCX_COMPARE_GROUP_COLS caps it) */
   long long scratch_bytes_per_col;   /* per-call scratch of one column of a group */
+  long long sort_tiles_a, sort_tiles_b;               /* sort tiles per column of each side: above 256 the scans of the sort carry */
+  long long bounds_workgroups_a, bounds_workgroups_b; /* grid.x of k_cmp_bounds, a lane per tile: ceil(tiles / block) */
+  long long step_chunk_a, step_chunk_b;               /* steps per workgroup of k_cmp_keys: max(64, ceil(nsteps / 32768)) */
+  long long grid_y_a, grid_y_b;                       /* and its grid.y; these four are 0 from the entry that is given na and nb alone */
 } mcx_compare_geometry;
 int mcx_debug_compare_geometry(long long na, long long nb, int ncol, mcx_compare_geometry *g);
+/* the same for na = nsteps_a * nc_a against nb = nsteps_b * nc_b values, with the step chunks of the key sweeps */
+int mcx_debug_compare_store_geometry(int nsteps_a, int nc_a, int nsteps_b, int nc_b, int ncol, mcx_compare_geometry *g);
 /* one mcx_samples_compare call, its results let go, ms[10] by HIP events: 0 the two sides' summaries, 1 A's keys, 2 A's sort,
  * 3 B's keys, 4 B's sort, 5 the bounds, 6 the sweep with self = A, 7 with self = B, 8 the reducer, 9 the whole call */
 int mcx_debug_compare_times(mcx_engine *e, int first_a, int nsteps_a, int first_b, int nsteps_b, const mcx_compare_spec *spec,
@@ -1213,8 +1219,12 @@ typedef struct mcx_reweight_geometry {
   long long tail_m, sort_tiles;
   long long draw_workgroups;
   long long scratch_bytes; /* of a reweight call, or of a resample call when K > 0 */
+  long long scan_tiles_per_lane; /* consecutive scan tiles a lane of k_rw_scan owns: ceil(scan_tiles / block) */
+  long long hist_step_chunks;    /* grid.y of the histogram passes, ceil(nsteps / 65536); 0 from the entry that is given N alone */
 } mcx_reweight_geometry;
 int mcx_debug_reweight_geometry(long long N, int ncol, int nprobs, long long K, mcx_reweight_geometry *g);
+/* the same for N = nsteps * nc rows, with hist_step_chunks, which depends on how N splits into steps and chains */
+int mcx_debug_reweight_store_geometry(int nsteps, int nc, int ncol, int nprobs, long long K, mcx_reweight_geometry *g);
 /* one mcx_samples_reweight call and, when nsteps_out * nc_out > 0, one mcx_samples_resample call, their results let go.  ms[8],
  * HIP events: 0 k_rw_max and its reducer, 1 k_rw_q and the scan, 2 the two moment passes, 3 the four histogram passes, 4 the
  * sort of q, 5 k_rw_draw, 6 the whole reweight call, 7 the whole resample call */
@@ -1373,6 +1383,8 @@ typedef struct mcx_lagcov_geometry {
   long long launches;           /* sweeps in all: 1 + windows */
   long long lags_computed;      /* min(nsteps, 1 + windows W) */
   long long scratch_bytes;
+  long long units_lag0;         /* the lag-0 sweep alone takes larger units: ceil(N / (4 rows_per_iteration)) */
+  long long workgroups_lag0;    /* and its grid.x = min(units_lag0, 4 max(32, 512 / tiles^2)) */
 } mcx_lagcov_geometry;
 int mcx_debug_lagcov_geometry(int nsteps, int nc, int np, int nlags, mcx_lagcov_geometry *g);
 /* mcx_samples_lagcov with HIP events around its stages, for tools/lagcov_bench.py (sigma, the columns and gamma are dropped).
@@ -1722,6 +1734,8 @@ typedef struct mcx_profile_geometry {
   long long unroll;               /* steps whose loads are issued together */
   long long pair_block, pair_chunk_rows, pair_chunks, pair_workgroups, pair_lds_bytes; /* k_profile_pairs: 12 g^2 bytes */
   long long scratch_bytes;        /* of a profile call without a path, behind the statistics' */
+  long long keys_workgroups;      /* k_profile_keys: min(ceil(N / block), keys_max_workgroups), a lane per row or a grid stride */
+  long long keys_max_workgroups;  /* 4096 */
 } mcx_profile_geometry;
 int mcx_debug_profile_geometry(int np, int nsteps, int nc, int n, int g, int npairs, mcx_profile_geometry *geom);
 /* one call with its results let go, for tools/profile_bench.py.  Profile: ms[0] the statistics passes (wall clock), ms[1]

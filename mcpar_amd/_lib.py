@@ -101,7 +101,9 @@ class CompareSpecC(C.Structure):
 class CompareGeometry(C.Structure):
     """include/mcx.h mcx_compare_geometry"""
     _fields_ = [(n, C.c_longlong) for n in ("block", "tile_keys", "tiles_a", "tiles_b", "window_lds_keys", "lds_bytes",
-                                            "group_cols", "scratch_bytes_per_col")]
+                                            "group_cols", "scratch_bytes_per_col", "sort_tiles_a", "sort_tiles_b",
+                                            "bounds_workgroups_a", "bounds_workgroups_b", "step_chunk_a", "step_chunk_b",
+                                            "grid_y_a", "grid_y_b")]
 
 
 class EnergySpecC(C.Structure):
@@ -154,7 +156,7 @@ class ReweightGeometry(C.Structure):
     """include/mcx.h mcx_reweight_geometry"""
     _fields_ = [(n, C.c_longlong) for n in ("block", "scan_tile_rows", "scan_tiles", "hist_targets", "hist_prefixes", "hist_launches",
                                             "hist_tile_cols", "hist_lds_bytes", "hist_lds_budget", "tail_m", "sort_tiles",
-                                            "draw_workgroups", "scratch_bytes")]
+                                            "draw_workgroups", "scratch_bytes", "scan_tiles_per_lane", "hist_step_chunks")]
 
 
 class IntervalSpecC(C.Structure):
@@ -183,7 +185,8 @@ class LagcovResultC(C.Structure):
 class LagcovGeometry(C.Structure):
     """include/mcx.h mcx_lagcov_geometry"""
     _fields_ = [(n, C.c_longlong) for n in ("block", "window_lags", "rows_per_iteration", "units", "workgroups", "tiles",
-                                            "pairs_lag0", "pairs", "slab_rows", "windows", "launches", "lags_computed", "scratch_bytes")]
+                                            "pairs_lag0", "pairs", "slab_rows", "windows", "launches", "lags_computed", "scratch_bytes",
+                                            "units_lag0", "workgroups_lag0")]
 
 
 class Counters(C.Structure):
@@ -265,7 +268,8 @@ class ProfileGeometry(C.Structure):
     """include/mcx.h mcx_profile_geometry"""
     _fields_ = [(n, C.c_longlong) for n in ("block", "tile_columns", "chains_per_workgroup", "column_tiles", "chain_blocks", "chunk_steps",
                                             "chunks", "workgroups", "lds_bytes", "unroll", "pair_block", "pair_chunk_rows", "pair_chunks",
-                                            "pair_workgroups", "pair_lds_bytes", "scratch_bytes")]
+                                            "pair_workgroups", "pair_lds_bytes", "scratch_bytes", "keys_workgroups",
+                                            "keys_max_workgroups")]
 
 
 class Profile(C.Structure):
@@ -409,6 +413,7 @@ def load():
         "mcx_samples_compare_store": [vp, C.c_int, C.c_int, vp, C.POINTER(CompareSpecC), vp],
         "mcx_ks_prob": [C.c_double, C.c_double, C.c_double, dp, dp],
         "mcx_debug_compare_geometry": [C.c_longlong, C.c_longlong, C.c_int, C.POINTER(CompareGeometry)],
+        "mcx_debug_compare_store_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CompareGeometry)],
         "mcx_debug_compare_times": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CompareSpecC), dp],
         "mcx_store_energy": [vp, vp, C.POINTER(EnergySpecC), C.POINTER(EnergyResultC), vp, dp],
         "mcx_rows_energy": [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.POINTER(EnergySpecC), C.POINTER(EnergyResultC), vp, dp],
@@ -429,6 +434,7 @@ def load():
         "mcx_khat_of_tail": [dp, C.c_longlong, dp, dp, C.POINTER(C.c_int)],
         "mcx_debug_reweight_q": [vp, fp, C.c_int, C.c_int, C.c_int, C.POINTER(WeightsC), u32p, dp],
         "mcx_debug_reweight_geometry": [C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.POINTER(ReweightGeometry)],
+        "mcx_debug_reweight_store_geometry": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(ReweightGeometry)],
         "mcx_debug_reweight_times": [vp, C.c_int, C.c_int, C.POINTER(WeightsC), dp, C.c_int, C.c_uint32, C.c_int, C.c_int, dp],
         "mcx_samples_intervals": [vp, C.c_int, C.c_int, C.POINTER(IntervalSpecC), vp, vp, vp],
         "mcx_rows_intervals": [fp, C.c_int, C.c_int, C.c_int, C.POINTER(IntervalSpecC), vp, vp, vp],

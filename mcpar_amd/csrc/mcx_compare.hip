@@ -237,7 +237,8 @@ __global__ void __launch_bounds__(SB) k_cmp_reduce(const CmpReduceArgs a)
 
 // ---- launch geometry: what the launches below use and mcx_debug_compare_geometry reports
 struct CompareGeometry {
-  uint32_t tiles_a, tiles_b;
+  uint32_t tiles_a, tiles_b;    // sort and sweep tiles per column of each side
+  uint32_t bounds_a, bounds_b;  // k_cmp_bounds' grid.x: a lane per tile
   int G;  // columns at a time, before any halving for memory
   size_t col_bytes;
 };
@@ -249,6 +250,8 @@ CompareGeometry compare_geometry(int64_t na, int64_t nb, int ncol)
   g.G = ncol;
   if (const char *cap = std::getenv("MCX_COMPARE_GROUP_COLS")) g.G = std::max(1, std::min(ncol, std::atoi(cap)));
   const size_t nmax = (size_t)std::max(na, nb), tmax = std::max(g.tiles_a, g.tiles_b), ts = (size_t)g.tiles_a + g.tiles_b;
+  g.bounds_a = (g.tiles_a + SB - 1) / SB;
+  g.bounds_b = (g.tiles_b + SB - 1) / SB;
   g.col_bytes = 4 * ((size_t)na + (size_t)nb + nmax) + 4 * 256 * (tmax + 1) + 4 * (ts + 2) + (8 + 4 + 8) * ts + (16 + 16 + 8);
   return g;
 }
@@ -365,10 +368,10 @@ int compare_device(hipStream_t st, Bufs B, const StoreView &va, const StoreView 
       MCXCHK(sort_columns(st, S.kb.p, S.alt.p, S.hist.p, S.rowsum.p, nb, k, g.tiles_b,
                           [&](int, auto f) -> int { return tm.run(CT_SORT_B, f); }));
       MCXCHK(tm.run(CT_BOUNDS, [&]() -> int {
-        hipLaunchKernelGGL(k_cmp_bounds, dim3((g.tiles_a + SB - 1) / SB, k), dim3(SB), 0, st, (const uint32_t *)S.ka.p, na, g.tiles_a,
+        hipLaunchKernelGGL(k_cmp_bounds, dim3(g.bounds_a, k), dim3(SB), 0, st, (const uint32_t *)S.ka.p, na, g.tiles_a,
                            (const uint32_t *)S.kb.p, nb, S.oba.p);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_cmp_bounds, dim3((g.tiles_b + SB - 1) / SB, k), dim3(SB), 0, st, (const uint32_t *)S.kb.p, nb, g.tiles_b,
+        hipLaunchKernelGGL(k_cmp_bounds, dim3(g.bounds_b, k), dim3(SB), 0, st, (const uint32_t *)S.kb.p, nb, g.tiles_b,
                            (const uint32_t *)S.ka.p, na, S.obb.p);
         HIPCHK(hipGetLastError());
         return MCX_OK;
@@ -553,5 +556,23 @@ extern "C" int mcx_debug_compare_geometry(long long na, long long nb, int ncol, 
   g->lds_bytes = (long long)((WIN_LDS + WIN_PAD + RKPT + 1) * sizeof(uint32_t) + SB * (2 * sizeof(long long) + sizeof(double)));
   g->group_cols = c.G;
   g->scratch_bytes_per_col = (long long)c.col_bytes;
+  g->sort_tiles_a = c.tiles_a;
+  g->sort_tiles_b = c.tiles_b;
+  g->bounds_workgroups_a = c.bounds_a;
+  g->bounds_workgroups_b = c.bounds_b;
+  g->step_chunk_a = g->step_chunk_b = g->grid_y_a = g->grid_y_b = 0;
+  return MCX_OK;
+}
+
+extern "C" int mcx_debug_compare_store_geometry(int nsteps_a, int nc_a, int nsteps_b, int nc_b, int ncol, mcx_compare_geometry *g)
+{
+  if (nsteps_a < 1 || nc_a < 1 || nsteps_b < 1 || nc_b < 1)
+    return fail(MCX_ERR_INVALID, "compare: %d steps of %d chains and %d of %d, at least one each", nsteps_a, nc_a, nsteps_b, nc_b);
+  MCXCHK(mcx_debug_compare_geometry((long long)nsteps_a * nc_a, (long long)nsteps_b * nc_b, ncol, g));
+  const RankGeometry ra = rank_geometry(nsteps_a, (int64_t)nsteps_a * nc_a), rb = rank_geometry(nsteps_b, (int64_t)nsteps_b * nc_b);
+  g->step_chunk_a = ra.rchunk;
+  g->step_chunk_b = rb.rchunk;
+  g->grid_y_a = ra.chunks;
+  g->grid_y_b = rb.chunks;
   return MCX_OK;
 }

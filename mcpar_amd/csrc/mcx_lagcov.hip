@@ -65,6 +65,15 @@ inline LagGeometry lag_geometry(size_t N, int np)
   return g;
 }
 
+// a sweep's units of lag_rows(W) rows and its workgroups over them: lg's when W = LW; fewer, larger units for lag 0 alone, a light
+// kernel with eight workgroups a compute unit resident and no partners to keep in the caches.  Its slab fits the window's
+// (units <= lg.units, 4 lg.cap <= LW lg.cap)
+inline size_t lag_sweep_units(size_t N, int W) { return (N + lag_rows(W) - 1) / lag_rows(W); }
+inline size_t lag_sweep_workgroups(const LagGeometry &lg, size_t N, int W)
+{
+  return W == 1 ? std::min(lag_sweep_units(N, 1), 4 * lg.cap) : lg.nwg;
+}
+
 // lags t0 .. min(t0 + W - 1, tmax) of the units (of lag_rows(W) rows) blockIdx.x, blockIdx.x + nwg, ...: slab w of part is lag
 // t0 + w
 template <bool DIAG, int W>
@@ -226,10 +235,7 @@ int lag_sweep(hipStream_t st, StageTimer &tm, const StoreView &v, const LagGeome
 {
   const int np = v.np, nt = lg.nt, noff = t0 == 0 ? lg.nu : 2 * lg.nu, tmax = t0 + nl - 1;
   const size_t N = (size_t)v.N, rows = t0 == 0 ? lg.R0 : (size_t)nl * lg.R, nn = (size_t)v.ncol * v.ncol;
-  const size_t units = (N + lag_rows(W) - 1) / lag_rows(W);  // (lg.units when W = LW; fewer, larger ones for lag 0 alone)
-  // lag 0 alone: a light kernel, eight workgroups a compute unit resident, and no partners to keep in the caches; its slab fits
-  // the window's (units <= lg.units, 4 lg.cap <= LW lg.cap)
-  const size_t nwg = W == 1 ? std::min(units, 4 * lg.cap) : lg.nwg;
+  const size_t units = lag_sweep_units(N, W), nwg = lag_sweep_workgroups(lg, N, W);
   MCXCHK(tm.run(t0 == 0 ? LT_LAG0 : LT_WINDOWS, [&]() -> int {
     hipLaunchKernelGGL((k_lagcov<true, W>), dim3((unsigned)nwg, (unsigned)nt), dim3(SB), 0, st, v.x, v.ly, np, nt, v.nc, N, units, t0,
                        tmax, ctr, part, nwg, lg.R);
@@ -461,5 +467,7 @@ extern "C" int mcx_debug_lagcov_geometry(int nsteps, int nc, int np, int nlags, 
   g->launches = 1 + g->windows;
   g->lags_computed = std::min<long long>(nsteps, 1 + g->windows * LW);
   g->scratch_bytes = 8 * ((long long)(np + 1) * (3LL * nc + 2) + (long long)LW * (long long)lg.R * (long long)(lg.nwg + 1));
+  g->units_lag0 = (long long)lag_sweep_units(N, 1);
+  g->workgroups_lag0 = (long long)lag_sweep_workgroups(lg, N, 1);
   return MCX_OK;
 }

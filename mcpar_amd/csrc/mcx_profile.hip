@@ -294,6 +294,9 @@ BinsGeometry bins_geometry(const TileSet &tx, int nc, int64_t T)
   b.chunks = (unsigned)((T + b.chunk - 1) / b.chunk);
   return b;
 }
+// k_profile_keys: a lane per row up to KEYS_MAX_WGS workgroups, a grid stride beyond
+constexpr int64_t KEYS_MAX_WGS = 4096;
+inline unsigned keys_workgroups(int64_t N) { return (unsigned)std::min<int64_t>((N + SB - 1) / SB, KEYS_MAX_WGS); }
 struct PairGeometry {
   int64_t nchunks;
   int W;
@@ -539,7 +542,7 @@ int pairs_device(hipStream_t st, Bufs B, const StoreView &v, int g, const std::v
                          npad, g, tc, (const double *)B.d->p, cmap, code);
       HIPCHK(hipGetLastError());
     }
-    const unsigned nb = (unsigned)std::min<int64_t>((v.N + SB - 1) / SB, 4096);
+    const unsigned nb = keys_workgroups(v.N);
     hipLaunchKernelGGL(k_profile_keys, dim3(nb), dim3(SB), 0, st, v.ly, v.N, rowkey, dhat);
     HIPCHK(hipGetLastError());
     return MCX_OK;
@@ -902,5 +905,7 @@ extern "C" int mcx_debug_profile_geometry(int np, int nsteps, int nc, int n, int
   o->pair_workgroups = (long long)npairs * p.W;
   o->pair_lds_bytes = (long long)pair_lds_bytes(g);
   o->scratch_bytes = (long long)((size_t)np * 3 * 8 + (2 * (size_t)np * n + 1) * 8 + ((size_t)np * n + np) * 4);
+  o->keys_workgroups = keys_workgroups(N);
+  o->keys_max_workgroups = KEYS_MAX_WGS;
   return MCX_OK;
 }

@@ -150,6 +150,9 @@ __global__ void __launch_bounds__(SB) k_rw_q(WSrc w, int64_t N, const double *lw
   }
 }
 
+// the consecutive scan tiles a lane of k_rw_scan owns (the last lanes own fewer, or none)
+__host__ __device__ inline uint32_t scan_tiles_per_lane(uint32_t ntile) { return (ntile + SB - 1) / SB; }
+
 // one workgroup: toff[0 .. ntile) the tile sums -> their exclusive scan in place, toff[ntile] = Q; out[4] = Q, the sum of q^2
 // (lo, hi), the rows with q = 0.  A lane owns ceil(ntile / SB) consecutive tiles
 __global__ void __launch_bounds__(SB) k_rw_scan(unsigned long long *toff, uint32_t ntile, const unsigned long long *sqlo,
@@ -157,7 +160,7 @@ __global__ void __launch_bounds__(SB) k_rw_scan(unsigned long long *toff, uint32
 {
   __shared__ unsigned long long r0[SB], r1[SB], r2[SB], r3[SB];
   const int tid = (int)threadIdx.x;
-  const uint32_t per = (ntile + SB - 1) / SB;
+  const uint32_t per = scan_tiles_per_lane(ntile);
   const uint32_t t0 = min(ntile, (uint32_t)tid * per), t1 = min(ntile, t0 + per);
   unsigned long long s = 0, lo = 0, hi = 0, z = 0;
   for (uint32_t t = t0; t < t1; ++t) {
@@ -353,6 +356,7 @@ __global__ void __launch_bounds__(SB) k_rw_draw(const DrawArgs a)
 inline uint32_t scan_tiles(int64_t N) { return (uint32_t)((N + RS - 1) / RS); }
 inline uint32_t sort_tiles(int64_t N) { return (uint32_t)((N + RTILE - 1) / RTILE); }
 inline unsigned draw_workgroups(int64_t K) { return (unsigned)((K + SB - 1) / SB); }
+inline unsigned hist_step_chunks(int64_t T) { return (unsigned)((T + RW_HIST_CHUNK - 1) / RW_HIST_CHUNK); }  // k_rw_hist's grid.y
 // a tile set for a histogram launch of gn prefixes per column: narrower parameter tiles keep the 64-bit bins within the budget
 TileSet rw_hist_tiles(TileSet t, int gn, int nc)
 {
@@ -531,7 +535,7 @@ int select_passes(hipStream_t st, Bufs B, const StoreView &v, const RwScratch &S
   std::vector<uint32_t> gp;
   std::vector<int> gc((size_t)ncol);
   std::vector<unsigned long long> hh;
-  const unsigned chunks = (unsigned)((v.T + RW_HIST_CHUNK - 1) / RW_HIST_CHUNK);
+  const unsigned chunks = hist_step_chunks(v.T);
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 32 - 8 * pass;
     int G = 1;  // the longest list of distinct prefixes
@@ -871,6 +875,16 @@ extern "C" int mcx_debug_reweight_geometry(long long N, int ncol, int nprobs, lo
   if (K > 0) b += 8 * (size_t)K;
   else if (M >= 5) b += 4 * (size_t)N + 4 * 256 * ((size_t)sort_tiles(N) + 1);
   g->scratch_bytes = (long long)b;
+  g->scan_tiles_per_lane = scan_tiles_per_lane(ntile);
+  g->hist_step_chunks = 0;
+  return MCX_OK;
+}
+
+extern "C" int mcx_debug_reweight_store_geometry(int nsteps, int nc, int ncol, int nprobs, long long K, mcx_reweight_geometry *g)
+{
+  MCXCHK(shape_args(nsteps, nc));
+  MCXCHK(mcx_debug_reweight_geometry((long long)nsteps * nc, ncol, nprobs, K, g));
+  g->hist_step_chunks = hist_step_chunks(nsteps);
   return MCX_OK;
 }
 

@@ -1049,6 +1049,14 @@ def debug_compare_geometry(na, nb, ncol):
     return {name: int(getattr(g, name)) for name, _ in CompareGeometry._fields_}
 
 
+def debug_compare_store_geometry(nsteps_a, nc_a, nsteps_b, nc_b, ncol):
+    """mcx_debug_compare_store_geometry (host only): debug_compare_geometry of nsteps_a * nc_a against nsteps_b * nc_b values,
+    with the step chunks of the key sweeps, which depend on the steps"""
+    g = CompareGeometry()
+    check(load().mcx_debug_compare_store_geometry(nsteps_a, nc_a, nsteps_b, nc_b, ncol, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in CompareGeometry._fields_}
+
+
 # ---- two stores compared jointly (include/mcx.h, DESIGN.md section 21) ----
 def _energy_spec(n_a=0, n_b=0, nperm=999, seed=0, with_ll=False, raw=False):
     return EnergySpecC(n_a, n_b, nperm, seed, (ENERGY_WITH_LL if with_ll else 0) | (ENERGY_RAW if raw else 0))
@@ -1854,6 +1862,14 @@ def debug_reweight_geometry(N, ncol, nprobs=3, K=0):
     probabilities and of a resample of K draws, as a dict of include/mcx.h's fields"""
     g = ReweightGeometry()
     check(load().mcx_debug_reweight_geometry(N, ncol, nprobs, K, C.byref(g)))
+    return {name: int(getattr(g, name)) for name, _ in ReweightGeometry._fields_}
+
+
+def debug_reweight_store_geometry(nsteps, nc, ncol, nprobs=3, K=0):
+    """mcx_debug_reweight_store_geometry (host only): debug_reweight_geometry of nsteps * nc rows, with hist_step_chunks, which
+    depends on the steps"""
+    g = ReweightGeometry()
+    check(load().mcx_debug_reweight_store_geometry(nsteps, nc, ncol, nprobs, K, C.byref(g)))
     return {name: int(getattr(g, name)) for name, _ in ReweightGeometry._fields_}
 
 

@@ -107,14 +107,29 @@ def key_float(k):
     return u.view(np.float32)
 
 
+def integer_sums_slow(q):
+    """(sum q, sum q^2, the count of q = 0) in Python integers, one row at a time: the definition"""
+    qi = [int(v) for v in q]
+    return sum(qi), sum(v * v for v in qi), sum(1 for v in qi if v == 0)
+
+
+def integer_sums(q):
+    """integer_sums_slow without the loop, for N < 2^31 values below 2^32: q = a 2^16 + b, and the three sums of a^2, a b and b^2
+    (each below 2^63) are exact in int64; tests/test_reweight_cpu.py pins the two to each other"""
+    q = np.asarray(q, np.uint32).astype(np.int64)
+    assert q.size < 2 ** 31
+    a, b = q >> 16, q & 0xffff
+    Q2 = (int(np.sum(a * a)) << 32) + (int(np.sum(a * b)) << 17) + int(np.sum(b * b))
+    return int(np.sum(q)), Q2, int(np.count_nonzero(q == 0))
+
+
 def restate(rows, q, lwmax, probs):
     """the result of mcx_*_reweight for rows [N, ncol] float32 and fixed-point weights q: a dict with Python integers for the
     sums, floats for the rest, and per column arrays"""
     rows = np.ascontiguousarray(rows, np.float32)
     N, ncol = rows.shape
-    qi = [int(v) for v in q]
-    Q, Q2 = sum(qi), sum(v * v for v in qi)
-    out = dict(n=N, nzero=sum(1 for v in qi if v == 0), lwmax=lwmax, sumq=Q, sumq2=Q2, sumq2_hi=Q2 >> 64, sumq2_lo=Q2 & (2 ** 64 - 1))
+    Q, Q2, nzero = integer_sums(q)
+    out = dict(n=N, nzero=nzero, lwmax=lwmax, sumq=Q, sumq2=Q2, sumq2_hi=Q2 >> 64, sumq2_lo=Q2 & (2 ** 64 - 1))
     out["ess_kish"] = float(Q * Q / Q2) if Q2 < 2 ** 1000 else math.nan  # (integer true division: correctly rounded)
     out["log_mean_w"] = lwmax + math.log(float(Q) / (float(TWO31) * float(N)))
     M = tail_length(N)

@@ -212,3 +212,19 @@ def test_host_code_under_sanitizers(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, timeout=60)
     assert r.returncode == 0, r.stdout.decode() + r.stderr.decode()
     assert b"compare_host_check ok" in r.stdout
+
+
+def test_distances_without_loops_are_distances():
+    """compare_ref.distances_numpy (the reference of the GPU case of millions of values) against distances(): every field the same
+    bits, on ties, shared values, non-finite values and signed zeros"""
+    for seed in range(5):
+        a, b = K.tie_rows(3, 5, 37, seed), K.tie_rows(3, 9, 11, seed + 10, shift=0.25 * (seed % 3))
+        if seed == 3:
+            a[3, 1], b[5, 1], a[7, 2], b[0, 0], a[1, 0] = np.nan, np.inf, -np.inf, -0.0, 0.0
+        for c in range(a.shape[1]):
+            want, got = R.distances(a[:, c], b[:, c]), R.distances_numpy(a[:, c], b[:, c])
+            assert sorted(want) == sorted(got)
+            for k in want:
+                assert want[k] == got[k] or (math.isnan(want[k]) and math.isnan(got[k])), (seed, c, k, want[k], got[k])
+    one = np.array([1.5], np.float32)
+    assert R.distances(one, one) == R.distances_numpy(one, one)

@@ -11,7 +11,18 @@ maximum, so its window is every key of B up to that value; were that at most 819
 and 8192 of B -- would lie above A's maximum, and the window of B's first tile would be all 8193 keys of A.  So the variants
 cross the switch between them: "overlap" (one range, one run value: the first tile of either side spans more than 8192 keys of
 the other, the global path), "above" (every tile of A in LDS, B's first tile global), and a third, "inside", with B cut to 8000
-values that all lie inside the window of A's first tile: every window of both sweeps in LDS."""
+values that all lie inside the window of A's first tile: every window of both sweeps in LDS.
+
+The BIG pair (2 105 349 x 1 against 100 001 x 3) crosses what the others do not reach: side A alone has more than 256 sort tiles
+(the second carry step of the sort's scans, with another stride than B's), a second workgroup of k_cmp_bounds, lanes of
+k_cmp_reduce that take two tiles and a step chunk of 65.  Its reference is compare_ref.distances_numpy (no Python loop; pinned
+to distances() in tests/test_compare_cpu.py) held by compare_ref.check with its rel_w1; mean, sd and ess of a side are the bytes
+of rows_summary of that side.  Both columns are built from their pooled order, so that the maxima of D+ lie where the case wants them.
+Equal values of D+ at two points need the same remainder of cA NB modulo NA: with gcd(NA, NB) = 3 they lie a multiple of
+NA / 3 = 701 783 keys of A (85.7 tiles) apart, so with these sizes no two tiles of one reducer lane (256 tiles apart) can tie.
+Column 0 therefore has its three equal maxima in tiles 0, 86 and 171 (three lanes; the lowest position wins), and the lane
+that takes two tiles is crossed by column 1, whose only maximum lies in tile 257, behind a lower one in tile 1.  One case holds
+both, since a summary of one chain of two million steps costs the library a second, whatever the columns."""
 import numpy as np
 import pytest
 
@@ -247,3 +258,95 @@ def test_a_statement_with_content():
     same = rows_case(a, c["T"], c["nc"], b, c["T"], c["nc"], what="iid normal stores")
     scaled = rows_case(a, c["T"], c["nc"], b15, c["T"], c["nc"], what="column 0 of B times 1.5")
     K.check_content(same, scaled)
+
+
+# ---- 9. a side beyond 256 tiles ----------------------------------------------------------------------------------------------------
+BIG_A, BIG_B = (2105349, 1), (100001, 3)  # (T, nc)
+BIG_THIRD = (701783, 100001)                # NA / 3, NB / 3: coprime
+BIG_VARIANTS = ("tie", "tile 257")          # column 0, column 1 (log L)
+
+
+def planted_columns(variant, rng):
+    """a column of A and one of B, given by their pooled order, position k holding the value (k - 1 200 000) / 1024 (exact in
+    float32), each in a shuffle of its own: in every third of A, B runs ahead of A's share (D+ <= 0, and 0 at the end of a third)
+    except where values of B are held back: "tie": two of them in every third until A's local key 4000 is past, three equal
+    maxima in tiles 0, 86 and 171; "tile 257": one of them until A's key 2 105 345 is past, a maximum of D+ that only tile 257
+    holds"""
+    (Ta, nca), (Tb, ncb) = BIG_A, BIG_B
+    NA, NB, (PA, PB) = Ta * nca, Tb * ncb, BIG_THIRD
+    idx = np.arange(NA, dtype=np.int64)
+    per, i = idx // PA, idx % PA
+    cb = np.minimum(PB, (i + 1) * PB // PA + 1)  # B's values at or before A's local key i
+    if variant == "tie":
+        at = 4000
+        cb = np.where(i <= at, np.minimum(cb, int(cb[at]) - 2), cb)
+    else:
+        at = 2105345 - 2 * PA
+        cb = np.where((per == 2) & (i <= at), np.minimum(cb, int(cb[at]) - 1), cb)
+    cB = per * PB + cb
+    assert (np.diff(cB) >= 0).all() and cB[-1] == NB
+    pos_a = idx + cB
+    taken = np.zeros(NA + NB, bool)
+    taken[pos_a] = True
+    pos_b = np.flatnonzero(~taken)
+    assert pos_b.size == NB
+    return rng.permutation((pos_a - 1200000) / 1024.0).astype(np.float32), rng.permutation((pos_b - 1200000) / 1024.0).astype(np.float32)
+
+
+def big_sides():
+    rng = np.random.default_rng(20)
+    cols = [planted_columns(v, rng) for v in BIG_VARIANTS]
+    return np.stack([c[0] for c in cols], axis=1), np.stack([c[1] for c in cols], axis=1)
+
+
+def big_reference(a, sa, b, sb):
+    """compare_ref.restate's dict of a against b, with distances_numpy for the distances and the sides' rows_summary sa, sb"""
+    out = {f: [] for f in R.FIELDS}
+    for c in range(a.shape[1]):
+        r = R.distances_numpy(a[:, c], b[:, c])
+        r.update(mean_a=sa["mean"][c], sd_a=sa["sd"][c], ess_a=sa["ess"][c], mean_b=sb["mean"][c], sd_b=sb["sd"][c], ess_b=sb["ess"][c],
+                 na=a.shape[0], nb=b.shape[0], flags=0)
+        r["z_mean"] = R.z_mean(r["mean_a"], r["sd_a"], r["ess_a"], r["mean_b"], r["sd_b"], r["ess_b"])
+        r["ks_neff"], r["ks_p"] = R.ks_prob(r["ks"], r["ess_a"], r["ess_b"])
+        for f in R.FIELDS:
+            out[f].append(r[f])
+    ints = ("ks_plus_num", "ks_minus_num", "na", "nb")
+    return {f: np.array(v, np.int64 if f in ints else np.int32 if f == "flags" else np.float64) for f, v in out.items()}
+
+
+def test_a_side_beyond_256_tiles():
+    from mcpar_amd import engine as E
+    (Ta, nca), (Tb, ncb) = BIG_A, BIG_B
+    NA, NB = Ta * nca, Tb * ncb
+    g = E.debug_compare_store_geometry(Ta, nca, Tb, ncb, 2)
+    assert (g["tile_keys"], g["block"], g["tiles_a"], g["tiles_b"]) == (K.TILE, 256, 258, 37)
+    assert (g["sort_tiles_a"], g["sort_tiles_b"]) == (258, 37) and g["sort_tiles_a"] > 256 >= g["sort_tiles_b"]  # A's scans carry
+    assert (g["bounds_workgroups_a"], g["bounds_workgroups_b"]) == (2, 1)
+    assert (g["step_chunk_a"], g["step_chunk_b"]) == (65, 64) and (g["grid_y_a"], g["grid_y_b"]) == (-(-Ta // 65), -(-Tb // 64))
+    assert g["tiles_a"] > g["block"] >= g["tiles_b"]  # lanes 0 and 1 of k_cmp_reduce take two tiles of A, none two of B
+    swapped_g = E.debug_compare_store_geometry(Tb, ncb, Ta, nca, 2)
+    assert (swapped_g["tiles_a"], swapped_g["bounds_workgroups_b"], swapped_g["step_chunk_b"]) == (37, 2, 65)
+    a, b = big_sides()
+    # the reference alone: where the maxima of D+ lie
+    plus = []
+    for c, variant in enumerate(BIG_VARIANTS):
+        ka, kb = np.sort(R.ckey(a[:, c])), np.sort(R.ckey(b[:, c]))
+        d = np.arange(1, NA + 1, dtype=np.int64) * NB - np.searchsorted(kb, ka, "right").astype(np.int64) * NA
+        top = np.flatnonzero(d == d.max())
+        plus.append((int(d.max()), R.key_value(ka[top[:1]])[0]))
+        if variant == "tie":
+            assert (top // K.TILE).tolist() == [0, 86, 171] and np.diff(top).tolist() == [BIG_THIRD[0]] * 2 and d.max() > 0
+            assert len({int(v) % 256 for v in top // K.TILE}) == 3  # three lanes of the reducer
+        else:
+            assert (top // K.TILE).tolist() == [257] and d[K.TILE:2 * K.TILE].max() < d.max()  # tile 1, the same lane, holds less
+    sa, sb = E.rows_summary(a, Ta, nca), E.rows_summary(b, Tb, ncb)
+    for x, Tx, ncx, sx, y, Ty, ncy, sy, order in ((a, Ta, nca, sa, b, Tb, ncb, sb, "A, B"), (b, Tb, ncb, sb, a, Ta, nca, sa, "B, A")):
+        ref = big_reference(x, sx, y, sy)
+        side = "ks_plus" if order == "A, B" else "ks_minus"
+        assert [(int(n), v) for n, v in zip(ref[side + "_num"], ref[side + "_x"])] == plus  # the lowest position of the maximum
+        got = E.compare_rows(x, Tx, ncx, y, Ty, ncy)
+        worst = R.check(got, ref)
+        print("beyond 256 tiles, %s: largest relative difference of w1 %.3g" % (order, worst))
+        for f, s_, k in (("mean_a", sx, "mean"), ("sd_a", sx, "sd"), ("ess_a", sx, "ess"), ("mean_b", sy, "mean"), ("sd_b", sy, "sd"),
+                         ("ess_b", sy, "ess")):
+            assert got[f].tobytes() == np.asarray(s_[k], np.float64).tobytes(), (order, f)

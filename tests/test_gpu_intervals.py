@@ -9,7 +9,15 @@ quantiles; s_lo, s_hi and mcse_q exactly those of numpy's sort.  The launch geom
 Shapes: the smallest that cross each switch -- the minimum (1, 2, 4); (3, 5, 8); (17, 37, 24) sorted four columns at a time; and
 seven columns of N = three window tiles and 77 more, with spans that stay inside a tile, cross one tile edge and cross two, the
 span 0 and the span N - 1, and columns made so that the least window is tied everywhere, lies in the last tile, or is tied between
-two tiles."""
+two tiles.
+
+The HUGE case (one chain of 2 105 349 steps) crosses what those do not reach: 515 window tiles, so that a lane of k_hdi_reduce
+takes tiles t, t + 256 and t + 512; 258 sort tiles (the second carry step of the sort's scans); a step chunk of 65.  Its HDI
+fields, q, the ranks, s_lo, s_hi and mcse_q are held as above, through intervals_ref.check.  summary_ref on three transformed
+columns of that length costs more than the few seconds a test may take, so ess_sd, ess_q, their lags and mcse_sd are held by
+intervals_ref.check's tolerances against rows_summary of the transformed columns (float((x - mean)^2) and the indicator x <= q,
+built as intervals_ref.restate_column builds them, in one call beside the columns themselves: a summary of one chain of two
+million steps costs the library a second, however many columns); mean and sd against numpy's float64 at check's 1e-9."""
 import numpy as np
 import pytest
 
@@ -25,7 +33,22 @@ BIG_N = BIG_T * BIG_NC
 
 
 def make_rows(np_, nc, T, seed=11, stay=0.7):
-    """skewed rows (lognormal parameters, log L below zero), column 1 rounded to one decimal, repeated with probability stay"""
+    """skewed rows (lognormal parameters, log L below zero), column 1 rounded to one decimal, repeated with probability stay.
+    make_rows_loop without its loop over the steps and with the same draws (a Generator fills one [T - 1, nc] request as it
+    fills T - 1 requests of nc): a row is the last row at or before it that was not a repeat.  tests/test_intervals_cpu.py pins
+    the two to each other"""
+    rng = np.random.default_rng([seed, np_, nc, T])
+    a = rng.lognormal(0.0, 0.7, (T, nc, np_ + 1)).astype(np.float32)
+    a[:, :, -1] = -a[:, :, -1]
+    if np_ > 1:
+        a[:, :, 1] = np.round(a[:, :, 1], 1)
+    rep = np.concatenate([np.zeros((1, nc), bool), rng.random((T - 1, nc)) < stay])
+    src = np.maximum.accumulate(np.where(rep, 0, np.arange(T)[:, None]), axis=0)
+    return a[src, np.arange(nc)[None, :]].reshape(T * nc, np_ + 1)
+
+
+def make_rows_loop(np_, nc, T, seed=11, stay=0.7):
+    """make_rows step by step: the definition"""
     rng = np.random.default_rng([seed, np_, nc, T])
     a = rng.lognormal(0.0, 0.7, (T, nc, np_ + 1)).astype(np.float32)
     a[:, :, -1] = -a[:, :, -1]
@@ -182,3 +205,65 @@ def test_the_three_owners_and_a_second_call_give_the_same_bytes():
     ms = eg.intervals_times(HDI, PROBS, first_step=first, nsteps=nsteps)
     assert ms.shape == (12,) and (ms >= 0).all() and ms[11] >= ms[:11].sum() * 0.99 > 0
     eg.close()
+
+
+# ---- more window tiles than lanes of the reducer, more sort tiles than a scan step ------------------------------------------------
+HUGE_T = 2105349
+HUGE_TILES = (3, 259, 300)  # equal runs of quarter gaps: tiles 3 and 259 are one lane's of k_hdi_reduce, 300 another's
+HUGE_SPANS = (40, 1000)
+HUGE_PROBS = (0.5,)
+
+
+def huge_rows():
+    """two columns of one chain.  0: a fixed shuffle of a sorted column of unit gaps with 3000 quarter gaps from key 500 of each
+    of HUGE_TILES on (every value a multiple of 1 / 4 below 2^22: exact); log L: Metropolis-like"""
+    rows = make_rows(1, 1, HUGE_T, seed=13)
+    g = np.ones(HUGE_T)
+    for t in HUGE_TILES:
+        g[t * WT + 500:t * WT + 3500] = 0.25
+    rows[np.random.default_rng(19).permutation(HUGE_T), 0] = np.cumsum(g).astype(np.float32)
+    return rows
+
+
+def test_more_window_tiles_than_reducer_lanes():
+    from mcpar_amd import engine as E
+    T, nc, N = HUGE_T, 1, HUGE_T
+    masses = tuple(span_mass(m, N) for m in HUGE_SPANS) + (0.9,)
+    g = E.debug_intervals_geometry(T, nc, 1, len(masses), len(HUGE_PROBS))
+    assert (g["block"], g["window_tile"], g["window_tiles"], g["sort_tiles"]) == (256, WT, 515, 258)
+    assert (g["step_chunk"], g["grid_y"], g["reduce_workgroups"], g["transforms"]) == (65, -(-T // 65), 3, 2)
+    assert g["window_tiles"] > 2 * g["block"] and g["sort_tiles"] > 256 and g["groups"] == 1
+    rows = huge_rows()
+    # the reference alone: the HDI of numpy's sort, and where column 0's narrowest windows tie
+    ref = []
+    for c in (0, 1):
+        srt = R.sorted_values(rows[:, c])
+        hd = [dict(zip(("lo", "hi", "width", "index", "span"), R.hdi(srt, p))) for p in masses]
+        ref.append(dict(flags=0, sorted=srt, hdi=hd))
+    s0 = ref[0]["sorted"].astype(np.float64)
+    for h, m in zip(ref[0]["hdi"], HUGE_SPANS):
+        w = s0[m:] - s0[:N - m]
+        tied = np.flatnonzero(w == w.min())
+        assert h["span"] == m and h["width"] == m / 4 == w.min() and h["index"] == tied[0] == HUGE_TILES[0] * WT + 499
+        assert sorted(set((tied // WT).tolist())) == list(HUGE_TILES)  # the reference sees the tie: one lane's two tiles, and another's
+    assert ref[0]["hdi"][2]["index"] == 0 and ref[0]["hdi"][2]["span"] == int(0.9 * N)  # every window over all three runs ties
+    assert ref[1]["hdi"][0]["index"] > 0
+    got = E.rows_intervals(rows, T, nc, masses, HUGE_PROBS)
+    # the mixing numbers: one rows_summary of the columns and the transformed columns (six series, six lanes' work).  The
+    # transforms are restate_column's: about numpy's float64 mean, and at the median, which for an odd N is an order statistic
+    x = rows.astype(np.float64)
+    assert N % 2 == 1 and HUGE_PROBS == (0.5,)
+    q = np.array([float(ref[c]["sorted"][(N - 1) // 2]) for c in (0, 1)])
+    c2 = ((x - x.mean(axis=0)[None, :]) ** 2).astype(np.float32)
+    ind = (x <= q[None, :]).astype(np.float32)
+    st = E.rows_summary(np.concatenate([rows, c2, ind], axis=1), T, nc, HUGE_PROBS)
+    assert not st["flags"].any() and st["quantiles"][:2, 0].tolist() == q.tolist()
+    for c in (0, 1):
+        ref[c].update(mean=x[:, c].mean(), sd=x[:, c].std(ddof=1), ess_sd=st["ess"][2 + c], ess_sd_lag=st["ess_lag"][2 + c],
+                      mcse_sd=R.mcse_sd(N, st["mean"][2 + c], st["sd"][2 + c], st["ess"][2 + c]),
+                      quantiles=[dict(q=q[c], ess_q=st["ess"][4 + c], ess_q_lag=st["ess_lag"][4 + c])])
+        assert np.isfinite(ref[c]["ess_sd"]) and np.isfinite(st["ess"][4 + c])
+    R.check(got, ref, HUGE_PROBS)
+    assert got["quantiles"]["q"].tobytes() == st["quantiles"][:2].tobytes()
+    for c in (0, 1):  # the ranks are decided well clear of the error of u
+        assert R.rank_margin(N, HUGE_PROBS[0], float(got["quantiles"]["ess_q"][c, 0])) > 1e-3

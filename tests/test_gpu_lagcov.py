@@ -17,6 +17,9 @@ What is held:
             f_jj / Lambda_jj + e_jj / Sigma_jj, mcse_j by half of e_jj / Sigma_jj
   bytes     two calls, the engine and rows_lagcov of its copied rows, and a derived store of them give the same bytes; the lags
             computed on demand give the bytes of a call that computes every lag
+  units     more units than workgroups (BIG): a workgroup's second and third unit and the last unit's tail at the windows, the
+            same at lag 0, with every tile pair of four tiles; the same bound (it grows with N), the reference on max_lag + 1
+            lags only; a NaN in a row that only a second-round unit reads
 The launch geometry is asserted before each result."""
 import numpy as np
 import pytest
@@ -246,4 +249,100 @@ def test_the_three_owners_and_a_second_call_give_the_same_bytes():
     assert whole["N"] == 30 * eg.nc and R.same(E.rows_lagcov(eg.samples, 30, eg.nc, nlags=5), whole)
     ms, lags = eg.lagcov_times(first_step=first, nsteps=nsteps)
     assert ms.shape == (5,) and (ms >= 0).all() and ms[4] >= ms[:4].sum() * 0.99 > 0 and 2 <= lags <= nsteps
+    eg.close()
+
+
+# ---- more units than workgroups: the loop of k_lagcov, unit += workgroups, at the windows and at lag 0 ---------------------------
+# shape -> (lags computed, units, workgroups, units of lag 0, workgroups of lag 0)
+BIG = {(3, 37, 887): (17, 1026, 512, 257, 257),     # workgroups 0 and 1 take three units, the last unit has 19 rows; lag 0 below its cap
+       (3, 7, 74917): (9, 16389, 512, 4098, 2048),  # lag 0: workgroups 0 and 1 take three units
+       (49, 7, 4701): (17, 1029, 32, 258, 128)}     # four tiles: 16 pairs at the windows, 10 at lag 0, the off-diagonal launches
+
+
+def big_case(shape, with_ll=False):
+    """(rows, the reference on the lags the call computes), made once"""
+    np_, nc, T = shape
+    if ("rows", shape) not in CACHE:
+        CACHE["rows", shape] = R.dependent_rows(np_, nc, T)
+    rows = CACHE["rows", shape]
+    if (shape, with_ll) not in CACHE:
+        CACHE[shape, with_ll] = R.restate(rows, T, nc, max_lag=BIG[shape][0] - 1, with_ll=with_ll)
+    return rows, CACHE[shape, with_ll]
+
+
+def check_big_geometry(shape):
+    np_, nc, T = shape
+    nl, units, wgs, units0, wgs0 = BIG[shape]
+    g = check_geometry(np_, nc, T, nl)
+    nt, N = (np_ + 15) // 16, T * nc
+    assert (g["units"], g["workgroups"], g["units_lag0"], g["workgroups_lag0"]) == (units, wgs, units0, wgs0)
+    assert g["units_lag0"] == -(-N // (4 * UNIT)) and g["workgroups_lag0"] == min(units0, 4 * max(32, WG_MAX // nt ** 2))
+    assert g["lags_computed"] == nl and g["launches"] == 1 + -(-(nl - 1) // W)
+    return g
+
+
+@pytest.mark.parametrize("shape", sorted(BIG), ids=str)
+def test_more_units_than_workgroups(shape):
+    from mcpar_amd import engine as E
+    np_, nc, T = shape
+    nl = BIG[shape][0]
+    g = check_big_geometry(shape)
+    if shape == (3, 37, 887):
+        assert g["units"] == 2 * g["workgroups"] + 2 and T * nc - (g["units"] - 1) * UNIT == 19 and g["units_lag0"] == g["workgroups_lag0"]
+    if shape == (3, 7, 74917):
+        assert g["units_lag0"] == 2 * g["workgroups_lag0"] + 2 and g["units"] > 2 * g["workgroups"]
+    if shape == (49, 7, 4701):
+        assert (g["tiles"], g["pairs"], g["pairs_lag0"]) == (4, 16, 10) and g["units"] > 32 * g["workgroups"]
+        assert g["units_lag0"] == 2 * g["workgroups_lag0"] + 2
+    for with_ll in ((False, True) if shape == (49, 7, 4701) else (False,)):
+        rows, ref = big_case(shape, with_ll)
+        assert ref["flags"] == R.TRUNCATED and ref["s"] == 0 and ref["k_used"] == (nl - 2) // 2
+        got = E.rows_lagcov(rows, T, nc, max_lag=nl - 1, nlags=nl, with_ll=with_ll)
+        assert got["lags_computed"] == nl and got["gamma"].shape == (nl, np_ + 1, np_ + 1) and got["p"] == np_ + with_ll
+        held(got, ref, rows, T, nc, with_ll=with_ll, where="%s%s" % (shape, " with log L" if with_ll else ""))
+
+
+def test_a_nan_in_a_second_round_unit():
+    """row 20000 of the first BIG shape lies in unit 625 = 512 + 113, and every unit that reads it as a partner (rows from 20000 -
+    16 * 37 on) is a second-round unit too; at lag 0 every unit is a first unit"""
+    from mcpar_amd import engine as E
+    shape = (3, 37, 887)
+    np_, nc, T = shape
+    nl = BIG[shape][0]
+    g = check_big_geometry(shape)
+    row, col = 20000, 1
+    first_reader, last_reader = (row - (nl - 1) * nc) // UNIT, row // UNIT
+    assert g["workgroups"] <= first_reader and last_reader < 2 * g["workgroups"] and g["units_lag0"] == g["workgroups_lag0"]
+    rows, _ = big_case(shape)
+    clean = E.rows_lagcov(rows, T, nc, max_lag=nl - 1, nlags=nl)
+    bad = rows.copy()
+    bad[row, col] = np.nan
+    got = E.rows_lagcov(bad, T, nc, max_lag=nl - 1, nlags=nl)
+    assert got["col_flags"].tolist() == [0, R.NONFINITE, 0, 0] and got["p"] == 2
+    assert np.isnan(got["gamma"][:, col, :]).all() and np.isnan(got["gamma"][:, :, col]).all() and np.isnan(got["mean"][col])
+    keep = [0, 2, 3]
+    assert np.isfinite(got["gamma"][:, keep][:, :, keep]).all()
+    assert got["gamma"][:, keep][:, :, keep].tobytes() == clean["gamma"][:, keep][:, :, keep].tobytes()
+    assert got["mean"][keep].tobytes() == clean["mean"][keep].tobytes()
+    check_gamma(got, R.restate(bad, T, nc, max_lag=nl - 1), T * nc, "a NaN in unit %d" % last_reader)
+
+
+def test_the_three_owners_give_the_same_bytes_beyond_one_unit_per_workgroup():
+    from mcpar_amd import engine as E
+    shape = (3, 37, 887)
+    np_, nc, T = shape
+    nl = BIG[shape][0]
+    check_big_geometry(shape)
+    first = 3
+    eg = run(nc, np_, first + T)
+    rows = eg.samples_range(first, T)
+    on_engine = eg.lagcov(max_lag=nl - 1, nlags=nl, first_step=first, nsteps=T)
+    ref = R.restate(rows, T, nc, max_lag=nl - 1)
+    check_gamma(on_engine, ref, T * nc, "engine sub-range, %s" % (shape,))
+    use = R.use_of(ref["col_flags"] & R.NONFINITE, False)
+    R.check_finish(on_engine, R.finish(on_engine["gamma"], T * nc, use), rtol=1e-9, where="engine sub-range: ")
+    assert R.same(E.rows_lagcov(rows, T, nc, max_lag=nl - 1, nlags=nl), on_engine)
+    st = E.select_chains_rows(rows, T, nc, list(range(nc)))
+    assert R.same(st.lagcov(max_lag=nl - 1, nlags=nl), on_engine)
+    st.close()
     eg.close()

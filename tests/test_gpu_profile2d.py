@@ -1,6 +1,8 @@
 """Pair profile likelihoods of the sample store on the GPU against tests/profile_ref.py: cnt, row, the
 counts, the flags and the level counts equal, the bits of lmax, xat_a, xat_b, lhat, xhat, from and to equal, z to 1e-12 relative.
-Values and log L are made of small integers, so that every cell has ties."""
+Values and log L are made of small integers, so that every cell has ties.  The last case has more rows than k_profile_keys
+has lanes (4096 workgroups of 256): the rows from 2^20 on are those of a lane's second turn, and some of them are made the only
+maximum of their cell, so that their keys show in row and lmax."""
 import numpy as np
 import pytest
 
@@ -123,3 +125,33 @@ def test_engine_rows_and_store_give_the_same_bytes():
     inner = eg.profile_likelihood2d(g=8, pairs=[(3, 0)], first_step=3, nsteps=11)
     check(inner, R.profile2d(eg.samples_range(3, 11), g=8, pairs=[(3, 0)]))
     eg.close()
+
+
+def test_more_rows_than_lanes_of_the_key_sweep():
+    """N = 1 048 833 > 4096 * 256: k_profile_keys walks a grid stride.  The highest log L sits in row N - 5 and, equal, in row
+    700 001: the earlier row is the maximum; row N - 5 is the maximum of its own cell, and ten more rows of the second turn are
+    their cells' only maxima"""
+    from mcpar_amd import engine as E
+    np_, nc, T, g = 2, 3, 349611, 8
+    N = T * nc
+    geo = E.debug_profile_geometry(np_, T, nc, 7, g=g, npairs=1)
+    first_turn = geo["keys_max_workgroups"] * geo["block"]
+    assert (geo["keys_workgroups"], geo["keys_max_workgroups"], geo["block"]) == (4096, 4096, 256) and N == 1048833 > first_turn
+    assert geo["pair_chunks"] == 17
+    rows = int_rows(15, T, nc, np_)
+    early, late = 700001, N - 5
+    assert early < first_turn <= late
+    rows[early] = (-2.25, -2.25, 1.0)
+    rows[late] = (2.25, 2.25, 1.0)
+    second = first_turn + 23 * np.arange(10)  # rows of the second turn: above every row's log L but those two, in ten cells
+    rows[second, 0] = -2.25 + 0.5 * np.arange(10).clip(0, 8)
+    rows[second, 1] = 2.25 - 0.5 * (np.arange(10) % 3)
+    rows[second, 2] = 0.25
+    ref = R.profile2d(rows, g=g, pairs=[(0, 1)], drops=DROPS)
+    # the reference alone: which row it picks, and that rows of the second turn decide cells
+    assert (ref["row_hat"] == early).all() and ref["row"][0, 0, 0] == early and ref["row"][0, g - 1, g - 1] == late
+    assert ref["lmax"][0, 0, 0] == ref["lmax"][0, g - 1, g - 1] == 1.0
+    won = np.intersect1d(ref["row"][0].reshape(-1), second)
+    assert won.size >= 8 and (ref["row"][0] >= first_turn).sum() == won.size + 1 and ref["nbinned"][0] == N
+    got = E.rows_profile2d(rows, T, nc, g=g, pairs=[(0, 1)], drops=DROPS)
+    check(got, ref, "beyond 2^20 rows")

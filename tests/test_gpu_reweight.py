@@ -9,7 +9,10 @@ library's own q:
   mean        1e-10 of sum q |x| / Q: the fixed-order bound N 2^-53 with N <= 2^17 in these cases (2^18 in the k-hat anchor,
               whose columns are not what it is about), as in section 20's argument
   sd, mcse    1e-9 relative, plus the mean's bound (an error d of the mean moves either by at most d)
-  ess_kish, log_mean_w   1e-14 relative;  khat, tail_sigma   1e-9"""
+  ess_kish, log_mean_w   1e-14 relative;  khat, tail_sigma   1e-9
+The two BIG cases cross what the others do not reach: k_rw_scan lanes that own three and nine tiles and lanes that own none,
+k_rw_maxred beyond 256 tiles, a second histogram step chunk, the sort of q beyond 256 sort tiles and k_rw_draw's search over such
+an offset table.  They keep the rules above (the mean's 1e-10 too, which is now below N 2^-53 = 2.3e-10 and so asks more)."""
 import math
 
 import numpy as np
@@ -430,3 +433,54 @@ def test_resample_then_analyse():
     assert c["ks_p"][0] > 0.001
     a.close()
     b.close()
+
+
+# ---- more scan tiles than lanes, more steps than a histogram chunk, more sort tiles than a scan step -----------------------------
+# (nc, np, T) -> scan tiles, tiles per lane of k_rw_scan, the first lane that owns none, histogram step chunks, sort tiles,
+# whether rows 2^17 .. 2^17 + 2^18 have q = 0 (256 scan tiles: lanes 43 .. 127 sum to zero), the resample's seed
+BIG = {(8, 1, 65537): (513, 3, 171, 2, 65, True, 1), (3, 1, 701783): (2057, 9, 229, 11, 258, False, 1)}
+BIG_K = 600
+
+
+def big_logw(nc, T, zeros):
+    logw = spread_logw(T * nc) * np.float32(1.0 / 3.0)
+    if zeros:
+        logw[2 ** 17:2 ** 17 + 2 ** 18] = -INF
+    return logw
+
+
+def lane_stretches(index, tiles, per):
+    """the lanes of k_rw_scan whose tiles the drawn rows lie in, and the last lane that owns a tile"""
+    return set((np.asarray(index) // RS // per).tolist()), (tiles - 1) // per
+
+
+@pytest.mark.parametrize("shape", sorted(BIG), ids=str)
+def test_more_tiles_than_lanes(shape):
+    from mcpar_amd import engine as E
+    nc, np_, T = shape
+    tiles, per, idle, chunks, stiles, zeros, seed = BIG[shape]
+    N = T * nc
+    g = E.debug_reweight_store_geometry(T, nc, np_ + 1, len(PROBS), BIG_K)
+    assert (g["block"], g["scan_tile_rows"], g["scan_tiles"], g["scan_tiles_per_lane"]) == (256, RS, tiles, per)
+    assert tiles > g["block"] and per == -(-tiles // 256) and idle == -(-tiles // per) and (idle < 256 or tiles - 228 * per == 5)
+    assert g["hist_step_chunks"] == chunks == -(-T // 65536) and g["sort_tiles"] == stiles and g["draw_workgroups"] == 3
+    if chunks == 2:
+        assert T - 65536 == 1  # the second chunk holds one step
+    assert g == dict(E.debug_reweight_geometry(N, np_ + 1, len(PROBS), BIG_K), hist_step_chunks=chunks)
+    rows = make_rows(nc, np_, T)
+    logw = big_logw(nc, T, zeros)
+    lw = R.log_weights(logw, 1.0)
+    # the reference alone: the draws fall in tiles of the first, a middle and the last lane stretch
+    lanes, last = lane_stretches(R.resample_index(R.fixed_point(lw)[0], seed, BIG_K)[0], tiles, per)
+    assert 0 in lanes and last in lanes and last == idle - 1 and any(0 < v < last for v in lanes), sorted(lanes)
+    w = E.weights_host(logw)
+    q, lwmax = held_q(w, rows, T, nc, lw, str(shape))
+    if zeros:
+        assert not q[2 ** 17:2 ** 17 + 2 ** 18].any() and q[2 ** 17 - 1] > 0 and q[2 ** 17 + 2 ** 18] > 0
+    got = E.reweight_rows(rows, T, nc, w, PROBS)
+    ref = R.restate(rows, q, lwmax, PROBS)
+    assert ref["tail_m"] >= 5 and not math.isnan(ref["khat"]) and ref["nzero"] >= (2 ** 18 if zeros else 0)
+    held(got, ref, str(shape))
+    index = resample_held(w, rows, T, nc, q, BIG_K, seed, str(shape))
+    lanes, last = lane_stretches(index, tiles, per)
+    assert 0 in lanes and last in lanes and any(0 < v < last for v in lanes)

@@ -302,3 +302,12 @@ def test_host_code_under_sanitizers(tmp_path):
                     os.path.join(ROOT, "tests", "cpp", "intervals_host_check.cc"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_make_rows_without_its_loop_gives_the_loop_s_rows():
+    """tests/test_gpu_intervals.py's make_rows (also lagcov_ref.dependent_rows') against its step-by-step definition"""
+    from test_gpu_intervals import make_rows, make_rows_loop
+    for a in ((1, 2, 4), (3, 5, 8), (17, 37, 24), (6, 2473, 5), (1, 1, 300), (1, 1, 1), (3, 37, 64)):
+        assert make_rows(*a).tobytes() == make_rows_loop(*a).tobytes(), a
+    assert make_rows(3, 7, 50, seed=13, stay=0.4).tobytes() == make_rows_loop(3, 7, 50, seed=13, stay=0.4).tobytes()
+    assert make_rows(2, 3, 40, stay=0.0).tobytes() == make_rows_loop(2, 3, 40, stay=0.0).tobytes()

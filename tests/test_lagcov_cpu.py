@@ -191,7 +191,7 @@ def test_geometry_of_the_gpu_shapes_and_on_both_sides_of_every_switch():
             E.debug_lagcov_geometry(*a)
         assert ei.value.code == 1
     assert load().mcx_debug_lagcov_geometry(4, 2, 1, 1, None) == 1
-    assert C.sizeof(LagcovGeometry) == 13 * 8
+    assert C.sizeof(LagcovGeometry) == 15 * 8
 
 
 # ---- the header and the host half on their own ------------------------------------------------------------------------------------

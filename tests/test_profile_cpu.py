@@ -31,7 +31,7 @@ def test_entry_points_are_declared_and_exported_and_the_abi_is_5():
     for name in ("mcx_profile_spec", "mcx_col_profile", "mcx_profile_interval_t", "mcx_profile2d_spec", "mcx_pair_profile", "mcx_profile_geometry"):
         assert "} %s;" % name in header, name
     assert L.mcx_abi_version() == 5 and "#define MCX_ABI_VERSION 5" in header
-    assert C.sizeof(ProfileSpecC) == 64 and C.sizeof(Profile2dSpecC) == 80 and C.sizeof(ProfileGeometry) == 16 * 8
+    assert C.sizeof(ProfileSpecC) == 64 and C.sizeof(Profile2dSpecC) == 80 and C.sizeof(ProfileGeometry) == 18 * 8
     assert (E.PROFILE_LL_NONFINITE, E.PROFILE_OPEN_LO, E.PROFILE_OPEN_HI, E.PROFILE_NO_BIN, E.PROFILE_HULL_OPEN_LO, E.PROFILE_HULL_OPEN_HI) == \
         (R.LL_NONFINITE, R.OPEN_LO, R.OPEN_HI, R.NO_BIN, R.HULL_OPEN_LO, R.HULL_OPEN_HI) == (2, 4, 8, 16, 32, 64)
     assert E.PROFILE_INTERVAL_DTYPE == R.INTERVAL_DTYPE and E.PROFILE_MAX_LEVELS == R.MAX_LEVELS == 8
@@ -285,7 +285,7 @@ def test_header_is_plain_c99_with_the_profile_declarations(tmp_path):
                    ' if (mcx_store_profile(0, &sp, 0, 0, 0, 0, 0, 0, 0, 0, 0) != MCX_ERR_INVALID) return 6;\n'
                    ' if (mcx_samples_profile2d(0, 0, 2, &s2, 0, 0, 0, 0, 0, 0, 0, 0, 0) != MCX_ERR_INVALID) return 7;\n'
                    ' if (sizeof(mcx_profile_spec) != 64 || sizeof(mcx_profile2d_spec) != 80 || sizeof(mcx_col_profile) != 72) return 8;\n'
-                   ' if (sizeof(mcx_profile_interval_t) != 56 || sizeof(mcx_pair_profile) != 24 || sizeof(g) != 128) return 9;\n'
+                   ' if (sizeof(mcx_profile_interval_t) != 56 || sizeof(mcx_pair_profile) != 24 || sizeof(g) != 144) return 9;\n'
                    ' if (MCX_PROFILE_MAX_LEVELS != 8 || MCX_PROFILE_LL_NONFINITE != 2 || MCX_PROFILE_OPEN_LO != 4 || MCX_PROFILE_NO_BIN != 16) return 10;\n'
                    ' return mcx_abi_version() == MCX_ABI_VERSION && MCX_ABI_VERSION == 5 ? 0 : 1; }\n')
     exe = tmp_path / "profile_cabi"

@@ -299,3 +299,12 @@ def test_host_code_under_sanitizers(tmp_path):
                     os.path.join(ROOT, "tests", "cpp", "reweight_host_check.cc"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_integer_sums_without_the_loop_are_the_loop_s():
+    """reweight_ref.integer_sums (what restate() uses, for the cases of millions of rows) against the row-by-row definition"""
+    rng = np.random.default_rng(23)
+    for q in (rng.integers(0, 2 ** 31 + 1, 5000), np.full(3000, 2 ** 31), np.zeros(7), np.array([2 ** 32 - 1] * 100 + [0, 1]),
+              np.where(rng.random(4000) < 0.5, 0, rng.integers(0, 2 ** 31 + 1, 4000))):
+        q = np.asarray(q, np.uint32)
+        assert R.integer_sums(q) == R.integer_sums_slow(q)
